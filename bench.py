@@ -11,7 +11,15 @@ i.e. per step: 1 target voxel-map build (from the reused covariances) + covarian
 fvh_vgicp_set_source_cloud (one H2D inside the timed region): the PCIe-inclusive, reference-exact rate, measured in the same run.
 
 N = 1 headline workload (BASELINE.json configs[1]): bundled 251370668/251371071 pair (HEAD preprocessing, 17,047 / 17,334 pts),
-VGICP, DIRECT27, k_correspondences = 20, voxel resolution 1.0.  The default invocation also measures, time-boxed, the other
+VGICP, DIRECT27, k_correspondences = 20, voxel resolution 1.0.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) is lean: set-up, W warm-up steps, ONE timed region of exactly N steps, the
+result line. Everything else -- the repeats of the timed region, host_clouds_in, the pipelined and 100times legs, the concurrent
+streams, the profiled stages and rooflines, the cpu_baseline legs, the extra configurations below and, with N > 1, the replicas
+and the sharded detail -- runs with `--full` only. `--dump-outputs DIR` writes what the last timed step computed (the arrays a
+caller of the loop receives) as DIR/<name>.npy, so that two builds can be compared output for output on identical inputs.
+
+With `--full` the default invocation also measures, time-boxed, the other
 single-GPU configurations of BASELINE.json and reports them under "configs", each with its own roofline and cpu_baseline:
     synth100k_rbf  configs[2]  synthetic 100k <-> 100k, res 0.5, RBF covariances 0.5/2.5, DIRECT27
     synth1m        configs[4]  synthetic 1M-point map <-> 100k-point scan, res 0.5, DIRECT7 (1-GPU form of the sharded config)
@@ -24,8 +32,8 @@ single-registration path (all-reduce of the normal equations per evaluation) is 
 Output (rank 0): the LAST stdout line is ONE compact JSON object (< 4 KB: the contract's keys, `roofline`, `cpu_baseline`, one short
 entry per extra configuration -- compact_line()). The full detail (stages, thread sweeps, notes, per-route sharded detail) goes to
 bench_detail.json beside this script and to stderr, never to stdout.
-The timed region is run REPEATS times (each: exactly --steps steps between barrier + synchronize); `ms_per_step` / `value` are the median
-repeat, min / max are reported beside it.
+With `--full` the timed region is run REPEATS times (each: exactly --steps steps between barrier + synchronize); `ms_per_step` / `value`
+are the median repeat, min / max are reported beside it. A plain run times it once.
 """
 import argparse
 import json
@@ -66,7 +74,41 @@ def parse():
     ap.add_argument("--streams", type=int, default=4, help="extra leg: S independent engine handles (own HIP streams, host threads) running the same loop concurrently on this GPU")
     ap.add_argument("--cpu-loops", type=int, default=0, help="oracle registrations to time (0 = auto-bound)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU budget of the headline's cpu_baseline leg (thread sweep included)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: repeats of the timed region, side legs, profiled stages and rooflines, "
+                    "cpu_baseline, extra configurations (a plain run sets up, warms up, times --steps steps once and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64)")
+    args = ap.parse_args()
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs: single-GPU runs only")
+    return args
+
+
+def repeats_of(args):
+    """times the headline's timed region is run: REPEATS with --full, once in a plain run"""
+    return REPEATS if args.full else 1
+
+
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array (float32 stays float32, everything else becomes float64), 64 MB at most in all."""
+    os.makedirs(dirname, exist_ok=True)
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        out[name] = np.ascontiguousarray(a, np.float32 if a.dtype == np.float32 else np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT))
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def result_arrays(r):
+    """the arrays a caller of align() receives: pose, Hessian, and the scalars of the result as float64"""
+    return {"T": r["T"], "H": r["H"], "final_error": [r["final_error"]], "converged": [float(r["converged"])],
+            "nr_iterations": [r["nr_iterations"]], "num_linearize": [r["num_linearize"]], "num_error_evals": [r["num_error_evals"]]}
 
 
 def make_workload(name):
@@ -467,7 +509,8 @@ def sharded_headline(args, dist, rank, world, local_rank, dev, small=False):
         r = step()
     n_eval = n_launch = 0
     rep_times = []
-    for _rep in range(REPEATS):
+    n_rep = repeats_of(args)
+    for _rep in range(n_rep):
         barrier()
         t0 = time.perf_counter()
         for _ in range(steps):
@@ -477,32 +520,33 @@ def sharded_headline(args, dist, rank, world, local_rank, dev, small=False):
         barrier()
         rep_times.append(max_over_ranks(time.perf_counter() - t0))
     elapsed, el_min, el_max = median_of(rep_times)
-    n_regs = steps * REPEATS
+    n_regs = steps * n_rep
     # roofline of the dominant kernel (this rank's cost launches, HIP events on the engine's stream), on a few more steps outside the timed region
     roofline = None
-    try:
-        c.profile_reset(); c.profile_enable(2)
-        ne = 0
-        for _ in range(5):
-            rr = step()
-            ne += rr["num_linearize"] + rr["num_error_evals"]
-        c.profile_enable(0)
-        cost_ms, cost_n = c.profile_get("cost")
-        n_tile = -(-n_s // world)
-        n_c = c.get_num_correspondences()  # (sharded: the pairs of this rank's tile)
-        bytes_eval = n_tile * 48 + n_tile * 7 * 16 + n_c * 52 + 172
-        if cost_n:
-            achieved = ne * bytes_eval / (cost_ms * 1e-3) / 1e9
-            roofline = {"kernel": "cost_kernel<double,VGICP,%s> on this rank's tile (1 / %d of the scan)" % ("persistent" if cost_n == 5 else "per-transition", world), "bound": "hbm",
-                        "achieved": round(achieved, 2), "peak": 8000.0, "unit": "GB/s", "frac": round(achieved / 8000.0, 5), "traffic": None,
-                        "algorithmic_bytes_per_launch": int(bytes_eval * ne / cost_n), "algorithmic_bytes_per_evaluation": bytes_eval, "evaluations": ne, "launches": cost_n, "avg_launch_us": round(cost_ms / cost_n * 1e3, 3),
-                        "note": "rank 0; SURVEY 8(d) B_eval over the tile; no PMC pass exists for the sharded launches (traffic null)"}
-    except Exception as ex:  # noqa: BLE001
-        roofline = {"error": repr(ex)}
+    if args.full:
+        try:
+            c.profile_reset(); c.profile_enable(2)
+            ne = 0
+            for _ in range(5):
+                rr = step()
+                ne += rr["num_linearize"] + rr["num_error_evals"]
+            c.profile_enable(0)
+            cost_ms, cost_n = c.profile_get("cost")
+            n_tile = -(-n_s // world)
+            n_c = c.get_num_correspondences()  # (sharded: the pairs of this rank's tile)
+            bytes_eval = n_tile * 48 + n_tile * 7 * 16 + n_c * 52 + 172
+            if cost_n:
+                achieved = ne * bytes_eval / (cost_ms * 1e-3) / 1e9
+                roofline = {"kernel": "cost_kernel<double,VGICP,%s> on this rank's tile (1 / %d of the scan)" % ("persistent" if cost_n == 5 else "per-transition", world), "bound": "hbm",
+                            "achieved": round(achieved, 2), "peak": 8000.0, "unit": "GB/s", "frac": round(achieved / 8000.0, 5), "traffic": None,
+                            "algorithmic_bytes_per_launch": int(bytes_eval * ne / cost_n), "algorithmic_bytes_per_evaluation": bytes_eval, "evaluations": ne, "launches": cost_n, "avg_launch_us": round(cost_ms / cost_n * 1e3, 3),
+                            "note": "rank 0; SURVEY 8(d) B_eval over the tile; no PMC pass exists for the sharded launches (traffic null)"}
+        except Exception as ex:  # noqa: BLE001
+            roofline = {"error": repr(ex)}
     out = {
         "metric": "registrations/sec (one registration stream, every registration sharded over the GPUs by spatial tile; BASELINE configs[4])",
         "value": round(steps / elapsed, 3), "unit": "registrations/sec", "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": round(elapsed / steps * 1e3, 5),
-        "repeats": REPEATS, "ms_per_step_min": round(el_min / steps * 1e3, 5), "ms_per_step_max": round(el_max / steps * 1e3, 5),
+        "repeats": n_rep, "ms_per_step_min": round(el_min / steps * 1e3, 5), "ms_per_step_max": round(el_max / steps * 1e3, 5),
         "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
         "config": {"workload": "synthetic %s-point map <-> %s-point scan, seed %d: scan-to-map step (host scan in, k-NN k = 20, PLANE covariances, align)" % (
                        "{:,}".format(n_t), "{:,}".format(n_s), seed),
@@ -709,7 +753,7 @@ def concurrent_leg(args, local_rank, d_clouds, n_pts, res, search, K):
                                    "above adds each stream's sort / k-NN / covariance kernels, which wait for room beside the resident LM workgroups"}}
 
 
-def run_stream(args, steps, warmup, cpu_loops=15, frames_n=10):
+def run_stream(args, steps, warmup, cpu_loops=15, frames_n=10, dump=False):
     """BASELINE.json configs[3] (KITTI-style streaming, NDT D2D): the loop of src/kitti.cpp:95-128 with every stage on the
     device -- raw ~118k-point frame (resident in HBM) -> ApproximateVoxelGrid 0.25 (kitti.cpp:80-82) -> setInputSource ->
     align (NDTCuda defaults: D2D, DIRECT7, resolution 1.0) -> swapSourceAndTarget.  KITTI is not available offline: frames
@@ -774,13 +818,14 @@ def run_stream(args, steps, warmup, cpu_loops=15, frames_n=10):
             gt = np.linalg.inv(workloads.lidar_pose(i - 1)) @ workloads.lidar_pose(i)
             errs.append(workloads.pose_error(gt, state["last"]["T"])[0])
     state["k"] = F - 1
-    profile = not args.no_profile
+    profile = args.full and not args.no_profile
     ndt.profile_reset(); vg.profile_reset()
     ndt.profile_enable(False); vg.profile_enable(False)
     state["n_ds"] = 0
     n_eval = n_launch = 0
     rep_times = []
-    for _rep in range(REPEATS):
+    n_rep = repeats_of(args)
+    for _rep in range(n_rep):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for it in range(steps):
@@ -793,7 +838,9 @@ def run_stream(args, steps, warmup, cpu_loops=15, frames_n=10):
         rep_times.append(time.perf_counter() - t0)
         ndt.profile_enable(False)
     elapsed, el_min, el_max = median_of(rep_times)
-    n_regs = steps * REPEATS
+    n_regs = steps * n_rep
+    if dump and args.dump_outputs:
+        dump_outputs(args.dump_outputs, result_arrays(state["last"]))
     ndt.profile_enable(False); vg.profile_enable(False)
     stage_ms, roofline, roofline_ds = {}, None, None
     cost_sample = ndt.profile_get("cost") if profile else (0.0, 0)
@@ -852,7 +899,7 @@ def run_stream(args, steps, warmup, cpu_loops=15, frames_n=10):
                            "avg_launch_us": round(ms / n * 1e3, 3), "launches": n,
                            "note": "1.4 MB of input per frame: launch/latency bound (a chain of four dependent small kernels), not HBM bound; `traffic` = the four kernels' PMC bytes summed"}
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import oracle as O
         best = None
         sweep = {}
@@ -881,6 +928,8 @@ def run_stream(args, steps, warmup, cpu_loops=15, frames_n=10):
     try:
         if getattr(args, "no_pipelined_leg", False):
             raise RuntimeError("skipped (--no-pipelined-leg)")
+        if not args.full:
+            raise RuntimeError("skipped (--full only)")
         vg.share_stream(None)
         vg.share_prepare_stream(ndt)
         P = max(steps, 20)
@@ -924,7 +973,7 @@ def run_stream(args, steps, warmup, cpu_loops=15, frames_n=10):
         pipelined = {"error": repr(ex)}
     vg.close(); ndt.close()
     return {"pipelined": pipelined, "metric": "registrations/sec (frame-by-frame odometry, kitti.cpp loop incl. downsampling)", "value": round(steps / elapsed, 3), "unit": "registrations/sec", "n_gpus": 1,
-            "steps": steps, "warmup": warmup, "ms_per_step": round(elapsed / steps * 1e3, 5), "repeats": REPEATS, "ms_per_step_min": round(el_min / steps * 1e3, 5),
+            "steps": steps, "warmup": warmup, "ms_per_step": round(elapsed / steps * 1e3, 5), "repeats": n_rep, "ms_per_step_min": round(el_min / steps * 1e3, 5),
             "ms_per_step_max": round(el_max / steps * 1e3, 5), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f64" if args.precision == "fp64" else "f32", "data": "KITTI" if kitti_dir else "synthetic",
             "config": {"workload": "%s, %d raw pts/frame -> ApproximateVoxelGrid 0.25 -> %d pts; NDT D2D, DIRECT7, res 1.0; %d-frame sequence walked back and forth" % (
@@ -1013,7 +1062,7 @@ def run_registration(args, workload, cov, search_name, steps, warmup, local_rank
     for _ in range(warmup):
         step()
 
-    profile = not args.no_profile
+    profile = args.full and not args.no_profile
     # HIP-event bracketing costs ~20 % on a registration it is applied to: sample every 9th registration of the timed region
     # (odd on purpose: the loop alternates between the two directions of the pair, which need 6 and 8 LM transitions)
     PROFILE_EVERY = 9
@@ -1027,7 +1076,8 @@ def run_registration(args, workload, cov, search_name, steps, warmup, local_rank
 
     n_lin = n_err = n_launch = 0
     rep_times = []
-    for _rep in range(REPEATS):  # the timed region, REPEATS times: exactly `steps` steps between barrier + synchronize on both sides, max over the ranks
+    n_rep = repeats_of(args)
+    for _rep in range(n_rep):  # the timed region, n_rep times: exactly `steps` steps between barrier + synchronize on both sides, max over the ranks
         barrier()
         t0 = time.perf_counter()
         for it in range(steps):
@@ -1047,11 +1097,13 @@ def run_registration(args, workload, cov, search_name, steps, warmup, local_rank
             el = float(t.item())
         rep_times.append(el)
     elapsed, el_min, el_max = median_of(rep_times)
-    n_regs = steps * REPEATS  # registrations the per-registration counters were summed over
+    n_regs = steps * n_rep  # registrations the per-registration counters were summed over
+    if headline and args.dump_outputs:  # the last timed step: its result + the source covariances it estimated
+        dump_outputs(args.dump_outputs, dict(result_arrays(state["last"]), source_covariances=core.get_covariances("source")))
 
     # ---- align.cpp:73-83 "100times": clearTarget / clearSource / setInputTarget / setInputSource / align -- BOTH clouds from scratch per registration ----
     full_ms = None
-    if world == 1 and workload != "synth1m":
+    if args.full and world == 1 and workload != "synth1m":
         def full_step():
             core.set_target_cloud_device(d_ptrs[0], n_pts[0], 3)
             cloud_of["target"], cloud_of["source"] = 0, 1
@@ -1073,7 +1125,7 @@ def run_registration(args, workload, cov, search_name, steps, warmup, local_rank
 
     # ---- the same loop, host clouds in (PCIe-inclusive; never `value`) ----
     host_leg = None
-    if not args.no_host_leg and world == 1:
+    if args.full and not args.no_host_leg and world == 1:
         state["host"] = True
         for _ in range(2):
             step()
@@ -1090,7 +1142,7 @@ def run_registration(args, workload, cov, search_name, steps, warmup, local_rank
     # ---- the same loop as a two-stage pipeline: the next source (sort, k-NN, covariances, its voxel map) is prepared on the handle's
     #      second stream beside the running LM kernel (fvh_vgicp_prepare_source_device / align_async / align_wait); never `value` ----
     pipelined_leg = None
-    if not args.no_pipelined_leg and world == 1 and workload != "synth1m" and cov in ("knn", "rbf"):
+    if args.full and not args.no_pipelined_leg and world == 1 and workload != "synth1m" and cov in ("knn", "rbf"):
         rbf = cov == "rbf"
         PSTAGES = int(os.environ.get("BENCH_PIPE_STAGES", "2"))
         seq_T = {}
@@ -1187,13 +1239,13 @@ def run_registration(args, workload, cov, search_name, steps, warmup, local_rank
         stage_ms["rbf"]["roofline"] = valu_roofline(workload + "_rbf_rbf", "cov_rbf1_kernel (+ cov_rbf_finish_kernel)", stage_ms["rbf"]["avg_us"], n_src, n_src)
 
     cpu_res = None
-    if cpu and not args.no_cpu_baseline and world == 1:
+    if args.full and cpu and not args.no_cpu_baseline and world == 1:
         # (the 100k / 1M configurations prepare their clouds once per thread count: only 16 and 64 threads are tried there)
         counts = thread_counts() if workload == "bundled17k" else [t for t in thread_counts() if t in (16, 64)] or thread_counts()[-1:]
         cpu_res = cpu_baseline_vgicp(tgt, src, res, search_name, cov, cpu_budget, mode="map" if workload == "synth1m" else "reuse", counts=counts)
 
     conc = None
-    if headline and args.streams > 1 and world == 1 and cov == "knn" and workload != "synth1m":
+    if args.full and headline and args.streams > 1 and world == 1 and cov == "knn" and workload != "synth1m":
         try:
             conc = concurrent_leg(args, local_rank, d_clouds, n_pts, res, search, K)
         except Exception as ex:
@@ -1202,7 +1254,7 @@ def run_registration(args, workload, cov, search_name, steps, warmup, local_rank
     out = {
         "metric": "registrations/sec (100-iter reuse) + final fitness_score; achieved HBM GB/s",
         "value": round(total_regs / elapsed, 3), "unit": "registrations/sec", "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": round(elapsed / steps * 1e3, 5),
-        "repeats": REPEATS, "ms_per_step_min": round(el_min / steps * 1e3, 5), "ms_per_step_max": round(el_max / steps * 1e3, 5),
+        "repeats": n_rep, "ms_per_step_min": round(el_min / steps * 1e3, 5), "ms_per_step_max": round(el_max / steps * 1e3, 5),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64" if args.precision == "fp64" else "f32",
         "data": "bundled scans (real LiDAR)" if workload == "bundled17k" else "synthetic",
         "config": {"workload": desc, "method": "VGICP", "neighbor_search": search_name, "k_correspondences": K, "covariance": cov, "regularization": "PLANE",
@@ -1221,7 +1273,7 @@ def run_registration(args, workload, cov, search_name, steps, warmup, local_rank
     return out
 
 
-def run_fgicp(args, steps, warmup, local_rank=0):
+def run_fgicp(args, steps, warmup, local_rank=0, dump=False):
     """`bundled17k_fgicp`: FastGICP -- nearest-target-point correspondences instead of voxel lookups -- on the bundled pair in the
     100times_reuse loop of align.cpp:87-101 (swap, new source: sort + k-NN + covariances, align), and getFitnessScore (the other half of the metric)
     on the result. Both run the exact 1-NN search nn1_rows_kernel: per LM transition in the registration, once in the fitness score."""
@@ -1249,7 +1301,8 @@ def run_fgicp(args, steps, warmup, local_rank=0):
     for _ in range(warmup):
         r = step()
     times, n_launch = [], 0
-    for _rep in range(REPEATS):
+    n_rep = repeats_of(args)
+    for _rep in range(n_rep):
         c.synchronize(); torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(steps):
@@ -1258,10 +1311,12 @@ def run_fgicp(args, steps, warmup, local_rank=0):
         c.synchronize(); torch.cuda.synchronize()
         times.append(time.perf_counter() - t0)
     el, lo, hi = median_of(times)
+    if dump and args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(result_arrays(r), source_covariances=c.get_covariances("source")))
     # the same loop with the next source prepared on the second stream while the host drives the LM transitions of the current pair
     # (fvh_vgicp_prepare_source_device is legal at any time; FastGICP's LM loop is two small launches per transition: the chip is mostly free)
     pipelined = None
-    if not args.no_pipelined_leg:
+    if args.full and not args.no_pipelined_leg:
         seq_T = {}
         for _ in range(2):
             out = step()
@@ -1296,7 +1351,7 @@ def run_fgicp(args, steps, warmup, local_rank=0):
         c.gicp_align()
         nxt[0] = 1 - nxt[0]
     stage = {}
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         c.profile_reset(); c.profile_enable(1)
         for _ in range(10):
             step()
@@ -1314,12 +1369,12 @@ def run_fgicp(args, steps, warmup, local_rank=0):
         roof["note"] = "four queries per wave (one per 16-lane row), boxes nearest first; the full-sweep-equivalent rate is what a brute-force N x N kernel would have to sustain"
     c.close()
     return {"metric": "registrations/sec (100-iter reuse), FastGICP (nearest-point correspondences)", "value": round(steps / el, 3), "unit": "registrations/sec", "n_gpus": 1, "steps": steps, "warmup": warmup,
-            "repeats": REPEATS, "ms_per_step": round(el / steps * 1e3, 5), "ms_per_step_min": round(lo / steps * 1e3, 5), "ms_per_step_max": round(hi / steps * 1e3, 5),
+            "repeats": n_rep, "ms_per_step": round(el / steps * 1e3, 5), "ms_per_step_min": round(lo / steps * 1e3, 5), "ms_per_step_max": round(hi / steps * 1e3, 5),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "bundled scans (real LiDAR)", "fitness_score": round(float(fitness), 6),
             "fitness_us": stage.get("fitness", {}).get("avg_us"),
             "config": {"workload": desc, "method": "FastGICP (fast_gicp_impl.hpp:118-240 on the device)", "k_correspondences": 20, "covariance": "knn", "regularization": "PLANE",
                        "loop": "100times_reuse (align.cpp:87-101)", "inputs": "resident in HBM before the timed region"},
-            "per_registration": {"kernel_launches_lm": n_launch / (steps * REPEATS), "converged": bool(r["converged"])},
+            "per_registration": {"kernel_launches_lm": n_launch / (steps * n_rep), "converged": bool(r["converged"])},
             "pipelined": pipelined, "roofline": roof, "stages": stage}
 
 
@@ -1420,17 +1475,19 @@ EXTRA_CONFIGS = {
 
 def main():
     args = parse()
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench.py needs a GPU (the product path has no CPU fallback)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # `python bench.py --gpus N` on its own: become the launch the driver would have made (one rank per GPU over RCCL)
+        # `python bench.py --gpus N` on its own: start the launch the driver would have made (one rank per GPU over RCCL) as a child
+        # process, before this one touches the GPU runtime
         import socket
+        import subprocess
         with socket.socket() as sk:
             sk.bind(("127.0.0.1", 0))
             port = sk.getsockname()[1]
-        os.execvp(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1",
-                                   "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        sys.exit(subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1",
+                                  "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]))
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("bench.py needs a GPU (the product path has no CPU fallback)")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     if args.gpus != world and rank == 0:
@@ -1439,12 +1496,12 @@ def main():
     if args.workload == "lidar_stream":
         if world != 1:
             raise SystemExit("lidar_stream is a single-GPU workload")
-        emit(run_stream(args, args.steps, args.warmup))
+        emit(run_stream(args, args.steps, args.warmup, dump=True))
         return
     if args.workload == "fgicp17k":
         if world != 1:
             raise SystemExit("fgicp17k is a single-GPU workload")
-        emit(run_fgicp(args, args.steps, args.warmup, local_rank))
+        emit(run_fgicp(args, args.steps, args.warmup, local_rank, dump=True))
         return
     # test-only knobs to walk the N > 1 control flow on a single-GPU box: all ranks on device 0, gloo for the barrier
     share_gpu = os.environ.get("FVH_BENCH_SHARE_GPU") == "1"
@@ -1476,7 +1533,7 @@ def main():
             head = None
             sharded_hung = hung
         replicas = None
-        if not sharded_hung:
+        if args.full and not sharded_hung:
             replicas = run_registration(args, args.workload, args.cov, args.search, min(args.steps, 100), min(args.warmup, 10), local_rank, dist, dev, world, rank, headline=False,
                                         cpu_budget=args.cpu_seconds, cpu=False)
             if os.environ.get("FVH_BENCH_SHARDED_DETAIL", "1") == "1" and (not share_gpu or os.environ.get("FVH_BENCH_SHARDED_TEST") == "1"):
@@ -1501,7 +1558,7 @@ def main():
 
     # ---- the other single-GPU configurations of BASELINE.json, time-boxed ----
     default_headline = args.workload == "bundled17k" and args.cov == "knn" and world == 1
-    names = [] if args.configs == "none" else (args.configs.split(",") if args.configs else (["bundled17k_rbf_kernel", "bundled17k_parallel_kdtree", "bundled17k_fgicp", "synth100k_rbf", "synth1m", "lidar_stream"] if default_headline else []))
+    names = [] if args.configs == "none" or not args.full else (args.configs.split(",") if args.configs else (["bundled17k_rbf_kernel", "bundled17k_parallel_kdtree", "bundled17k_fgicp", "synth100k_rbf", "synth1m", "lidar_stream"] if default_headline else []))
     if names:
         configs = {}
         for name in names:

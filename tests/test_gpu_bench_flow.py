@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 def test_two_rank_bench_prints_one_aggregate_line():
     env = dict(os.environ, FVH_BENCH_SHARE_GPU="1", FVH_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", FVH_BENCH_SHARDED_TEST="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29531",
-           os.path.join(util.ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--configs", "none"]
+           os.path.join(util.ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--configs", "none"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=util.ROOT)
     lines = [l for l in p.stdout.splitlines() if l.strip()]  # (gloo prints its own "[Gloo] Rank 0 is connected ..." lines to stdout)
     assert p.returncode == 0 and lines and lines[-1].startswith("{") and sum(l.startswith("{") for l in lines) == 1, (p.returncode, p.stdout[-400:], p.stderr[-800:])

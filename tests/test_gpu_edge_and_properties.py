@@ -207,7 +207,7 @@ def test_registration_recovers_ground_truth_1m_map(big):
     c.close()
 
 
-def test_full_sweep_modes_agree_with_culled_modes():
+def test_full_sweep_modes_agree_with_culled_modes(tmp_path):
     """The un-culled LDS-tiled sweeps (FVH_KNN_MODE/FVH_RBF_MODE/FVH_FIT_MODE=0) of the TEST build of the library
     (-DFVH_TEST_KERNELS, fast_gicp_amd/build.py: the product library no longer carries them) give the culled kernels' results."""
     import os
@@ -235,8 +235,7 @@ np.savez(sys.argv[1], nb=nb, cov=cov, f=f)
         env = dict(os.environ, FVH_KNN_MODE=mode, FVH_RBF_MODE=mode, FVH_FIT_MODE=mode)
         if mode == "0":
             env["FVH_LIB_PATH"] = B.TEST_LIB_PATH  # mode 1 = the product library
-        path = os.path.join(util.ROOT, "gpurun_out", "modes_%s.npz" % mode)
-        os.makedirs(os.path.dirname(path), exist_ok=True)
+        path = str(tmp_path / ("modes_%s.npz" % mode))
         subprocess.check_call([sys.executable, "-c", code, path], env=env)
         out.append(np.load(path))
     assert np.array_equal(out[0]["nb"], out[1]["nb"])

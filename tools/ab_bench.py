@@ -31,7 +31,7 @@ def main():
         for kv in filter(None, envs.split(",")):
             k, _, v = kv.partition("=")
             env[k] = v
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--steps", steps, "--warmup", "10", "--no-cpu-baseline", "--streams", streams, "--configs", "none", "--no-host-leg", "--cov", cov]
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", workload, "--steps", steps, "--warmup", "10", "--no-cpu-baseline", "--streams", streams, "--configs", "none", "--no-host-leg", "--cov", cov]
         p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
         line = [l for l in p.stdout.splitlines() if l.startswith("{")]
         if not line:

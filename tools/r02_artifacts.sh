@@ -20,9 +20,9 @@ if [ "$WHAT" = "pmc" ] || [ "$WHAT" = "all" ]; then
   SPECS=""
   for w in bundled17k synth100k_rbf synth1m; do
     for c in FETCH_SIZE WRITE_SIZE; do
-      timeout 120 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_${w}_$c -o p -- python bench.py ${WL[$w]} $COMMON > $O/pmc_${w}_$c.log 2>&1 < /dev/null
+      timeout 120 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_${w}_$c -o p -- python bench.py --full ${WL[$w]} $COMMON > $O/pmc_${w}_$c.log 2>&1 < /dev/null
     done
-    timeout 120 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_VALU --output-format csv -d $O/pmc_${w}_SQ -o p -- python bench.py ${WL[$w]} $COMMON > $O/pmc_${w}_SQ.log 2>&1 < /dev/null
+    timeout 120 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_VALU --output-format csv -d $O/pmc_${w}_SQ -o p -- python bench.py --full ${WL[$w]} $COMMON > $O/pmc_${w}_SQ.log 2>&1 < /dev/null
     F=$(find $O/pmc_${w}_FETCH_SIZE -name "*counter_collection.csv" | head -1)
     W=$(find $O/pmc_${w}_WRITE_SIZE -name "*counter_collection.csv" | head -1)
     if [ -n "$F" ] && [ -n "$W" ]; then SPECS="$SPECS ${w}_persistent:cost_kernel:$F:$W"; fi
@@ -33,10 +33,10 @@ if [ "$WHAT" = "pmc" ] || [ "$WHAT" = "all" ]; then
   cat $O/pmc_cost_kernel.json | head -40; cat $O/pmc_sq.out | tail -30
 fi
 if [ "$WHAT" = "stats" ] || [ "$WHAT" = "all" ]; then
-  timeout 120 rocprofv3 --kernel-trace --stats -d $O/prof17k -o h -- python bench.py --steps 100 --warmup 10 --no-cpu-baseline --streams 1 --configs none > $O/bench_under_rocprof.json 2> $O/prof17k.log < /dev/null
-  timeout 120 rocprofv3 --kernel-trace --stats -d $O/prof100k -o h -- python bench.py --workload synth100k --cov rbf --steps 40 --warmup 5 --no-cpu-baseline --streams 1 --configs none > $O/synth100k_rbf_under_rocprof.json 2> $O/prof100k.log < /dev/null
-  timeout 120 rocprofv3 --kernel-trace --stats -d $O/prof1m -o h -- python bench.py --workload synth1m --steps 40 --warmup 5 --no-cpu-baseline --streams 1 --configs none > $O/synth1m_under_rocprof.json 2> $O/prof1m.log < /dev/null
-  timeout 150 rocprofv3 --kernel-trace --stats -d $O/profstream -o h -- python bench.py --workload lidar_stream --steps 60 --warmup 5 --no-cpu-baseline --no-profile > $O/stream_under_rocprof.json 2> $O/profstream.log < /dev/null
+  timeout 120 rocprofv3 --kernel-trace --stats -d $O/prof17k -o h -- python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --streams 1 --configs none > $O/bench_under_rocprof.json 2> $O/prof17k.log < /dev/null
+  timeout 120 rocprofv3 --kernel-trace --stats -d $O/prof100k -o h -- python bench.py --full --workload synth100k --cov rbf --steps 40 --warmup 5 --no-cpu-baseline --streams 1 --configs none > $O/synth100k_rbf_under_rocprof.json 2> $O/prof100k.log < /dev/null
+  timeout 120 rocprofv3 --kernel-trace --stats -d $O/prof1m -o h -- python bench.py --full --workload synth1m --steps 40 --warmup 5 --no-cpu-baseline --streams 1 --configs none > $O/synth1m_under_rocprof.json 2> $O/prof1m.log < /dev/null
+  timeout 150 rocprofv3 --kernel-trace --stats -d $O/profstream -o h -- python bench.py --full --workload lidar_stream --steps 60 --warmup 5 --no-cpu-baseline --no-profile > $O/stream_under_rocprof.json 2> $O/profstream.log < /dev/null
   for d in prof17k prof100k prof1m profstream; do
     f=$(find $O/$d -name "*.db" | head -1)
     [ -n "$f" ] && timeout 30 python tools/rocpd_stats.py $f > $O/${d}_kernel_stats.md 2>/dev/null < /dev/null
@@ -45,7 +45,7 @@ if [ "$WHAT" = "stats" ] || [ "$WHAT" = "all" ]; then
   head -12 $O/prof17k_kernel_stats.md
 fi
 if [ "$WHAT" = "bench" ] || [ "$WHAT" = "all" ]; then
-  timeout 400 python bench.py > $O/bench.json 2> $O/bench.err < /dev/null
+  timeout 400 python bench.py --full > $O/bench.json 2> $O/bench.err < /dev/null
   echo "bench rc=$?"; tail -3 $O/bench.err
   python - <<PY < /dev/null
 import json

@@ -23,9 +23,9 @@ if [ "$WHAT" = "pmc" ] || [ "$WHAT" = "all" ]; then
   SPECS=""
   for w in bundled17k synth100k_rbf synth1m lidar_stream; do
     for c in FETCH_SIZE WRITE_SIZE; do
-      timeout 150 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_${w}_$c -o p -- python bench.py ${WL[$w]} > $O/pmc_${w}_$c.log 2>&1 < /dev/null
+      timeout 150 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_${w}_$c -o p -- python bench.py --full ${WL[$w]} > $O/pmc_${w}_$c.log 2>&1 < /dev/null
     done
-    timeout 150 rocprofv3 --kernel-trace --pmc $SQ --output-format csv -d $O/pmc_${w}_SQ -o p -- python bench.py ${WL[$w]} > $O/pmc_${w}_SQ.log 2>&1 < /dev/null
+    timeout 150 rocprofv3 --kernel-trace --pmc $SQ --output-format csv -d $O/pmc_${w}_SQ -o p -- python bench.py --full ${WL[$w]} > $O/pmc_${w}_SQ.log 2>&1 < /dev/null
     F=$(find $O/pmc_${w}_FETCH_SIZE -name "*counter_collection.csv" | head -1); F=${F:--}
     W=$(find $O/pmc_${w}_WRITE_SIZE -name "*counter_collection.csv" | head -1); W=${W:--}
     S=$(find $O/pmc_${w}_SQ -name "*counter_collection.csv" | head -1); S=${S:--}
@@ -48,7 +48,7 @@ fi
 if [ "$WHAT" = "stats" ] || [ "$WHAT" = "all" ]; then
   for w in bundled17k synth100k_rbf synth1m lidar_stream; do
     ARGS=$(echo "${WL[$w]}" | sed 's/--no-profile//')
-    timeout 150 rocprofv3 --kernel-trace --stats -d $O/prof_$w -o h -- python bench.py $ARGS > $O/${w}_under_rocprof.json 2> $O/prof_$w.log < /dev/null
+    timeout 150 rocprofv3 --kernel-trace --stats -d $O/prof_$w -o h -- python bench.py --full $ARGS > $O/${w}_under_rocprof.json 2> $O/prof_$w.log < /dev/null
     f=$(find $O/prof_$w -name "*.db" | head -1)
     [ -n "$f" ] && timeout 30 python tools/rocpd_stats.py $f > $O/prof_${w}_kernel_stats.md 2>/dev/null < /dev/null
     rm -rf $O/prof_$w
@@ -56,7 +56,7 @@ if [ "$WHAT" = "stats" ] || [ "$WHAT" = "all" ]; then
   head -14 $O/prof_bundled17k_kernel_stats.md
 fi
 if [ "$WHAT" = "bench" ] || [ "$WHAT" = "all" ]; then
-  timeout 500 python bench.py > $O/bench.json 2> $O/bench.err < /dev/null
+  timeout 500 python bench.py --full > $O/bench.json 2> $O/bench.err < /dev/null
   echo "bench rc=$?"; tail -3 $O/bench.err
   python - <<PY < /dev/null
 import json

@@ -24,9 +24,9 @@ if [ "$WHAT" = "pmc" ] || [ "$WHAT" = "all" ]; then
   SPECS=""
   for w in bundled17k synth100k_rbf synth1m lidar_stream; do
     for c in FETCH_SIZE WRITE_SIZE; do
-      timeout 150 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_${w}_$c -o p -- python bench.py ${WL[$w]} > $O/pmc_${w}_$c.log 2>&1 < /dev/null
+      timeout 150 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_${w}_$c -o p -- python bench.py --full ${WL[$w]} > $O/pmc_${w}_$c.log 2>&1 < /dev/null
     done
-    timeout 150 rocprofv3 --kernel-trace --pmc $SQ --output-format csv -d $O/pmc_${w}_SQ -o p -- python bench.py ${WL[$w]} > $O/pmc_${w}_SQ.log 2>&1 < /dev/null
+    timeout 150 rocprofv3 --kernel-trace --pmc $SQ --output-format csv -d $O/pmc_${w}_SQ -o p -- python bench.py --full ${WL[$w]} > $O/pmc_${w}_SQ.log 2>&1 < /dev/null
     F=$(find $O/pmc_${w}_FETCH_SIZE -name "*counter_collection.csv" | head -1); F=${F:--}
     W=$(find $O/pmc_${w}_WRITE_SIZE -name "*counter_collection.csv" | head -1); W=${W:--}
     S=$(find $O/pmc_${w}_SQ -name "*counter_collection.csv" | head -1); S=${S:--}
@@ -51,7 +51,7 @@ fi
 if [ "$WHAT" = "stats" ] || [ "$WHAT" = "all" ]; then
   for w in bundled17k synth100k_rbf synth1m lidar_stream; do
     ARGS=$(echo "${WL[$w]}" | sed 's/--no-profile//')
-    timeout 150 rocprofv3 --kernel-trace --stats -d $O/prof_$w -o h -- python bench.py $ARGS > $O/${w}_under_rocprof.json 2> $O/prof_$w.log < /dev/null
+    timeout 150 rocprofv3 --kernel-trace --stats -d $O/prof_$w -o h -- python bench.py --full $ARGS > $O/${w}_under_rocprof.json 2> $O/prof_$w.log < /dev/null
     f=$(find $O/prof_$w -name "*.db" | head -1)
     [ -n "$f" ] && timeout 30 python tools/rocpd_stats.py $f > $O/prof_${w}_kernel_stats.md 2>/dev/null < /dev/null
     rm -rf $O/prof_$w
@@ -61,6 +61,6 @@ fi
 if [ "$WHAT" = "bench" ] || [ "$WHAT" = "all" ]; then
   # (bench.py quotes profiles/r05_pmc.json when its stamp matches the kernels: in an "all" run that is the file made above)
   [ "$WHAT" = "all" ] && [ -s $O/pmc.json ] && cp $O/pmc.json profiles/r05_pmc.json
-  timeout 500 python bench.py > $O/bench_line.json 2> $O/bench.err < /dev/null
+  timeout 500 python bench.py --full > $O/bench_line.json 2> $O/bench.err < /dev/null
   echo "bench rc=$?"; cp bench_detail.json $O/bench_detail.json; wc -c $O/bench_line.json; cat $O/bench_line.json
 fi
