@@ -68,8 +68,16 @@ def load():
         L.fvh_vgicp_last_error.restype = C.c_char_p
         L.fvh_ndt_last_error.restype = C.c_char_p
         L.fvh_voxelgrid_last_error.restype = C.c_char_p
+        for fn in (L.fvh_vgicp_align_multi, L.fvh_ndt_align_multi):
+            fn.argtypes = ALIGN_MULTI_ARGTYPES
+            fn.restype = C.c_int
         _LIB = L
     return _LIB
+
+
+# fvh_{vgicp,ndt}_align_multi(handle, k, guesses16, params, results, grid_blocks_out)
+ALIGN_MULTI_ARGTYPES = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+MAX_MULTI = 64  # hypotheses per align_multi call
 
 
 def declared_symbols():
@@ -211,6 +219,26 @@ class _Core:
         r = LmResult()
         self._call("align", _p(g), C.byref(p), C.byref(r))
         return _result_dict(r)
+
+    def align_multi(self, guesses, **lm):
+        """K independent registrations of the same pair from K initial guesses ((K, 4, 4) or a list of 4x4) in one launch. Returns one
+        align() result dict per guess, each with `grid_blocks`: the workgroups per hypothesis -- result k equals, bit for bit, align(guess k)
+        on a handle whose cost_max_blocks is that number."""
+        g = np.asarray(guesses, dtype=np.float64)
+        if g.ndim != 3 or g.shape[1:] != (4, 4):
+            raise FvhError("align_multi: guesses must be (K, 4, 4), got %s" % (g.shape,))
+        k = g.shape[0]
+        cm = np.ascontiguousarray(np.transpose(g, (0, 2, 1)))  # column-major per pose
+        p = _lm_params(**lm) if lm else _DEFAULT_LM
+        res = (LmResult * max(k, 1))()
+        nb = C.c_int(0)
+        self._call("align_multi", int(k), _p(cm), C.byref(p), res, C.byref(nb))
+        out = []
+        for i in range(k):
+            d = _result_dict(res[i])
+            d["grid_blocks"] = nb.value
+            out.append(d)
+        return out
 
     def fitness_score(self, T, max_range=1.7976931348623157e308):
         t = _colmajor16(T)

@@ -75,6 +75,43 @@ struct Engine {
   }
   void* result_host = nullptr;            // mapped pinned memory the persistent kernel writes the final state + a sequence word to
   unsigned long long* result_dev = nullptr;  // its device address
+  // align_multi (fvh_*_align_multi): the per-align buffers once per hypothesis -- states, partial / row regions, tickets, broadcast areas,
+  // correspondence buffers, mapped result blocks (kernels_cost.hpp: GangParams) and the guesses. Grown once per K (never while an align_async is
+  // in flight: the C ABI refuses the call), freed with the handle.
+  int multi_cap = 0;
+  DevBuf multi_state, multi_partials, multi_ticket, multi_bcast, multi_corr, multi_guess;
+  void* multi_pinned = nullptr;                    // K states (copies of the device states) + K guesses
+  void* multi_result_host = nullptr;               // K blocks of GANG_RESULT_WORDS (mapped, like result_host)
+  unsigned long long* multi_result_dev = nullptr;
+  int ensure_multi(int k) {
+    if (k <= multi_cap) return FVH_OK;
+    hipError_t e;
+    if ((e = hipStreamSynchronize(stream)) != hipSuccess) return hipfail(e, "hipStreamSynchronize");
+    if ((e = multi_state.ensure(sizeof(LmState) * k)) != hipSuccess) return hipfail(e, "hipMalloc");
+    if ((e = multi_partials.ensure(sizeof(double) * PARTIALS_DOUBLES * k)) != hipSuccess) return hipfail(e, "hipMalloc");
+    if ((e = multi_ticket.ensure(sizeof(unsigned) * GANG_TICKET_WORDS * k)) != hipSuccess) return hipfail(e, "hipMalloc");
+    if ((e = multi_bcast.ensure(sizeof(double) * GANG_BCAST_DOUBLES * k)) != hipSuccess) return hipfail(e, "hipMalloc");
+    if ((e = multi_guess.ensure(sizeof(PoseD) * k)) != hipSuccess) return hipfail(e, "hipMalloc");
+    // tagged rows and broadcast: tags of no launch; tickets armed
+    if ((e = hipMemsetAsync(multi_partials.p, 0, multi_partials.cap, stream)) != hipSuccess) return hipfail(e, "hipMemsetAsync");
+    if ((e = hipMemsetAsync(multi_ticket.p, 0, multi_ticket.cap, stream)) != hipSuccess) return hipfail(e, "hipMemsetAsync");
+    if ((e = hipMemsetAsync(multi_bcast.p, 0, multi_bcast.cap, stream)) != hipSuccess) return hipfail(e, "hipMemsetAsync");
+    if (multi_pinned) { (void)hipHostFree(multi_pinned); multi_pinned = nullptr; }
+    if ((e = hipHostMalloc(&multi_pinned, (sizeof(LmState) + sizeof(PoseD)) * k, hipHostMallocDefault)) != hipSuccess) { multi_pinned = nullptr; multi_cap = 0; return hipfail(e, "hipHostMalloc"); }
+    if (multi_result_host) { (void)hipHostFree(multi_result_host); multi_result_host = nullptr; multi_result_dev = nullptr; }
+    const size_t rbytes = sizeof(unsigned long long) * GANG_RESULT_WORDS * k;
+    if (hipHostMalloc(&multi_result_host, rbytes, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess) {
+      std::memset(multi_result_host, 0, rbytes);
+      void* dp = nullptr;
+      if (hipHostGetDevicePointer(&dp, multi_result_host, 0) == hipSuccess) multi_result_dev = reinterpret_cast<unsigned long long*>(dp);
+    } else {
+      multi_result_host = nullptr;
+    }
+    (void)hipGetLastError();  // zero-copy results are optional
+    if ((e = hipStreamSynchronize(stream)) != hipSuccess) return hipfail(e, "hipStreamSynchronize");
+    multi_cap = k;
+    return FVH_OK;
+  }
   PoseD lin;               // pose of the last update_correspondences()
   bool has_corr = false;
   int corr_kind = 0;       // 0: voxel correspondences (VGICP / NDT), 1: nearest-point correspondences (GICP)
@@ -318,6 +355,10 @@ struct Engine {
     if (upload_pinned) (void)hipHostFree(upload_pinned);
     for (int s = 0; s < 2; s++) if (upload_done[s]) (void)hipEventDestroy(upload_done[s]);
     if (result_host) (void)hipHostFree(result_host);
+    multi_state.release(); multi_partials.release(); multi_ticket.release(); multi_bcast.release(); multi_corr.release(); multi_guess.release();
+    if (multi_pinned) (void)hipHostFree(multi_pinned);
+    if (multi_result_host) (void)hipHostFree(multi_result_host);
+    multi_pinned = multi_result_host = nullptr; multi_result_dev = nullptr; multi_cap = 0;
     if (stream) (void)hipStreamDestroy(stream);
     if (gang_done) (void)hipEventDestroy(gang_done);
     if (side_done) (void)hipEventDestroy(side_done);
@@ -845,6 +886,24 @@ int fvh_vgicp_align(fvh_vgicp* h, const double* guess, const fvh_lm_params* p, f
   if (rc == FVH_OK) h->e.quiet = true;
   return rc;
 }
+// ---- align_multi: K initial guesses of the same pair in one launch (host_stages.inc.hpp: do_align_multi) ----
+static int check_multi_args(Engine* e, int k, const double* guesses16, const fvh_lm_result* results) {
+  if (k < 1 || k > MAX_GANGS) return e->fail(FVH_ERR_INVALID_ARGUMENT, "align_multi: need 1 <= k <= " + std::to_string(MAX_GANGS));
+  if (!guesses16 || !results) return e->fail(FVH_ERR_INVALID_ARGUMENT, "align_multi: null argument");
+  for (int i = 0; i < 16 * k; i++)
+    if (!std::isfinite(guesses16[i])) return e->fail(FVH_ERR_INVALID_ARGUMENT, "align_multi: guess " + std::to_string(i / 16) + " is not finite");
+  return FVH_OK;
+}
+int fvh_vgicp_align_multi(fvh_vgicp* h, int k, const double* guesses16, const fvh_lm_params* p, fvh_lm_result* results, int* grid_blocks_out) {
+  CHECK_HANDLE(h);
+  { const int rc = check_multi_args(&h->e, k, guesses16, results); if (rc) return rc; }
+  if (h->e.sharded()) return h->e.fail(FVH_ERR_UNSUPPORTED, "align_multi: not on a multi-GPU handle");
+  if (!h->source.has_pts || !h->source.has_cov) return h->e.fail(FVH_ERR_BAD_STATE, "align: source cloud/covariances not set");
+  h->e.crowd_fence = h->next_ready ? h->prep_done : nullptr;
+  const int rc = do_align_multi<MODE_VGICP>(&h->e, h->cost_source(), h->voxelmap, k, guesses16, p, results, grid_blocks_out, h->rebuild_safe());
+  if (rc == FVH_OK) h->e.quiet = true;
+  return rc;
+}
 // ---- pipelined scan streams (scan-to-scan odometry: src/kitti.cpp's loop with the next scan prepared beside the running LM kernel) ----
 //   prepare_source_device(scan k+1)  [second stream: pack, Morton sort, exact k-NN, covariances, the scan's own voxel map]
 //   align_async(guess) .. align_wait(result)   [main stream: the persistent LM kernel of the pair (k, k-1)]
@@ -1253,6 +1312,17 @@ int fvh_ndt_align(fvh_ndt* h, const double* guess, const fvh_lm_params* p, fvh_l
   h->e.crowd_fence = h->next_ready ? h->prep_done : nullptr;  // (a preparation still running on the second stream: a grid that crowds the chip waits for it)
   if (h->distance_mode == FVH_NDT_P2D) return do_align<MODE_NDT_P2D>(&h->e, h->cost_source(), h->target_vm, guess, p, r, h->rebuild_safe());
   return do_align<MODE_NDT_D2D>(&h->e, h->cost_source(), h->target_vm, guess, p, r, h->rebuild_safe());
+}
+int fvh_ndt_align_multi(fvh_ndt* h, int k, const double* guesses16, const fvh_lm_params* p, fvh_lm_result* results, int* grid_blocks_out) {
+  CHECK_HANDLE(h); NDT_NOT_PENDING(h);
+  { const int rc = check_multi_args(&h->e, k, guesses16, results); if (rc) return rc; }
+  if (h->e.sharded()) return h->e.fail(FVH_ERR_UNSUPPORTED, "align_multi: not on a tiled / multi-GPU handle (fvh_ndt_set_source_tile, fvh_ndt_comm_init)");
+  int rc = fvh_ndt_create_voxelmaps(h);
+  if (rc) return rc;
+  rc = ndt_ready(h); if (rc) return rc;
+  h->e.crowd_fence = h->next_ready ? h->prep_done : nullptr;
+  if (h->distance_mode == FVH_NDT_P2D) return do_align_multi<MODE_NDT_P2D>(&h->e, h->cost_source(), h->target_vm, k, guesses16, p, results, grid_blocks_out, h->rebuild_safe());
+  return do_align_multi<MODE_NDT_D2D>(&h->e, h->cost_source(), h->target_vm, k, guesses16, p, results, grid_blocks_out, h->rebuild_safe());
 }
 // ---- pipelined frame streams: align = launch + wait; the next source is prepared beside the running LM kernel ----
 int fvh_ndt_align_async(fvh_ndt* h, const double* guess, const fvh_lm_params* p) {

@@ -716,10 +716,14 @@ inline CostShape cost_shape(const Engine* e, const CostSource& src, int mode = M
   return s;
 }
 
+// align_multi: K hypotheses in one launch of lm_gang_kernel (kernels_cost.hpp), each on its slice of the handle's multi_* buffers
+struct MultiLaunch { int k; };
+
 template <int MODE>
 int launch_cost(Engine* e, const CostSource& src, const VoxelMapDev& vm, int host_phase, const PoseD* lin, const PoseD* ev, const fvh_lm_params* init = nullptr,
                 bool persistent = false, unsigned long long peer_xbase = 0 /* multi-GPU: exchange counter of this launch's first sums exchange */,
-                const GridPlan* plan = nullptr /* align(): the layout both routes take (workgroups granted, groups, XCD confinement) */) {
+                const GridPlan* plan = nullptr /* align(): the layout both routes take (workgroups granted, groups, XCD confinement) */,
+                const MultiLaunch* multi = nullptr /* align_multi: the per-align buffers are the K slices of the multi_* buffers */) {
   CostParams P;
   std::memset(&P, 0, sizeof(P));
   P.src_pts = src.pts; P.src_cov = src.cov; P.d_n_src = src.d_n; P.n_src = src.n_upper; P.order = src.order; P.src_sorted = src.order ? src.sorted : nullptr; P.src_cov_sorted = (src.order && src.sorted) ? src.cov_sorted : nullptr;
@@ -810,8 +814,21 @@ int launch_cost(Engine* e, const CostSource& src, const VoxelMapDev& vm, int hos
   }
   const int launch_blocks = blocks;
   if (persistent && plan) P.xcd_local = plan->local;
+  GangParams G{blocks, nullptr};
+  const int gangs = multi ? multi->k : 1;
+  if (multi) {
+    // (per-hypothesis slices: kernels_cost.hpp, GangParams. Transport only differs from a single align: no XCD confinement -- a gang's groups
+    // need not follow the dispatcher's XCD rotation -- and no wave priority; the lm_everywhere rule looks at the whole grid)
+    P.st = e->multi_state.as<LmState>(); P.partials = e->multi_partials.as<double>(); P.ticket = e->multi_ticket.as<unsigned>();
+    P.bcast = e->multi_bcast.as<double>(); P.corr = e->multi_corr.as<int>(); P.lm_trace = nullptr;
+    P.xcd_local = 0; P.prio_mode = 0;
+    int cus = 256;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device);
+    P.lm_everywhere = (persistent && P.ng > 1 && (e->params.lm_everywhere == 2 || (e->params.lm_everywhere == 1 && (long long)gangs * blocks <= 2 * cus))) ? 1 : 0;
+    G.guesses = e->multi_guess.as<PoseD>();
+  }
   // abort word = 0 (the last 8 bytes of the state; never covered by the state write-back)
-  if (e->abort_word_dirty) {
+  if (!multi && e->abort_word_dirty) {
     HIP_OR_FAIL(e, hipMemsetAsync(reinterpret_cast<char*>(e->state.p) + sizeof(LmState) - 8, 0, 8, e->stream));
     e->abort_word_dirty = false;
   }
@@ -821,9 +838,9 @@ int launch_cost(Engine* e, const CostSource& src, const VoxelMapDev& vm, int hos
     // row and the workgroups waiting for their broadcast must outlast that, or a 50 ms skew between ranks would look like a stuck local barrier
     if (P.peer.n > 1 && P.watchdog_ticks) P.watchdog_ticks = std::max(P.watchdog_ticks, 2 * P.peer_watchdog_ticks);
     const int zc = e->params.zerocopy_result;
-    P.result_host = (zc && (!e->prof.on || e->prof.cost_only)) ? e->result_dev : nullptr;  // (full stage profiling drains the stream per call anyway; the two events of level 2 do not need it)
+    P.result_host = (zc && (!e->prof.on || e->prof.cost_only)) ? (multi ? e->multi_result_dev : e->result_dev) : nullptr;  // (full stage profiling drains the stream per call anyway; the two events of level 2 do not need it)
     e->zero_copy_armed = P.result_host != nullptr;
-    P.bcast = e->bcast.as<double>();
+    if (!multi) P.bcast = e->bcast.as<double>();
     P.launch_tag = ++e->persist_seq;
     e->last_persist_blocks = blocks;
     (void)e->gang_begin(false);  // (the persistent launches share the chip through the SlotPool; other handles' cooperative sorts stay away while this runs)
@@ -831,23 +848,25 @@ int launch_cost(Engine* e, const CostSource& src, const VoxelMapDev& vm, int hos
       ProfScope ps(e, "cost");
       // (items of ONE offset take the instantiation unrolled for one lookup; both routes of an align pick by the same shape.
       // Gauss-Newton aligns take their own instantiations: the Levenberg-Marquardt ones do not carry the other optimiser's code)
-#define FVH_LAUNCH_COST(PERS, GRID)                                                                                                   \
+#define FVH_LAUNCH_COST(KERNEL, PERS, GRID, ...)                                                                                      \
   do {                                                                                                                                \
     const bool f32 = e->float_cost();                                                                                                 \
     if ((host_phase < 0 ? e->align_optimizer : 0) == 0) {                                                                             \
-      if (P.group == 1) { if (f32) cost_kernel<float, MODE, PERS, 1><<<GRID, 256, 0, e->stream>>>(P); else cost_kernel<double, MODE, PERS, 1><<<GRID, 256, 0, e->stream>>>(P); } \
-      else { if (f32) cost_kernel<float, MODE, PERS><<<GRID, 256, 0, e->stream>>>(P); else cost_kernel<double, MODE, PERS><<<GRID, 256, 0, e->stream>>>(P); }                    \
+      if (P.group == 1) { if (f32) KERNEL<float, MODE, PERS, 1><<<GRID, 256, 0, e->stream>>>(__VA_ARGS__); else KERNEL<double, MODE, PERS, 1><<<GRID, 256, 0, e->stream>>>(__VA_ARGS__); } \
+      else { if (f32) KERNEL<float, MODE, PERS><<<GRID, 256, 0, e->stream>>>(__VA_ARGS__); else KERNEL<double, MODE, PERS><<<GRID, 256, 0, e->stream>>>(__VA_ARGS__); }                    \
     } else {                                                                                                                          \
-      if (P.group == 1) { if (f32) cost_kernel<float, MODE, PERS, 1, true><<<GRID, 256, 0, e->stream>>>(P); else cost_kernel<double, MODE, PERS, 1, true><<<GRID, 256, 0, e->stream>>>(P); } \
-      else { if (f32) cost_kernel<float, MODE, PERS, COST_CH, true><<<GRID, 256, 0, e->stream>>>(P); else cost_kernel<double, MODE, PERS, COST_CH, true><<<GRID, 256, 0, e->stream>>>(P); } \
+      if (P.group == 1) { if (f32) KERNEL<float, MODE, PERS, 1, true><<<GRID, 256, 0, e->stream>>>(__VA_ARGS__); else KERNEL<double, MODE, PERS, 1, true><<<GRID, 256, 0, e->stream>>>(__VA_ARGS__); } \
+      else { if (f32) KERNEL<float, MODE, PERS, COST_CH, true><<<GRID, 256, 0, e->stream>>>(__VA_ARGS__); else KERNEL<double, MODE, PERS, COST_CH, true><<<GRID, 256, 0, e->stream>>>(__VA_ARGS__); } \
     }                                                                                                                                 \
   } while (0)
-      FVH_LAUNCH_COST(true, launch_blocks);
+      if (multi) FVH_LAUNCH_COST(lm_gang_kernel, true, gangs * launch_blocks, P, G);
+      else FVH_LAUNCH_COST(cost_kernel, true, launch_blocks, P);
     }
     e->gang_end();
   } else {
     ProfScope ps(e, "cost");
-    FVH_LAUNCH_COST(false, blocks);
+    if (multi) FVH_LAUNCH_COST(lm_gang_kernel, false, gangs * blocks, P, G);
+    else FVH_LAUNCH_COST(cost_kernel, false, blocks, P);
   }
   HIP_OR_FAIL(e, hipGetLastError());
   return FVH_OK;
@@ -1128,6 +1147,168 @@ int do_align(Engine* e, const CostSource& src, VoxelMapDev& vm, const double* gu
   int rc = align_begin<MODE>(e, c, src, vm, guess16, params, retried, no_persist, forced_plan);
   if (rc) return rc;
   return align_finish<MODE>(e, c, src, vm, result, rebuild_safe);
+}
+
+// ---- align_multi: K independent LM problems on the same prepared clouds (K initial guesses) in one launch of lm_gang_kernel ----
+// The plan is the one a single align makes (nb_h workgroups, default_groups(nb_h) groups), shrunk -- when the K gangs do not fit the co-resident
+// slots together -- to what the pool grants (nb_h >= 8), else the K gangs take the multi-launch route (one launch per LM transition over all of
+// them) with the single align's plan. Either way gang k walks, groups and sums exactly as do_align(guess k) with nb = nb_h: results[k] is that
+// align's, bit for bit, on a handle whose cost_max_blocks is nb_h. Afterwards the handle is where `for k: align(guess k)` leaves it.
+template <int MODE>
+int do_align_multi(Engine* e, const CostSource& src_in, VoxelMapDev& vm, int K, const double* guesses16, const fvh_lm_params* params, fvh_lm_result* results,
+                   int* grid_out, const Rebuild& rebuild_safe) {
+  hipEvent_t const fence = e->crowd_fence;  // (valid for this call only)
+  e->crowd_fence = nullptr;
+  e->lm_crowds_chip = false;
+  if (!vm.valid) return e->fail(FVH_ERR_BAD_STATE, "align_multi: target voxel map not built");
+  CostSource src = src_in;
+  fvh_lm_params p;
+  if (params) p = *params; else fvh_default_lm_params(&p);
+  e->lm_trace_rows = 0;  // (the LM debug trace is not recorded for multi calls)
+  int cap = persistent_capacity<MODE>(e);
+  if (cap <= 0) return e->fail(FVH_ERR_HIP, "cost kernel: occupancy query failed");
+  int nb_h = std::min(cost_shape(e, src, MODE, true).blocks, cap);  // the plan of a single align
+  if (p.max_iterations <= 0) {  // nothing to launch: every result is its guess, exactly as K plain aligns leave them
+    for (int k = 0; k < K; k++) { const int rc = do_align<MODE>(e, src, vm, guesses16 + 16 * k, &p, results + k, rebuild_safe); if (rc) return rc; }
+    if (grid_out) *grid_out = nb_h;
+    return FVH_OK;
+  }
+  e->align_optimizer = p.optimizer != 0 ? 1 : 0;
+  { const int rc = e->ensure_multi(K); if (rc) return rc; }
+  const size_t corr_stride = (size_t)std::max(src.n_upper, 1) * e->n_off;
+  HIP_OR_FAIL(e, e->corr.ensure(2 * sizeof(int) * corr_stride));
+  HIP_OR_FAIL(e, e->multi_corr.ensure(2 * sizeof(int) * corr_stride * K));
+  const long long budget = (long long)std::max(p.max_iterations, 0) * (1 + (long long)std::max(p.lm_max_iterations, 0)) + 1;
+  bool persistent = e->params.persistent != 0 && budget < 4000 && (long long)src.n_upper * e->n_off <= PERSIST_MAX_ITEMS;
+  if (persistent && e->persist_skip > 0) { e->persist_skip--; persistent = false; }  // backing off after an abort, like align()
+  SlotPool::Grant grant;
+  const int grant_dev = e->device;
+  struct Slots { SlotPool::Grant& g; int dev; void release() { if (g.n > 0) g_slots.release(dev, g); g = SlotPool::Grant{}; } ~Slots() { release(); } } slots{grant, grant_dev};
+  if (persistent) {
+    grant = g_slots.acquire(e->device, cap, K * nb_h);
+    if (grant.n >= K * nb_h) {
+    } else if (!cost_shape(e, src, MODE, true).split && grant.n / K >= 8) {
+      nb_h = grant.n / K;  // smaller gangs that are co-resident together (a wave-role grid keeps its size: its layout ignores cost_max_blocks)
+    } else {
+      slots.release();
+      persistent = false;
+    }
+  }
+  GridPlan plan;
+  plan.nb = nb_h; plan.ng = default_groups(nb_h); plan.local = 0;
+  // guesses and fresh states (the abort words included)
+  LmState* hs = static_cast<LmState*>(e->multi_pinned);
+  PoseD* hg = reinterpret_cast<PoseD*>(static_cast<char*>(e->multi_pinned) + sizeof(LmState) * (size_t)e->multi_cap);
+  for (int k = 0; k < K; k++) hg[k] = pose_from_colmajor16(guesses16 + 16 * k);
+  HIP_OR_FAIL(e, hipMemcpyAsync(e->multi_guess.p, hg, sizeof(PoseD) * K, hipMemcpyHostToDevice, e->stream));
+  const MultiLaunch ml{K};
+  long long launched = 0;
+  bool retried = false;
+  for (;;) {
+    HIP_OR_FAIL(e, hipMemsetAsync(e->multi_state.p, 0, sizeof(LmState) * K, e->stream));
+    launched = 0;
+    if (persistent) {
+      e->lm_crowds_chip = Engine::crowds(K * nb_h, cap);
+      if (e->lm_crowds_chip && fence && hipEventQuery(fence) != hipSuccess) {  // a preparation still runs on the second stream (Engine::lm_crowds_chip)
+        (void)hipGetLastError();
+        HIP_OR_FAIL(e, hipStreamWaitEvent(e->stream, fence, 0));
+      }
+      int rc = launch_cost<MODE>(e, src, vm, -1, nullptr, nullptr, &p, true, 0, &plan, &ml);
+      if (rc) return rc;
+      bool have = false;
+      if (e->multi_result_dev && e->zero_copy_armed) {  // the K sequence words (align_finish's spin / query logic)
+        volatile unsigned long long* words = reinterpret_cast<volatile unsigned long long*>(e->multi_result_host);
+        const size_t seq_at = sizeof(LmState) / 8;
+        if (e->params.host_wait_block != 0) (void)hipStreamSynchronize(e->stream);
+        const unsigned long long query_mask = [&] { unsigned long long m = 1; while (m < e->params.result_query_spins) m <<= 1; return m - 1; }();
+        auto all_in = [&] { for (int k = 0; k < K; k++) if (words[(size_t)k * GANG_RESULT_WORDS + seq_at] != e->persist_seq) return false; return true; };
+        for (unsigned long long spins = 0;; spins++) {
+          if (all_in()) { have = true; break; }
+          if ((spins & query_mask) == query_mask && hipStreamQuery(e->stream) != hipErrorNotReady) { have = all_in(); break; }
+        }
+        if (have) {
+          std::atomic_thread_fence(std::memory_order_acquire);
+          for (int k = 0; k < K; k++) {
+            std::memcpy(hs + k, static_cast<const char*>(e->multi_result_host) + sizeof(unsigned long long) * GANG_RESULT_WORDS * k, sizeof(LmState) - 8);
+            hs[k].gen = 0; hs[k].aborted = 0;
+          }
+        }
+      }
+      if (!have) {
+        HIP_OR_FAIL(e, hipMemcpyAsync(hs, e->multi_state.p, sizeof(LmState) * K, hipMemcpyDeviceToHost, e->stream));
+        HIP_OR_FAIL(e, hipStreamSynchronize(e->stream));
+      }
+      slots.release();
+      e->lm_crowds_chip = false;
+      bool failed = false;
+      for (int k = 0; k < K; k++) failed = failed || hs[k].aborted || hs[k].phase != PH_DONE;
+      if (failed) {  // the barrier watchdog fired in some gang: all K again on the multi-launch route, the same plan (the same sums)
+        e->persist_aborts++;
+        e->persist_backoff = std::min(std::max(2 * e->persist_backoff, 1), 64);
+        e->persist_skip = e->persist_backoff;
+        persistent = false;
+        continue;
+      }
+      launched = 1;
+      e->persist_backoff = 0;
+    } else {
+      int batch = e->last_steps > 0 ? std::max(e->last_steps, e->prev_steps) + 1 : 8;
+      for (;;) {
+        for (int s = 0; s < batch; s++) {  // (gangs that are done return at once)
+          const int rc = launch_cost<MODE>(e, src, vm, -1, nullptr, nullptr, (launched == 0 && s == 0) ? &p : nullptr, false, 0, &plan, &ml);
+          if (rc) return rc;
+        }
+        launched += batch;
+        HIP_OR_FAIL(e, hipMemcpyAsync(hs, e->multi_state.p, sizeof(LmState) * K, hipMemcpyDeviceToHost, e->stream));
+        HIP_OR_FAIL(e, hipStreamSynchronize(e->stream));
+        bool all_done = true;
+        for (int k = 0; k < K; k++) all_done = all_done && hs[k].phase == PH_DONE;
+        if (all_done || launched >= budget) break;
+        batch = 3;
+      }
+    }
+    vm.nv_hint = hs[K - 1].vm_num_voxels;
+    if (src.source_map) src.source_map->nv_hint = hs[K - 1].vm_num_voxels2;
+    bool dropped = false;
+    for (int k = 0; k < K; k++) dropped = dropped || hs[k].vm_dropped > 0;
+    if (!dropped) break;
+    // a hint-sized table overflowed: rebuild at the safe size once and run all K again (multi-launch route: no slots to ask for again)
+    if (retried) return e->fail(FVH_ERR_BAD_STATE, "voxel map overflow persists after safe rebuild");
+    retried = true;
+    const int rc = rebuild_safe();
+    if (rc) return rc;
+    src.refresh();
+    persistent = false;
+    plan.nb = nb_h = std::min(cost_shape(e, src, MODE, true).blocks, cap); plan.ng = default_groups(nb_h);
+  }
+  if (grid_out) *grid_out = nb_h;
+  e->gang_clear();
+  for (int k = 0; k < K; k++) {
+    const LmState& h = hs[k];
+    fvh_lm_result* r = results + k;
+    pose_to_colmajor16(h.x0, r->T);
+    for (int i = 0; i < 6; i++) for (int j = 0; j < 6; j++) r->H[j * 6 + i] = h.final_H[i * 6 + j];
+    r->final_error = h.y0;
+    r->converged = h.converged;
+    r->nr_iterations = h.nr_iterations;
+    r->num_linearize = h.num_linearize;
+    r->num_error_evals = h.num_error_evals;
+    r->lm_failed = h.lm_failed;
+    r->num_launches = (int)launched;
+    e->prev_steps = e->last_steps;
+    e->last_steps = p.optimizer ? std::max(1, (int)h.num_linearize) : 1 + h.num_error_evals;
+  }
+  // the handle as the last of K plain aligns leaves it: its linearisation pose, correspondences (compute_error) and device state
+  const LmState& last = hs[K - 1];
+  e->lin = last.x_lin;
+  e->corr_sel = last.corr_cur;
+  e->has_corr = true;
+  e->corr_kind = 0;
+  e->corr_n_src = src.n_upper;
+  HIP_OR_FAIL(e, hipMemcpyAsync(e->corr.p, e->multi_corr.as<int>() + (size_t)(K - 1) * 2 * corr_stride, 2 * sizeof(int) * corr_stride, hipMemcpyDeviceToDevice, e->stream));
+  HIP_OR_FAIL(e, hipMemcpyAsync(e->state.p, e->multi_state.as<LmState>() + (K - 1), sizeof(LmState) - 8, hipMemcpyDeviceToDevice, e->stream));
+  std::memcpy(e->pinned, &last, sizeof(LmState));
+  return FVH_OK;
 }
 
 // exact 1-NN of every (transformed) source point in the target (kernels_cov.hpp: nn1_rows_kernel -- four queries per wave, one per 16-lane row)

@@ -768,9 +768,31 @@ __device__ __forceinline__ Pose<Real> lds_pose(LdsPose<Real> p, int which) {
   return o;
 }
 
-template <typename Real, int MODE, bool PERSIST, int CH = COST_CH, bool GN = false>
-__global__ FVH_COST_BOUNDS void cost_kernel(CostParams P) {
+// Gang launches (lm_gang_kernel below): K independent LM problems on the same clouds in one grid of K x nb_h workgroups. Workgroup g
+// belongs to hypothesis g / nb_h and has local index g % nb_h; every per-align buffer is that hypothesis's slice -- K states, K partial /
+// row regions, K ticket sets, K broadcast areas, K double-buffered correspondence buffers, K result blocks in the mapped result memory.
+// Inside a gang the algorithm is the single align's with nb = nb_h: the same partition of the items, the same groups, the same sums.
+constexpr size_t GANG_TICKET_WORDS = 16;                                          // unsigned per hypothesis (TICKET_GROUPS + 1 used)
+constexpr size_t GANG_BCAST_DOUBLES = (size_t)PERSIST_REPLICAS * BCAST_PAIRS * 2;  // doubles per hypothesis
+constexpr size_t GANG_RESULT_WORDS = (sizeof(LmState) / 8 + 1 + 7) & ~(size_t)7;   // 64-bit words per hypothesis: state + sequence word, whole lines
+constexpr int MAX_GANGS = 64;
+struct GangParams {
+  int nb_h;               // workgroups per hypothesis
+  const PoseD* guesses;   // [K] initial guesses (launches with CostParams::init)
+};
+
+// The body of the LM cost kernel: one workgroup `lb` of `nb`, working on the buffers of hypothesis `gang` (GANG = false: the plain
+// single-align kernel: blockIdx.x of gridDim.x, the buffers of CostParams as they are).
+template <typename Real, int MODE, bool PERSIST, int CH, bool GN, bool GANG>
+__device__ __forceinline__ void cost_body(const CostParams& P, const unsigned gang_lb, const unsigned gang_nb, const unsigned gang, const PoseD* gang_guesses) {
   static_assert(CH == 1 || CH == COST_CH, "one or COST_CH lookups per item");
+  // this align's buffers, read where they are used (for GANG = false exactly the plain kernel's reads of CostParams)
+  auto lin_arg = [&]() -> PoseD { if constexpr (GANG) return gang_guesses[gang]; else return P.lin; };  // first launch of an align: the initial guess
+  auto partials = [&]() -> double* { if constexpr (GANG) return P.partials + (size_t)gang * PARTIALS_DOUBLES; else return P.partials; };
+  auto ticket = [&]() -> unsigned* { if constexpr (GANG) return P.ticket + (size_t)gang * GANG_TICKET_WORDS; else return P.ticket; };
+  auto bcast_base = [&]() -> double* { if constexpr (GANG) return P.bcast + (size_t)gang * GANG_BCAST_DOUBLES; else return P.bcast; };
+  auto corr_base = [&]() -> int* { if constexpr (GANG) return P.corr + (size_t)gang * 2 * P.corr_stride; else return P.corr; };
+  auto result_host = [&]() -> unsigned long long* { if constexpr (GANG) return P.result_host ? P.result_host + (size_t)gang * GANG_RESULT_WORDS : nullptr; else return P.result_host; };
 #ifdef FVH_COST_TIMING
   __shared__ unsigned long long stamp[12];  // LDS, not registers: must not change the kernel being measured
   if (threadIdx.x == 0) { stamp[0] = wall_clock64(); atomicMin(&g_cost_timing[0], stamp[0]); }
@@ -782,12 +804,9 @@ __global__ FVH_COST_BOUNDS void cost_kernel(CostParams P) {
   static_assert(sizeof(LmState) % 8 == 0, "LmState is copied as 64-bit words");
   constexpr int ST_WORDS = sizeof(LmState) / 8 - 1;  // without the barrier word
   static_assert(ST_WORDS <= 256, "one state word per thread after the barrier");
-  LmState* st = P.st;
+  LmState* st = GANG ? P.st + gang : P.st;
   unsigned long long* st_words = reinterpret_cast<unsigned long long*>(st);
-  // Workgroup id / count. The dispatcher hands consecutive blocks to consecutive XCDs (block b runs on XCD (b + c) % 8 with one c per
-  // launch: tools/probes/probe_xcc.hip). That is an observation, not a contract: every workgroup publishes the c it sees with its sums and
-  // the collectors end the launch if they ever differ (`xcd_local` below).
-  const unsigned lb = blockIdx.x, nb = gridDim.x;
+  const unsigned lb = GANG ? gang_lb : blockIdx.x, nb = GANG ? gang_nb : gridDim.x;
   unsigned gen = 0;  // PERSIST: barrier generations this workgroup has passed
   int phase, corr_sel;
   PoseD lin_d, ev_d;
@@ -798,8 +817,8 @@ __global__ FVH_COST_BOUNDS void cost_kernel(CostParams P) {
     corr_sel = P.host_corr_sel;
   } else if (P.init) {  // first launch of an align: the state in memory is stale, everything comes from the kernel arguments
     phase = PH_LINEARIZE;
-    lin_d = P.lin;
-    ev_d = P.lin;
+    lin_d = lin_arg();
+    ev_d = lin_arg();
     corr_sel = 0;
   } else {
     phase = st->phase;
@@ -867,8 +886,8 @@ __global__ FVH_COST_BOUNDS void cost_kernel(CostParams P) {
     w_lo = lo * P.groups_per_src;
     n_items = min(lo + chunk, n_src) * P.groups_per_src;
   }
-  int* corr_old = P.corr + (size_t)corr_sel * P.corr_stride;                      // read (stored ids)
-  int* corr_new = fused ? P.corr + (size_t)(corr_sel ^ 1) * P.corr_stride : corr_old;  // written by the find
+  int* corr_old = corr_base() + (size_t)corr_sel * P.corr_stride;                      // read (stored ids)
+  int* corr_new = fused ? corr_base() + (size_t)(corr_sel ^ 1) * P.corr_stride : corr_old;  // written by the find
   // Wave roles (NDT instantiations with one lookup per item, device LM, grids of at most one workgroup per CU -- `P.split`): a fused trip
   // is two independent pieces of work per item -- (A) the trial error of the STORED id at the trial pose (old record, R_lin C R_lin^T,
   // one Mahalanobis term) and (B) the new linearisation (voxel coordinate, probe, record, R_ev C R_ev^T, hit term, 28 item sums, the
@@ -1297,7 +1316,7 @@ __global__ FVH_COST_BOUNDS void cost_kernel(CostParams P) {
       const double x = (red[0][vv] + red[1][vv]) + (red[2][vv] + red[3][vv]);
       // write-through (sc1) so another workgroup can read it from L2 without a release fence;
       // row slot v: sums 0..27, fused trial error at 28 (== NSUM), 29..31 zero
-      __hip_atomic_store(&P.partials[(size_t)lb * PART_STRIDE + vv], x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&partials()[(size_t)lb * PART_STRIDE + vv], x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -1313,7 +1332,7 @@ __global__ FVH_COST_BOUNDS void cost_kernel(CostParams P) {
 #pragma unroll
         for (int u = 0; u < 8; u++) {
           const unsigned j = j0 + 8 * u;
-          t[u] = (j < gsize) ? __hip_atomic_load(&P.partials[(size_t)(grp + j * NG) * PART_STRIDE + v], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
+          t[u] = (j < gsize) ? __hip_atomic_load(&partials()[(size_t)(grp + j * NG) * PART_STRIDE + v], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
         }
 #pragma unroll
         for (int u = 0; u < 8; u++) s += t[u];
@@ -1326,7 +1345,7 @@ __global__ FVH_COST_BOUNDS void cost_kernel(CostParams P) {
       double s = 0.0;
 #pragma unroll
       for (int c = 0; c < 8; c++) s += fin[c][v];
-      __hip_atomic_store(&P.partials[out_row * PART_STRIDE + v], s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&partials()[out_row * PART_STRIDE + v], s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -1336,7 +1355,7 @@ __global__ FVH_COST_BOUNDS void cost_kernel(CostParams P) {
     {
       const int v = tid & 31;
       const unsigned g = tid >> 5;
-      fin[g][v] = (g < ngroups) ? __hip_atomic_load(&P.partials[(first_row + g) * PART_STRIDE + v], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
+      fin[g][v] = (g < ngroups) ? __hip_atomic_load(&partials()[(first_row + g) * PART_STRIDE + v], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
     }
     __syncthreads();
     if (tid < PART_STRIDE) {
@@ -1349,7 +1368,7 @@ __global__ FVH_COST_BOUNDS void cost_kernel(CostParams P) {
   };
   // what lm_init_kernel would have written (first evaluation of an align), on the LDS copy of the state
   auto init_state = [&]() {
-    s_st.x0 = P.lin; s_st.xi = P.lin; s_st.x_lin = P.lin;
+    s_st.x0 = lin_arg(); s_st.xi = lin_arg(); s_st.x_lin = lin_arg();
     s_st.rotation_epsilon = P.rotation_epsilon; s_st.transformation_epsilon = P.transformation_epsilon; s_st.lm_init_lambda_factor = P.lm_init_lambda_factor;
     s_st.max_iterations = P.max_iterations; s_st.lm_max_iterations = P.lm_max_iterations; s_st.optimizer = P.optimizer; s_st.pad_ = 0;
     s_st.lambda = -1.0; s_st.nu = 2.0; s_st.y0 = 0.0;
@@ -1365,19 +1384,19 @@ __global__ FVH_COST_BOUNDS void cost_kernel(CostParams P) {
     // thread, fixed order), publishes one group row and arrives at the top counter; the last group
     // sums the <= 8 group rows and runs the LM step. No address sees more than gridDim/8 + 8 atomics
     // and no thread walks a long chain of dependent L2 round trips.
-    if (tid == 0) s_last = (atomicAdd(&P.ticket[grp], 1u) == gsize - 1);
+    if (tid == 0) s_last = (atomicAdd(&ticket()[grp], 1u) == gsize - 1);
     __syncthreads();
     if (!s_last) return;
     FVH_STAMP(3);
     reduce_group_rows((size_t)MAX_PARTIAL_ROWS + grp);
-    if (tid == 0) s_last = (atomicAdd(&P.ticket[TICKET_GROUPS], 1u) == ngroups - 1);
+    if (tid == 0) s_last = (atomicAdd(&ticket()[TICKET_GROUPS], 1u) == ngroups - 1);
     __syncthreads();
     if (!s_last) return;
     FVH_STAMP(4);
 
     // ---- the very last workgroup: sum the group rows in group order (deterministic), LM step ----
     reduce_final((size_t)MAX_PARTIAL_ROWS);
-    if (tid <= TICKET_GROUPS) P.ticket[tid] = 0;  // re-arm for the next launch
+    if (tid <= TICKET_GROUPS) ticket()[tid] = 0;  // re-arm for the next launch
     if (MODE == MODE_VGICP && P.peer.n > 1) {  // multi-GPU: sum the blocks of all ranks (rank order -> bit-identical on every rank); one workgroup per rank is in here
       __syncthreads();
       if (!peer_exchange_sums(P.peer, red[0], P.peer.xbase, P.peer_watchdog_ticks, tid, 256, &s_last)) {
@@ -1453,9 +1472,9 @@ __global__ FVH_COST_BOUNDS void cost_kernel(CostParams P) {
     auto abort_tag_of = [&]() { unsigned long long t = ltag * 4096ull; asm volatile("" : "+s"(t)); return -(double)t; };  // launch-specific: a poisoned row of an older launch means nothing
     __shared__ double bc[BCAST_PAIRS];  // payload of the broadcast row as seen by this workgroup
     __shared__ unsigned s_abort;
-    pair_t* wrows = reinterpret_cast<pair_t*>(P.partials + WG_ROWS_OFFSET);
-    pair_t* trows = reinterpret_cast<pair_t*>(P.partials + TAGGED_ROWS_OFFSET) + (size_t)(trip & 1u) * (TICKET_GROUPS + 1) * PART_STRIDE;
-    pair_t* bcast = reinterpret_cast<pair_t*>(P.bcast);
+    pair_t* wrows = reinterpret_cast<pair_t*>(partials() + WG_ROWS_OFFSET);
+    pair_t* trows = reinterpret_cast<pair_t*>(partials() + TAGGED_ROWS_OFFSET) + (size_t)(trip & 1u) * (TICKET_GROUPS + 1) * PART_STRIDE;
+    pair_t* bcast = reinterpret_cast<pair_t*>(bcast_base());
     const bool local = P.xcd_local != 0;  // (kernel argument: uniform)
     // copies of the broadcast row a group owns: all of them for a single group, PERSIST_REPLICAS / 8 each otherwise; workgroup lb
     // polls copy (lb / NG) % reps of its group -- no address is read by more than ~15 workgroups
@@ -1680,14 +1699,14 @@ __global__ FVH_COST_BOUNDS void cost_kernel(CostParams P) {
       }
       if (lb == 0 && s_st.phase == PH_DONE) {  // the state leaves the LDS once, at the end (the kernel boundary makes it visible)
         for (int i = tid; i < ST_WORDS; i += 256) st_words[i] = reinterpret_cast<const unsigned long long*>(&s_st)[i];
-        if (P.result_host) {
+        if (result_host()) {
           // ... and goes straight to the host through mapped pinned memory: the caller spins on the sequence word instead of
           // paying a device-to-host copy kernel and a stream synchronisation (~8 us of a 300 us registration)
           for (int i = tid; i < ST_WORDS; i += 256)
-            __hip_atomic_store(&P.result_host[i], reinterpret_cast<const unsigned long long*>(&s_st)[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(&result_host()[i], reinterpret_cast<const unsigned long long*>(&s_st)[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
           __syncthreads();
-          if (tid == 0) __hip_atomic_store(&P.result_host[ST_WORDS + 1], P.launch_tag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+          if (tid == 0) __hip_atomic_store(&result_host()[ST_WORDS + 1], P.launch_tag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
       }
     } else {
@@ -1738,6 +1757,24 @@ __global__ FVH_COST_BOUNDS void cost_kernel(CostParams P) {
     __syncthreads();  // bc[] is rewritten after the next barrier; s_pose is read by the next trip
   }
   }  // trips
+}
+
+template <typename Real, int MODE, bool PERSIST, int CH = COST_CH, bool GN = false>
+__global__ FVH_COST_BOUNDS void cost_kernel(CostParams P) {
+  // Workgroup id / count. The dispatcher hands consecutive blocks to consecutive XCDs (block b runs on XCD (b + c) % 8 with one c per
+  // launch: tools/probes/probe_xcc.hip). That is an observation, not a contract: every workgroup publishes the c it sees with its sums and
+  // the collectors end the launch if they ever differ (`xcd_local` in the body).
+  cost_body<Real, MODE, PERSIST, CH, GN, false>(P, 0u, 0u, 0u, nullptr);
+}
+
+// K hypotheses in one grid of K x G.nb_h workgroups (see GangParams): the host passes the base address of every per-align buffer, xcd_local = 0
+// (a gang's groups need not follow the dispatcher's XCD rotation) and no LM trace. A gang that reaches PH_DONE leaves; its slots free up
+// while the others keep working. Used by both routes: one persistent launch, or one launch per LM transition (finished gangs return at once).
+template <typename Real, int MODE, bool PERSIST, int CH = COST_CH, bool GN = false>
+__global__ FVH_COST_BOUNDS void lm_gang_kernel(CostParams P, GangParams G) {
+  const unsigned nb_h = (unsigned)G.nb_h;
+  const unsigned gang = blockIdx.x / nb_h;
+  cost_body<Real, MODE, PERSIST, CH, GN, true>(P, blockIdx.x - gang * nb_h, nb_h, gang, G.guesses);
 }
 
 }  // namespace fvh

@@ -69,6 +69,13 @@ static Matrix4f numpy2mat4(const Mat4& m) {
   for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) M(i, j) = (float)r(i, j);
   return M;
 }
+static std::vector<Matrix4f> numpy2mat4s(const Mat4& m) {  // (K, 4, 4) -> K poses
+  if (m.ndim() != 3 || m.shape(1) != 4 || m.shape(2) != 4) throw std::invalid_argument("poses must be a (K, 4, 4) array");
+  std::vector<Matrix4f> out((size_t)m.shape(0));
+  auto r = m.unchecked<3>();
+  for (py::ssize_t k = 0; k < m.shape(0); k++) for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) out[k](i, j) = (float)r(k, i, j);
+  return out;
+}
 static py::array_t<float> mat4_to_numpy(const Matrix4f& M) {
   py::array_t<float> out({4, 4});
   auto w = out.mutable_unchecked<2>();
@@ -223,7 +230,30 @@ PYBIND11_MODULE(pygicp, m) {
         Cloud aligned;
         reg.align(aligned, numpy2mat4(initial_guess));
         return mat4_to_numpy(reg.getFinalTransformation());
-      }, py::arg("initial_guess") = identity4());
+      }, py::arg("initial_guess") = identity4())
+      // not in the reference: K initial guesses of the same pair in ONE device launch (include/fast_vgicp_hip.h: fvh_vgicp_align_multi /
+      // fvh_ndt_align_multi; FastVGICPCuda, FastVGICP, NDTCuda -- FastGICP raises). (K, 4, 4) ->
+      // (T (K, 4, 4) float64, final_error (K,), converged (K,) bool, iterations (K,) int: getNumIterations() of align(guess k))
+      .def("align_multi", [](Lsq& reg, const Mat4& guesses) {
+        const std::vector<MultiAlignResult> rs = reg.alignMulti(numpy2mat4s(guesses));
+        const py::ssize_t k = (py::ssize_t)rs.size();
+        py::array_t<double> T({k, (py::ssize_t)4, (py::ssize_t)4}), err(k);
+        py::array_t<bool> conv(k);
+        py::array_t<int> its(k);
+        for (py::ssize_t i = 0; i < k; i++) {
+          std::memcpy(T.mutable_data() + 16 * i, rs[i].T.m, 16 * sizeof(double));
+          err.mutable_data()[i] = rs[i].final_error;
+          conv.mutable_data()[i] = rs[i].converged;
+          its.mutable_data()[i] = rs[i].nr_iterations;
+        }
+        return py::make_tuple(T, err, conv, its);
+      }, py::arg("guesses"))
+      // ... and the pose with the lowest fitness score becomes the result as align() would leave it: (get_final_transformation(), index)
+      .def("align_best", [](Lsq& reg, const Mat4& guesses, double max_range) {
+        Cloud aligned;
+        const int best = reg.alignBest(numpy2mat4s(guesses), max_range, aligned);
+        return py::make_tuple(mat4_to_numpy(reg.getFinalTransformation()), best);
+      }, py::arg("guesses"), py::arg("max_range") = std::numeric_limits<double>::max());
 
   py::class_<VGICPCuda, Lsq, std::shared_ptr<VGICPCuda>>(m, "FastVGICPCuda")
       .def(py::init([](int device) { return std::make_shared<VGICPCuda>(device); }), py::arg("device") = 0)

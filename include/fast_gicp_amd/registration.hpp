@@ -69,6 +69,20 @@ struct Matrix4f {  // row-major 4x4 (Eigen::Matrix4f stand-in)
 
 using Matrix6d = std::array<double, 36>;  // row-major (symmetric)
 using Vector6d = std::array<double, 6>;
+struct Matrix4d {  // row-major 4x4 (Eigen::Matrix4d stand-in)
+  double m[16];
+  double& operator()(int r, int c) { return m[r * 4 + c]; }
+  double operator()(int r, int c) const { return m[r * 4 + c]; }
+};
+/// one hypothesis of alignMulti (no reference counterpart): what align(guess k) leaves in getFinalTransformation() (here in double),
+/// getFinalHessian(), hasConverged(), getNumIterations()
+struct MultiAlignResult {
+  Matrix4d T;
+  Matrix6d H;
+  double final_error;
+  bool converged;
+  int nr_iterations;
+};
 
 struct Isometry3d {  // row-major R | t, double
   double R[9];
@@ -312,6 +326,61 @@ public:
   /// pcl::Registration::getFitnessScore(max_range): mean squared exact-NN distance of T*source to the target
   virtual double getFitnessScore(double max_range = std::numeric_limits<double>::max()) = 0;
 
+  /// K initial guesses of the same source / target pair registered in ONE device launch (C ABI: fvh_vgicp_align_multi / fvh_ndt_align_multi;
+  /// no reference counterpart). Result k is, bit for bit, what align(guesses[k]) computes under the same grid plan (see the C ABI); the
+  /// class's getters are left as the last of K align() calls leaves the device handle. 1 <= K <= 64. Classes whose device LM does not go
+  /// through fvh_vgicp_align / fvh_ndt_align (FastGICP) throw.
+  std::vector<MultiAlignResult> alignMulti(const std::vector<Matrix4f>& guesses) {
+    if (!input_ || !target_) throw std::invalid_argument("alignMulti: source / target cloud not set");
+    const int k = (int)guesses.size();
+    std::vector<double> g16(16 * (size_t)k);
+    for (int i = 0; i < k; i++) Isometry3d::from(guesses[i]).to_colmajor16(&g16[16 * (size_t)i]);
+    fvh_lm_params p{max_iterations_, rotation_epsilon_, transformation_epsilon_, lm_max_iterations_, lm_init_lambda_factor_,
+                    lsq_optimizer_type_ == LSQ_OPTIMIZER_TYPE::GaussNewton ? 1 : 0};
+    std::vector<fvh_lm_result> r((size_t)std::max(k, 1));
+    device_align_multi(k, g16.data(), &p, r.data(), &multi_grid_blocks_);
+    std::vector<MultiAlignResult> out((size_t)k);
+    for (int i = 0; i < k; i++) {
+      const Isometry3d x = Isometry3d::from_colmajor16(r[i].T);
+      MultiAlignResult& o = out[i];
+      std::memset(o.T.m, 0, sizeof(o.T.m));
+      for (int a = 0; a < 3; a++) { for (int b = 0; b < 3; b++) o.T(a, b) = x.R[a * 3 + b]; o.T(a, 3) = x.t[a]; }
+      o.T(3, 3) = 1.0;
+      for (int a = 0; a < 6; a++) for (int b = 0; b < 6; b++) o.H[a * 6 + b] = r[i].H[b * 6 + a];
+      o.final_error = r[i].final_error;
+      o.converged = r[i].converged != 0;
+      o.nr_iterations = r[i].nr_iterations;
+    }
+    return out;
+  }
+  /// alignMulti, then the pose with the lowest device fitness score (getFitnessScore(max_range) at that pose; ties go to the lowest index)
+  /// becomes the result as align() would set it: getFinalTransformation(), hasConverged(), getNumIterations(), getFinalHessian(), `output`.
+  /// Returns the chosen index.
+  int alignBest(const std::vector<Matrix4f>& guesses, double max_range, PointCloudSource& output) {
+    const std::vector<MultiAlignResult> rs = alignMulti(guesses);
+    int best = -1;
+    double best_score = 0.0;
+    for (int i = 0; i < (int)rs.size(); i++) {
+      double T16[16];
+      for (int a = 0; a < 4; a++) for (int b = 0; b < 4; b++) T16[b * 4 + a] = rs[i].T(a, b);
+      const double score = device_fitness(T16, max_range);
+      if (best < 0 || score < best_score) { best = i; best_score = score; }
+    }
+    if (best < 0) throw std::invalid_argument("alignBest: no guesses");
+    const MultiAlignResult& b = rs[best];
+    Isometry3d x;
+    for (int a = 0; a < 3; a++) { for (int c = 0; c < 3; c++) x.R[a * 3 + c] = b.T(a, c); x.t[a] = b.T(a, 3); }
+    final_transformation_ = x.cast_float();
+    converged_ = b.converged;
+    nr_iterations_ = b.nr_iterations;
+    final_hessian_ = b.H;
+    output.points.resize(input_->size());
+    detail::transform_points(input_->points.data(), output.points.data(), input_->size(), final_transformation_.m);
+    return best;
+  }
+  /// workgroups per hypothesis of the last alignMulti (fvh_*_align_multi's grid_blocks_out)
+  int getMultiGridBlocks() const { return multi_grid_blocks_; }
+
 protected:
   virtual void computeTransformation(PointCloudSource& output, const Matrix4f& guess) {  // lsq_registration_impl.hpp:53-79
     Isometry3d x0 = Isometry3d::from(guess);
@@ -354,6 +423,13 @@ protected:
   virtual double compute_error(const Isometry3d& trans) = 0;
   /// subclasses with a device-resident LM return true after updating x0 / converged_ / nr_iterations_ / final_hessian_
   virtual bool device_align(Isometry3d& x0) { (void)x0; return false; }
+  /// alignMulti / alignBest: the subclass's fvh_*_align_multi and fvh_*_fitness_score
+  virtual void device_align_multi(int k, const double* guesses16, const fvh_lm_params* p, fvh_lm_result* results, int* grid_blocks) {
+    (void)k; (void)guesses16; (void)p; (void)results; (void)grid_blocks;
+    throw std::runtime_error("alignMulti: not offered by this class");
+  }
+  virtual double device_fitness(const double* T16, double max_range) { (void)T16; (void)max_range; throw std::runtime_error("alignBest: not offered by this class"); }
+  int multi_grid_blocks_ = 0;
 
   bool step_optimize(Isometry3d& x0, Isometry3d& delta) {  // :94-104
     return lsq_optimizer_type_ == LSQ_OPTIMIZER_TYPE::GaussNewton ? step_gn(x0, delta) : step_lm(x0, delta);
@@ -600,6 +676,14 @@ protected:
     trans.to_colmajor16(T16);
     call(fvh_vgicp_compute_error(core_, T16, nullptr, nullptr, &err), "compute_error");
     return err;
+  }
+  void device_align_multi(int k, const double* guesses16, const fvh_lm_params* p, fvh_lm_result* results, int* grid_blocks) override {
+    call(fvh_vgicp_align_multi(core_, k, guesses16, p, results, grid_blocks), "align_multi");
+  }
+  double device_fitness(const double* T16, double max_range) override {
+    double score = 0;
+    call(fvh_vgicp_fitness_score(core_, T16, max_range, &score), "fitness_score");
+    return score;
   }
   bool device_align(Isometry3d& x0) override {
     double g16[16];
@@ -879,6 +963,14 @@ protected:
     this->call(fvh_vgicp_compute_error(core_, T16, nullptr, nullptr, &err), "compute_error");
     return err;
   }
+  void device_align_multi(int k, const double* guesses16, const fvh_lm_params* p, fvh_lm_result* results, int* grid_blocks) override {
+    this->call(fvh_vgicp_align_multi(core_, k, guesses16, p, results, grid_blocks), "align_multi");
+  }
+  double device_fitness(const double* T16, double max_range) override {
+    double score = 0;
+    this->call(fvh_vgicp_fitness_score(core_, T16, max_range, &score), "fitness_score");
+    return score;
+  }
   bool device_align(Isometry3d& x0) override {
     double g16[16];
     x0.to_colmajor16(g16);
@@ -983,6 +1075,15 @@ protected:
   void computeTransformation(typename Base::PointCloudSource& output, const Matrix4f& guess) override {  // :76-79
     call(fvh_ndt_create_voxelmaps(core_), "create_voxelmaps");
     Base::computeTransformation(output, guess);
+  }
+  void device_align_multi(int k, const double* guesses16, const fvh_lm_params* p, fvh_lm_result* results, int* grid_blocks) override {
+    call(fvh_ndt_create_voxelmaps(core_), "create_voxelmaps");
+    call(fvh_ndt_align_multi(core_, k, guesses16, p, results, grid_blocks), "align_multi");
+  }
+  double device_fitness(const double* T16, double max_range) override {
+    double score = 0;
+    call(fvh_ndt_fitness_score(core_, T16, max_range, &score), "fitness_score");
+    return score;
   }
   double linearize(const Isometry3d& trans, Matrix6d* H, Vector6d* b) override {
     double T16[16], err = 0, Hc[36];

@@ -191,6 +191,18 @@ int fvh_vgicp_compute_error(fvh_vgicp* h, const double* T16, double* H36, double
  * lookups per evaluation, or after the barrier watchdog aborted a persistent launch (FVH_PERSISTENT=0 forces it).
  * All routes produce bit-identical results. */
 int fvh_vgicp_align(fvh_vgicp* h, const double* guess16, const fvh_lm_params* params, fvh_lm_result* result);
+/* new: K independent LM problems (the same clouds, K initial guesses) in one launch. results[k] equals, bit for bit,
+ * fvh_vgicp_align(h, guesses16 + 16 k, params) on a handle whose cost_max_blocks is grid_blocks_out (K = 1: plain align, default plan).
+ * 1 <= k <= 64; guesses column-major, finite. grid_blocks_out may be NULL.
+ * Each hypothesis runs in its own gang of grid_blocks_out workgroups with its own LM state; all K share the prepared source, its
+ * covariances and the target voxel map. One persistent launch when the K gangs fit the co-resident workgroup slots together (the gangs
+ * shrink to fit, down to 8 workgroups), else one launch per LM transition over all K gangs; an aborted persistent launch is redone on
+ * that route with the same plan. Afterwards the handle is where `for k: fvh_vgicp_align(guess k)` leaves it (linearisation pose and
+ * correspondences of hypothesis K-1: a later compute_error / align gives the same bits either way). The LM debug trace is not recorded.
+ * Refused: multi-GPU handles (FVH_ERR_UNSUPPORTED), an align_async in flight (FVH_ERR_BAD_STATE), k out of range, null pointers and
+ * non-finite guesses (FVH_ERR_INVALID_ARGUMENT); the handle stays usable. FastGICP (nearest-point correspondences) has no multi call. */
+int fvh_vgicp_align_multi(fvh_vgicp* h, int k, const double* guesses16, const fvh_lm_params* params,
+                          fvh_lm_result* results, int* grid_blocks_out);
 /* new: a scan stream as a two-stage pipeline (scan-to-scan odometry, src/kitti.cpp:95-128 / src/align.cpp:87-101 with the preparation of
  * scan k+1 hidden under the registration of scan k). The handle owns a SECOND stream and a prepared-source slot:
  *   fvh_vgicp_prepare_source_device  packs a device cloud into the slot and queues, on the second stream, the first `stages` stages of what
@@ -341,6 +353,10 @@ int fvh_ndt_create_source_voxelmap(fvh_ndt* h);                                 
 int fvh_ndt_update_correspondences(fvh_ndt* h, const double* T16);                           /* [NC]:49 */
 int fvh_ndt_compute_error(fvh_ndt* h, const double* T16, double* H36, double* b6, double* error); /* [NC]:50 */
 int fvh_ndt_align(fvh_ndt* h, const double* guess16, const fvh_lm_params* params, fvh_lm_result* result);
+/* new: fvh_vgicp_align_multi for NDT (P2D and D2D), with the same contract against fvh_ndt_align. Also refused (FVH_ERR_UNSUPPORTED):
+ * tiled handles (fvh_ndt_set_source_tile). */
+int fvh_ndt_align_multi(fvh_ndt* h, int k, const double* guesses16, const fvh_lm_params* params,
+                        fvh_lm_result* results, int* grid_blocks_out);
 /* new: a frame stream as a two-stage pipeline (src/kitti.cpp:95-128 with the preparation of frame k+1 hidden under the registration of
  * frame k). The handle owns a SECOND stream and a prepared-source slot:
  *   fvh_ndt_align_async          launches the LM kernel on the main stream and returns; fvh_ndt_align_wait collects its result
