@@ -460,6 +460,39 @@ class VGICPCore(_Core):
     def create_target_voxelmap(self):
         self._call("create_target_voxelmap")
 
+    # ---- incremental target map (include/fast_vgicp_hip.h: fvh_vgicp_map_begin ...) ----
+    def map_begin(self, expected_voxels=0):
+        """Start (or restart) an empty incremental target map at the handle's resolution and voxel accumulation mode."""
+        self._call("map_begin", int(expected_voxels))
+
+    def map_insert_source(self, T=None):
+        """Add the current source (points + covariances) to the map at pose T (4x4, default identity)."""
+        t = _IDENTITY16 if T is None else _colmajor16(T)
+        self._call("map_insert_source", _p(t))
+
+    def map_insert_cloud(self, xyz, covs, T=None, device_ptr=None, n=None, stride=3):
+        """Add a cloud that is not the source: host points (N x 3 float32) or a device pointer (device_ptr, n, stride), covariances N x 3 x 3 on the host."""
+        t = _IDENTITY16 if T is None else _colmajor16(T)
+        c = np.ascontiguousarray(covs, np.float64)
+        if device_ptr is not None:
+            self._call("map_insert_cloud", C.c_void_p(device_ptr), int(n), int(stride), _p(c), _p(t), 1)
+        else:
+            a = _f32(xyz)
+            self._call("map_insert_cloud", _p(a), len(a), 3, _p(c), _p(t), 0)
+
+    def map_prune(self, center=None, radius=0.0, max_age=0):
+        """Drop voxels further than `radius` from `center` (None: no distance rule) and those untouched by the last max_age inserts (0: no age rule). -> voxels removed"""
+        removed = C.c_int(0)
+        c = None if center is None else np.ascontiguousarray(center, np.float64).reshape(3)
+        self._call("map_prune", None if c is None else _p(c), C.c_double(radius), int(max_age), C.byref(removed))
+        return removed.value
+
+    def map_info(self):
+        inc, nv, cap, ni, dr = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        npts = C.c_longlong(0)
+        self._call("map_get_info", C.byref(inc), C.byref(nv), C.byref(cap), C.byref(ni), C.byref(npts), C.byref(dr))
+        return dict(incremental=bool(inc.value), num_voxels=nv.value, capacity=cap.value, num_inserts=ni.value, num_points=npts.value, dropped=dr.value)
+
     def get_voxelmap(self):
         n = C.c_int(0)
         self._call("get_num_voxels", C.byref(n))

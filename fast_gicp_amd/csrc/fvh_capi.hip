@@ -437,6 +437,7 @@ inline void pose_to_colmajor16(const PoseD& p, double* T) {
 }
 
 #include "host_stages.inc.hpp"
+#include "host_incmap.inc.hpp"
 #include "host_gicp.inc.hpp"
 #include "host_downsample.inc.hpp"
 
@@ -483,11 +484,26 @@ struct fvh_vgicp {
   bool shard_map = false;
   int shard_margin = 2;      // voxels of pose motion the halo allows for on top of the reach of the neighbour offsets
   int shard_fallbacks = 0;   // aligns redone on the full map because a source element left the shard's inner box
+  // Incremental target map (fvh_vgicp_map_*, host_incmap.inc.hpp): `voxelmap` keeps its sums and grows in place; there is no cloud behind it
+  bool incremental() const { return voxelmap.inc.live && voxelmap.valid; }
+  CloudDev insert_cloud;     // staging of fvh_vgicp_map_insert_cloud
+  // the target cloud was replaced: the batch map built from the old one is dead; an incremental map never depended on it
+  void target_replaced() { e.has_corr = false; if (!incremental()) voxelmap.invalidate(); gicp_records.invalidate(); }
   int build_map(double res, bool force_safe = false, hipStream_t on_side = nullptr, bool shard = false) {
     live_map_stale = false;
-    return voxel_mode == 2 ? build_voxelmap<2>(&e, target, voxelmap, res, false, force_safe, on_side, shard) : build_voxelmap<0>(&e, target, voxelmap, res, false, force_safe, on_side, shard);
+    const int rc = voxel_mode == 2 ? build_voxelmap<2>(&e, target, voxelmap, res, false, force_safe, on_side, shard) : build_voxelmap<0>(&e, target, voxelmap, res, false, force_safe, on_side, shard);
+    // a batch build replaces an incremental map: the mode ends -- once the build has taken the table over (a call refused for want of a
+    // target cloud / covariances leaves the incremental map as it was; one that failed later has invalidated the map)
+    if (rc == FVH_OK || !voxelmap.valid) voxelmap.inc.live = false;
+    return rc;
   }
-  Rebuild rebuild_safe() { return [this] { return build_map(voxelmap.res, true, nullptr, voxelmap.is_shard); }; }
+  Rebuild rebuild_safe() {
+    return [this] {
+      // (an insert secures its capacity before it launches: an incremental map never reports an overflow, and has no cloud to rebuild from)
+      if (incremental()) return e.fail(FVH_ERR_BAD_STATE, "the incremental target map reported a table overflow; start again with fvh_vgicp_map_begin");
+      return build_map(voxelmap.res, true, nullptr, voxelmap.is_shard);
+    };
+  }
   // A sharded align leaves this rank's SHARD behind as the live map; everything host-driven (update_correspondences, compute_error,
   // the voxel getters) works on the whole map: rebuilt here, at the resolution the live map was built with. (The correspondences of
   // the shard die with it: compute_error then asks for update_correspondences instead of reading the wrong buckets.)
@@ -606,19 +622,26 @@ int fvh_vgicp_destroy(fvh_vgicp* h) {
   if (h->e.side) (void)hipStreamSynchronize(h->e.side);
   if (h->e.stream) (void)hipStreamSynchronize(h->e.stream);
   if (h->pending.active) { h->pending.release_slots(); h->pending.active = false; }
-  h->source.release(); h->target.release(); h->voxelmap.release(); h->gicp_records.release(); h->next_source.release(); h->next_map.release(); h->source_map.release();
+  h->source.release(); h->target.release(); h->voxelmap.release(); h->gicp_records.release(); h->next_source.release(); h->next_map.release(); h->source_map.release(); h->insert_cloud.release();
   if (h->prep_done) (void)hipEventDestroy(h->prep_done);
   h->e.shutdown();
   delete h;
   return FVH_OK;
 }
 const char* fvh_vgicp_last_error(const fvh_vgicp* h) { return h ? h->e.err.c_str() : "null handle"; }
-int fvh_vgicp_set_resolution(fvh_vgicp* h, double r) { CHECK_HANDLE_HOST_ONLY(h); if (!(r > 0)) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "resolution must be > 0"); h->resolution = r; return FVH_OK; }
+int fvh_vgicp_set_resolution(fvh_vgicp* h, double r) {
+  CHECK_HANDLE_HOST_ONLY(h);
+  if (!(r > 0)) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "resolution must be > 0");
+  if (h->incremental() && r != h->voxelmap.res) return h->e.fail(FVH_ERR_BAD_STATE, "set_resolution: an incremental target map is live at another resolution; call fvh_vgicp_map_begin again");
+  h->resolution = r;
+  return FVH_OK;
+}
 int fvh_vgicp_set_kernel_params(fvh_vgicp* h, double w, double d) { CHECK_HANDLE_HOST_ONLY(h); h->kernel_width = w; h->kernel_max_dist = d; return FVH_OK; }
 int fvh_vgicp_set_neighbor_search_method(fvh_vgicp* h, int m, double radius) { CHECK_HANDLE(h); return h->e.set_offsets(m, radius); }
 int fvh_vgicp_set_precision(fvh_vgicp* h, int p) {
   CHECK_HANDLE(h);
   if (p != FVH_COMPUTE_FP64 && p != FVH_COMPUTE_FP32 && p != FVH_COMPUTE_CUDA_COMPAT) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "bad precision");
+  if (p == FVH_COMPUTE_CUDA_COMPAT && h->incremental()) return h->e.fail(FVH_ERR_UNSUPPORTED, "set_precision: FVH_COMPUTE_CUDA_COMPAT has no incremental target map (its voxel sums are float sums in point order)");
   if ((p == FVH_COMPUTE_CUDA_COMPAT) != (h->e.precision == FVH_COMPUTE_CUDA_COMPAT)) { h->voxelmap.invalidate(); h->map_rules_changed(); h->e.has_corr = false; }  // the voxel records of the two arithmetics differ (kernels_compat.hpp)
   h->e.precision = p;
   return FVH_OK;
@@ -628,10 +651,61 @@ int fvh_vgicp_get_engine_params(fvh_vgicp* h, fvh_engine_params* out) { CHECK_HA
 int fvh_vgicp_set_engine_params(fvh_vgicp* h, const fvh_engine_params* p) { CHECK_HANDLE(h); return set_engine_params(&h->e, p); }
 
 int fvh_vgicp_create_target_voxelmap(fvh_vgicp* h) { CHECK_HANDLE(h); return h->build_map(h->resolution); }
+// ---- incremental target map (host_incmap.inc.hpp) ----
+static void cloud_replaced(CloudDev& c);
+static int map_refusal(fvh_vgicp* h, const char* who) {
+  if (h->e.sharded()) return h->e.fail(FVH_ERR_UNSUPPORTED, std::string(who) + ": not on a multi-GPU handle (communicator / peers / tile attached)");
+  if (h->shard_map) return h->e.fail(FVH_ERR_UNSUPPORTED, std::string(who) + ": not with target map sharding on");
+  if (h->e.precision == FVH_COMPUTE_CUDA_COMPAT) return h->e.fail(FVH_ERR_UNSUPPORTED, std::string(who) + ": FVH_COMPUTE_CUDA_COMPAT has no incremental target map (its voxel sums are float sums in point order)");
+  return FVH_OK;
+}
+int fvh_vgicp_map_begin(fvh_vgicp* h, int expected_voxels) {
+  CHECK_HANDLE(h);
+  { const int rc = map_refusal(h, "map_begin"); if (rc) return rc; }
+  h->live_map_stale = false;
+  return incmap_begin(&h->e, h->voxelmap, h->resolution, h->voxel_mode, expected_voxels);
+}
+int fvh_vgicp_map_insert_source(fvh_vgicp* h, const double* T16) {
+  CHECK_HANDLE(h);
+  { const int rc = map_refusal(h, "map_insert_source"); if (rc) return rc; }
+  return incmap_insert(&h->e, h->voxelmap, h->source, T16, "map_insert_source");
+}
+int fvh_vgicp_map_insert_cloud(fvh_vgicp* h, const float* xyz, int n, int stride_floats, const double* covs9, const double* T16, int on_device) {
+  CHECK_HANDLE(h);
+  { const int rc = map_refusal(h, "map_insert_cloud"); if (rc) return rc; }
+  if (!h->incremental()) return h->e.fail(FVH_ERR_BAD_STATE, "map_insert_cloud: no incremental map is live (fvh_vgicp_map_begin)");
+  if (n > 0 && !covs9) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "map_insert_cloud: null covariances");
+  cloud_replaced(h->insert_cloud);
+  int rc = upload_cloud(&h->e, h->insert_cloud, xyz, n, stride_floats, on_device != 0, false);
+  if (!rc && n > 0) rc = set_cov_host(&h->e, h->insert_cloud, covs9);
+  else if (!rc) h->insert_cloud.has_cov = true;
+  if (rc) return rc;
+  return incmap_insert(&h->e, h->voxelmap, h->insert_cloud, T16, "map_insert_cloud");
+}
+int fvh_vgicp_map_prune(fvh_vgicp* h, const double* center3, double radius, int max_age, int* num_removed) {
+  CHECK_HANDLE(h);
+  { const int rc = map_refusal(h, "map_prune"); if (rc) return rc; }
+  return incmap_prune(&h->e, h->voxelmap, center3, radius, max_age, num_removed);
+}
+int fvh_vgicp_map_get_info(fvh_vgicp* h, int* incremental, int* num_voxels, int* capacity, int* num_inserts, long long* num_points, int* num_dropped) {
+  CHECK_HANDLE(h);
+  const bool live = h->incremental();
+  if (incremental) *incremental = live ? 1 : 0;
+  if (capacity) *capacity = live ? (int)h->voxelmap.capacity : 0;
+  if (num_inserts) *num_inserts = live ? (int)h->voxelmap.inc.epoch : 0;
+  if (num_points) *num_points = live ? h->voxelmap.inc.num_points : 0;
+  int cnt[3] = {0, 0, 0};
+  if (live && (num_voxels || num_dropped)) { const int rc = incmap_read_counts(&h->e, h->voxelmap, cnt, nullptr); if (rc) return rc; h->voxelmap.inc.voxel_bound = cnt[0]; }
+  if (num_voxels) *num_voxels = cnt[0];
+  if (num_dropped) *num_dropped = cnt[1];
+  return FVH_OK;
+}
 int fvh_vgicp_set_voxel_accumulation_mode(fvh_vgicp* h, int mode) {
   CHECK_HANDLE(h);
   if (mode < 0 || mode > 2) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "unknown voxel accumulation mode");
-  if (mode != h->voxel_mode) { h->voxelmap.invalidate(); h->map_rules_changed(); h->e.has_corr = false; }
+  if (h->incremental() && (mode == 2) != (h->voxelmap.inc.mode == 2)) return h->e.fail(FVH_ERR_BAD_STATE, "set_voxel_accumulation_mode: an incremental target map is live in the other mode; call fvh_vgicp_map_begin again");
+  if (mode != h->voxel_mode && h->incremental()) h->map_rules_changed();  // (ADDITIVE <-> ADDITIVE_WEIGHTED: the same voxel type, the live map stays)
+  else if (mode != h->voxel_mode) { h->voxelmap.invalidate(); h->map_rules_changed(); h->e.has_corr = false; }
   h->voxel_mode = mode;
   return FVH_OK;
 }
@@ -639,7 +713,8 @@ int fvh_vgicp_set_voxel_accumulation_mode(fvh_vgicp* h, int mode) {
 int fvh_vgicp_set_target_map_sharding(fvh_vgicp* h, int on, int margin_voxels) {
   CHECK_HANDLE(h);
   if (margin_voxels < 0 || margin_voxels > 64) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "set_target_map_sharding: margin must be within [0, 64] voxels");
-  if ((on != 0) != h->shard_map || margin_voxels != h->shard_margin) { h->voxelmap.invalidate(); h->e.has_corr = false; }
+  if (on && h->incremental()) return h->e.fail(FVH_ERR_UNSUPPORTED, "set_target_map_sharding: an incremental target map cannot be sharded");
+  if (((on != 0) != h->shard_map || margin_voxels != h->shard_margin) && !h->incremental()) { h->voxelmap.invalidate(); h->e.has_corr = false; }
   h->shard_map = on != 0;
   h->shard_margin = margin_voxels;
   return FVH_OK;
@@ -673,6 +748,7 @@ int fvh_vgicp_debug_get_spatial_order(fvh_vgicp* h, int which, int* order, float
 }
 int fvh_vgicp_swap_source_and_target(fvh_vgicp* h) {
   CHECK_HANDLE(h);
+  if (h->incremental()) return h->e.fail(FVH_ERR_BAD_STATE, "swap_source_and_target: the live target map is incremental -- there is no cloud behind it to become a source");
   h->source.swap(h->target);
   h->e.has_corr = false;
   std::swap(h->voxelmap, h->source_map);   // (the map of the old target stays with its cloud, now the source ...
@@ -693,6 +769,7 @@ int fvh_vgicp_swap_source_and_target(fvh_vgicp* h) {
 }
 int fvh_vgicp_gicp_swap_source_and_target(fvh_vgicp* h) {  // FastGICP::swapSourceAndTarget (fast_gicp_impl.hpp:56-62): no voxel map to rebuild
   CHECK_HANDLE(h);
+  if (h->incremental()) return h->e.fail(FVH_ERR_BAD_STATE, "gicp_swap_source_and_target: the live target map is incremental -- there is no cloud behind it to become a source");
   h->source.swap(h->target);
   h->e.has_corr = false;
   h->voxelmap.invalidate();
@@ -709,11 +786,11 @@ static int uploaded(Engine* e, CloudDev& c, int rc) {
   return ensure_sorted(e, c);
 }
 int fvh_vgicp_set_source_cloud(fvh_vgicp* h, const float* xyz, int n) { CHECK_HANDLE_SOURCE_CHAIN(h); h->e.has_corr = false; cloud_replaced(h->source); h->source_changed(); return uploaded(&h->e, h->source, upload_cloud(&h->e, h->source, xyz, n, 3, false)); }
-int fvh_vgicp_set_target_cloud(fvh_vgicp* h, const float* xyz, int n) { CHECK_HANDLE(h); h->e.has_corr = false; h->voxelmap.invalidate(); h->gicp_records.invalidate(); cloud_replaced(h->target); return uploaded(&h->e, h->target, upload_cloud(&h->e, h->target, xyz, n, 3, false)); }
+int fvh_vgicp_set_target_cloud(fvh_vgicp* h, const float* xyz, int n) { CHECK_HANDLE(h); h->target_replaced(); cloud_replaced(h->target); return uploaded(&h->e, h->target, upload_cloud(&h->e, h->target, xyz, n, 3, false)); }
 int fvh_vgicp_set_source_cloud_strided(fvh_vgicp* h, const float* xyz, int n, int stride) { CHECK_HANDLE_SOURCE_CHAIN(h); h->e.has_corr = false; cloud_replaced(h->source); h->source_changed(); return uploaded(&h->e, h->source, upload_cloud(&h->e, h->source, xyz, n, stride, false)); }
-int fvh_vgicp_set_target_cloud_strided(fvh_vgicp* h, const float* xyz, int n, int stride) { CHECK_HANDLE(h); h->e.has_corr = false; h->voxelmap.invalidate(); h->gicp_records.invalidate(); cloud_replaced(h->target); return uploaded(&h->e, h->target, upload_cloud(&h->e, h->target, xyz, n, stride, false)); }
+int fvh_vgicp_set_target_cloud_strided(fvh_vgicp* h, const float* xyz, int n, int stride) { CHECK_HANDLE(h); h->target_replaced(); cloud_replaced(h->target); return uploaded(&h->e, h->target, upload_cloud(&h->e, h->target, xyz, n, stride, false)); }
 int fvh_vgicp_set_source_cloud_device(fvh_vgicp* h, const float* d, int n, int stride) { CHECK_HANDLE_SOURCE_CHAIN(h); h->e.has_corr = false; cloud_replaced(h->source); h->source_changed(); return uploaded(&h->e, h->source, upload_cloud(&h->e, h->source, d, n, stride, true)); }
-int fvh_vgicp_set_target_cloud_device(fvh_vgicp* h, const float* d, int n, int stride) { CHECK_HANDLE(h); h->e.has_corr = false; h->voxelmap.invalidate(); h->gicp_records.invalidate(); cloud_replaced(h->target); return uploaded(&h->e, h->target, upload_cloud(&h->e, h->target, d, n, stride, true)); }
+int fvh_vgicp_set_target_cloud_device(fvh_vgicp* h, const float* d, int n, int stride) { CHECK_HANDLE(h); h->target_replaced(); cloud_replaced(h->target); return uploaded(&h->e, h->target, upload_cloud(&h->e, h->target, d, n, stride, true)); }
 int fvh_vgicp_set_source_neighbors(fvh_vgicp* h, int k, const int* idx) { CHECK_HANDLE(h); return set_neighbors(&h->e, h->source, k, idx); }
 int fvh_vgicp_set_target_neighbors(fvh_vgicp* h, int k, const int* idx) { CHECK_HANDLE(h); return set_neighbors(&h->e, h->target, k, idx); }
 int fvh_vgicp_find_source_neighbors(fvh_vgicp* h, int k) { CHECK_HANDLE_SOURCE_CHAIN(h); return h->e.after_source_chain_call(find_neighbors(&h->e, h->source, k)); }
@@ -1098,7 +1175,11 @@ int fvh_comm_unique_id(void* id128) {
   if (!g_rccl.load()) return FVH_ERR_COMM;
   return g_rccl.GetUniqueId(id128) == 0 ? FVH_OK : FVH_ERR_COMM;
 }
-int fvh_vgicp_comm_init(fvh_vgicp* h, const void* id, int nranks, int rank) { CHECK_HANDLE(h); return comm_init(&h->e, id, nranks, rank); }
+int fvh_vgicp_comm_init(fvh_vgicp* h, const void* id, int nranks, int rank) {
+  CHECK_HANDLE(h);
+  if (h->incremental()) return h->e.fail(FVH_ERR_BAD_STATE, "comm_init: an incremental target map is live (every rank would grow a private map); end it first (create_target_voxelmap / a new handle)");
+  return comm_init(&h->e, id, nranks, rank);
+}
 // ---- peer-mapped exchange (kernels_peer.hpp) ----
 int fvh_vgicp_peer_export(fvh_vgicp* h, int max_points, void* ipc_handle64, unsigned long long* process_local_ptr) {
   CHECK_HANDLE(h);
@@ -1126,6 +1207,7 @@ int fvh_vgicp_peer_export(fvh_vgicp* h, int max_points, void* ipc_handle64, unsi
 int fvh_vgicp_peer_attach(fvh_vgicp* h, int nranks, int rank, int ranks_on_this_device, const void* ipc_handles, const unsigned long long* process_local_ptrs) {
   CHECK_HANDLE(h);
   Engine* e = &h->e;
+  if (nranks > 1 && h->incremental()) return e->fail(FVH_ERR_BAD_STATE, "peer_attach: an incremental target map is live (every rank would grow a private map); end it first (create_target_voxelmap / a new handle)");
   if (nranks < 1 || nranks > FVH_MAX_PEERS || rank < 0 || rank >= nranks || ranks_on_this_device < 1 || (!ipc_handles && !process_local_ptrs))
     return e->fail(FVH_ERR_INVALID_ARGUMENT, "peer_attach: bad arguments (at most 8 ranks)");
   if (!e->peer.region) return e->fail(FVH_ERR_BAD_STATE, "peer_attach: call peer_export first");

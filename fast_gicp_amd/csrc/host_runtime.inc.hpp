@@ -125,6 +125,17 @@ struct VoxelMapDev {
   DevBuf keys[2];   // voxel keys, double buffered: keys[cur] belongs to the live map, the other one is what the next build fills
   DevBuf counters;  // 2 sets of 16 ints, [0] num_voxels [1] dropped; set `cur` belongs to the live map
   int cur = 0;
+  // incremental map (fvh_vgicp_map_*, host_incmap.inc.hpp): the persistent per-voxel sums and last-touched stamps (one set per key buffer: a
+  // rehash moves the map to the other side), the dirty list of one insert and its control words {dirty count, 0, removed, 0}
+  struct Incremental {
+    bool live = false;
+    int mode = 0;               // 0 additive, 2 multiplicative (fixed by map_begin)
+    DevBuf sums[2], stamps[2], dirty, ctl;
+    unsigned epoch = 0;         // inserts so far: the stamp of the last one
+    long long num_points = 0;   // points offered to the map since map_begin (skipped ones included)
+    long long voxel_bound = 0;  // host-side upper bound of the voxel count (exact after a readback)
+    void release() { sums[0].release(); sums[1].release(); stamps[0].release(); stamps[1].release(); dirty.release(); ctl.release(); live = false; }
+  } inc;
   unsigned clean_cap = 0;  // keys[cur ^ 1], counter set cur ^ 1 and acc are clean (EMPTY / 0) over this capacity; 0 = unknown
   int* counters_cur() const { return counters.as<int>() + 16 * cur; }
   const unsigned long long* keys_cur() const { return keys[cur].as<unsigned long long>(); }
@@ -137,7 +148,7 @@ struct VoxelMapDev {
   std::vector<int> h_occupied;
   std::unordered_map<int, int> bucket_to_index;
   void invalidate() { valid = false; host_valid = false; has_bitmap = false; is_shard = false; has_canon = false; }
-  void release() { table.release(); acc.release(); occupied.release(); compact_pts.release(); compact_cov.release(); counters.release(); keys[0].release(); keys[1].release(); bitmap.release(); grid.release(); region.release(); canon.release(); compat_keys.release(); compat_idx.release(); compat_seg.release(); compat_hist.release(); clean_cap = 0; has_bitmap = false; is_shard = false; has_canon = false; }
+  void release() { table.release(); acc.release(); occupied.release(); compact_pts.release(); compact_cov.release(); counters.release(); keys[0].release(); keys[1].release(); bitmap.release(); grid.release(); region.release(); canon.release(); compat_keys.release(); compat_idx.release(); compat_seg.release(); compat_hist.release(); inc.release(); clean_cap = 0; has_bitmap = false; is_shard = false; has_canon = false; }
 };
 
 struct Profiler {

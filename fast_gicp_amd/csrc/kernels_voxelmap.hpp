@@ -441,4 +441,258 @@ __global__ __launch_bounds__(256) void vm_grid_set_kernel(const unsigned long lo
   }
 }
 
+// ---- incremental target map (fvh_vgicp_map_*: host_incmap.inc.hpp) ------------------------------------------------------------
+// A map that grows by accumulation: the per-voxel sums are KEPT (vm_finalize_kernel consumes and zeroes VoxelMapDev::acc; these
+// kernels never touch that buffer), so a scan is added with work proportional to the scan:
+//   sums   : capacity x 10 doubles {sum p | sum C^-1 p (3), sum C | sum C^-1 (6), count}, bucket index == key slot. One set: every
+//            flush adds with fp64 atomics (a bucket lives across launches, so no workgroup can own it).
+//   stamps : capacity x u32, the epoch (1-based insert number) of the last insert that touched the bucket; 0 = never touched.
+//   dirty  : the buckets an insert touched, bit 31 set on those it created. Appended by the flush whose exchange CHANGED the stamp:
+//            once per bucket and insert. One counter atomic per workgroup.
+//   ctl    : {dirty count, 0, voxels removed by the last rehash, 0}
+// vm_insert (pose applied on the way in) -> vm_refresh (one thread per DIRTY bucket: record from the sums, new buckets listed).
+// vm_rehash moves the surviving buckets into the other key / sums / stamp buffers: growth and pruning (linear probing cannot
+// delete in place); it recomputes every record from the moved sums, so the single record table needs no second copy.
+constexpr unsigned VM_INC_NEW = 0x80000000u;
+
+// the insert runs at a load factor <= 0.5 secured by the host BEFORE the launch, and may probe the whole table: it cannot fail
+__device__ __forceinline__ unsigned inc_claim(unsigned long long* keys, unsigned mask, unsigned long long key) {
+  unsigned slot = hash_slot(key, mask);
+  for (unsigned it = 0; it <= mask; it++) {
+    const unsigned long long old = atomicCAS(keys + slot, FVH_EMPTY_KEY, key);
+    if (old == FVH_EMPTY_KEY || old == key) return slot;
+    slot = (slot + 1) & mask;
+  }
+  return 0xFFFFFFFFu;
+}
+
+// record {key, n, mean, cov, sqrt(n)} of bucket b from its sums: the arithmetic of vm_finalize_kernel<0 | 2>
+template <int MODE>
+__device__ __forceinline__ void inc_write_record(unsigned long long key, const double* a, uint4* __restrict__ table, unsigned b) {
+  const double cnt = a[9];
+  const double inv = 1.0 / cnt;
+  double mx = a[0] * inv, my = a[1] * inv, mz = a[2] * inv;
+  Sym3<double> C;
+  if (MODE == 0) {
+    C.xx = a[3] * inv; C.xy = a[4] * inv; C.xz = a[5] * inv; C.yy = a[6] * inv; C.yz = a[7] * inv; C.zz = a[8] * inv;
+  } else {
+    C = inverse(Sym3<double>{a[3], a[4], a[5], a[6], a[7], a[8]});
+    const Vec3<double> m = mul(C, Vec3<double>{a[0], a[1], a[2]});
+    mx = m.x; my = m.y; mz = m.z;
+  }
+  const int n = (int)cnt;
+  const double wn = sqrt((double)n);
+  float4* tf = reinterpret_cast<float4*>(table);
+  table[(size_t)b * 4] = make_uint4((unsigned)key, (unsigned)(key >> 32), (unsigned)n, 0u);
+  tf[(size_t)b * 4 + 1] = make_float4((float)mx, (float)my, (float)mz, (float)n);
+  tf[(size_t)b * 4 + 2] = make_float4((float)C.xx, (float)C.xy, (float)C.xz, (float)C.yy);
+  tf[(size_t)b * 4 + 3] = make_float4((float)C.yz, (float)C.zz, __int_as_float(__double2loint(wn)), __int_as_float(__double2hiint(wn)));
+}
+
+// MODE 0 additive, 2 multiplicative. An inserted point is p' = (float)(R p + t) and its covariance C' = (float)(R C R^T), both formed in
+// fp64 and rounded once: the values a batch build of the transformed cloud would be handed.
+template <int MODE>
+__global__ __launch_bounds__(256) void vm_insert_kernel(const float4* __restrict__ pts, const float4* __restrict__ cov, int n, PoseD T, double res,
+                                                        unsigned long long* __restrict__ table_keys, unsigned mask, double* __restrict__ sums, unsigned* __restrict__ stamps,
+                                                        unsigned epoch, unsigned* __restrict__ dirty, int* __restrict__ ctl, int* __restrict__ dropped, const int* __restrict__ order) {
+  __shared__ unsigned long long lkey[VM_LDS_SLOTS];
+  __shared__ double lacc[VM_LDS_SLOTS * VM_ACC_STRIDE];
+  __shared__ int s_cnt, s_base;
+  const int tid = threadIdx.x;
+  for (int s = tid; s < VM_LDS_SLOTS; s += 256) lkey[s] = FVH_EMPTY_KEY;
+  for (int s = tid; s < VM_LDS_SLOTS * VM_ACC_STRIDE; s += 256) lacc[s] = 0.0;
+  if (tid == 0) s_cnt = 0;
+  __syncthreads();
+
+  unsigned pend[3];  // buckets whose stamp this thread changed: the lone unstaged point + two flushed LDS slots
+  int npend = 0;
+  const int i0 = blockIdx.x * 256 + tid;
+  if (i0 < n) {
+    const int i = order ? order[i0] : i0;
+    const float4 p = pts[i];
+    const double x = p.x, y = p.y, z = p.z;
+    const float px = (float)(T.r[0] * x + T.r[1] * y + T.r[2] * z + T.t[0]);
+    const float py = (float)(T.r[3] * x + T.r[4] * y + T.r[5] * z + T.t[1]);
+    const float pz = (float)(T.r[6] * x + T.r[7] * y + T.r[8] * z + T.t[2]);
+    const double fx = floor((double)px / res - 0.5), fy = floor((double)py / res - 0.5), fz = floor((double)pz / res - 0.5);
+    if (!voxel_index_ok(fx, fy, fz)) {
+      atomicAdd(dropped + 1, 1);  // non-finite / absurdly far: belongs to no voxel (counted as vm_accumulate_kernel does)
+    } else {
+      const unsigned long long key = pack_key((int)fx, (int)fy, (int)fz);
+      const float4 c0 = cov[2 * i], c1 = cov[2 * i + 1];
+      const double C[3][3] = {{(double)c0.x, (double)c0.y, (double)c0.z}, {(double)c0.y, (double)c0.w, (double)c1.x}, {(double)c0.z, (double)c1.x, (double)c1.y}};
+      double M[3][3];  // R C
+#pragma unroll
+      for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) M[r][c] = T.r[3 * r] * C[0][c] + T.r[3 * r + 1] * C[1][c] + T.r[3 * r + 2] * C[2][c];
+      auto rcr = [&](int r, int c) { return (double)(float)(M[r][0] * T.r[3 * c] + M[r][1] * T.r[3 * c + 1] + M[r][2] * T.r[3 * c + 2]); };
+      const Sym3<double> Cp = {rcr(0, 0), rcr(0, 1), rcr(0, 2), rcr(1, 1), rcr(1, 2), rcr(2, 2)};
+      double v[VM_ACC_STRIDE];
+      if (MODE == 0) {
+        v[0] = px; v[1] = py; v[2] = pz;
+        v[3] = Cp.xx; v[4] = Cp.xy; v[5] = Cp.xz; v[6] = Cp.yy; v[7] = Cp.yz; v[8] = Cp.zz;
+      } else {
+        const Sym3<double> Ci = inverse(Cp);
+        const Vec3<double> cp = mul(Ci, Vec3<double>{(double)px, (double)py, (double)pz});
+        v[0] = cp.x; v[1] = cp.y; v[2] = cp.z;
+        v[3] = Ci.xx; v[4] = Ci.xy; v[5] = Ci.xz; v[6] = Ci.yy; v[7] = Ci.yz; v[8] = Ci.zz;
+      }
+      v[9] = 1.0;
+      unsigned slot = hash_slot(key, VM_LDS_SLOTS - 1);
+      bool staged = false;
+#pragma unroll 1
+      for (int pr = 0; pr < VM_LDS_PROBES; pr++) {
+        unsigned long long old = atomicCAS(&lkey[slot], FVH_EMPTY_KEY, key);
+        if (old == FVH_EMPTY_KEY || old == key) { staged = true; break; }
+        slot = (slot + 1) & (VM_LDS_SLOTS - 1);
+      }
+      if (staged) {
+#pragma unroll
+        for (int j = 0; j < VM_ACC_STRIDE; j++) atomicAdd(&lacc[slot * VM_ACC_STRIDE + j], v[j]);
+      } else {  // LDS table crowded: straight to the map
+        const unsigned b = inc_claim(table_keys, mask, key);
+        if (b != 0xFFFFFFFFu) {
+#pragma unroll
+          for (int j = 0; j < VM_ACC_STRIDE; j++) atomicAdd(&sums[(size_t)b * VM_ACC_STRIDE + j], v[j]);
+          const unsigned was = atomicExch(stamps + b, epoch);
+          if (was != epoch) pend[npend++] = b | (was == 0u ? VM_INC_NEW : 0u);
+        } else {
+          atomicAdd(dropped, 1);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  // flush: one claim, 10 fp64 adds and one stamp exchange per (workgroup, voxel); the first probes of a thread's two slots are in flight together
+  static_assert(VM_LDS_SLOTS == 512, "two LDS slots per thread of a 256-thread workgroup");
+  unsigned long long fk[2], fold[2];
+  unsigned fslot[2];
+#pragma unroll
+  for (int u = 0; u < 2; u++) {
+    fk[u] = lkey[tid + 256 * u];
+    fslot[u] = hash_slot(fk[u], mask);
+    fold[u] = FVH_EMPTY_KEY;
+    if (fk[u] != FVH_EMPTY_KEY) fold[u] = atomicCAS(table_keys + fslot[u], FVH_EMPTY_KEY, fk[u]);
+  }
+#pragma unroll
+  for (int u = 0; u < 2; u++) {
+    if (fk[u] == FVH_EMPTY_KEY) continue;
+    const int s = tid + 256 * u;
+    unsigned b = fslot[u];
+    if (fold[u] != FVH_EMPTY_KEY && fold[u] != fk[u]) b = inc_claim(table_keys, mask, fk[u]);
+    if (b == 0xFFFFFFFFu) { atomicAdd(dropped, 1); continue; }
+#pragma unroll
+    for (int j = 0; j < VM_ACC_STRIDE; j++) atomicAdd(&sums[(size_t)b * VM_ACC_STRIDE + j], lacc[s * VM_ACC_STRIDE + j]);
+    const unsigned was = atomicExch(stamps + b, epoch);
+    if (was != epoch) pend[npend++] = b | (was == 0u ? VM_INC_NEW : 0u);
+  }
+  // dirty list: positions from an LDS counter, ONE memory-side atomic per workgroup
+  const int pos = npend ? atomicAdd(&s_cnt, npend) : 0;
+  __syncthreads();
+  if (tid == 0) s_base = s_cnt ? atomicAdd(ctl, s_cnt) : 0;
+  __syncthreads();
+  for (int k = 0; k < npend; k++) dirty[s_base + pos + k] = pend[k];
+}
+
+// One thread per DIRTY bucket: the record from the (kept) sums; new buckets join the compact list and the voxel count, and the occupancy
+// bitmap of a large map: a bit inside its box is set, a voxel outside it switches the bitmap off on the device (the LM kernel reads
+// VmGrid::enabled per launch) until the next rehash rebuilds it.
+template <int MODE>
+__global__ __launch_bounds__(256) void vm_refresh_kernel(const unsigned* __restrict__ dirty, int* __restrict__ ctl, const unsigned long long* __restrict__ keys,
+                                                         const double* __restrict__ sums, uint4* __restrict__ table, int* __restrict__ num_voxels, int* __restrict__ occupied,
+                                                         VmGrid* __restrict__ grid, unsigned long long* __restrict__ bitmap) {
+  __shared__ int s_cnt, s_base;
+  if (threadIdx.x == 0) s_cnt = 0;
+  __syncthreads();
+  const int nd = ctl[0];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  bool is_new = false;
+  unsigned b = 0;
+  int local = 0;
+  if (i < nd) {
+    const unsigned d = dirty[i];
+    b = d & ~VM_INC_NEW;
+    is_new = (d & VM_INC_NEW) != 0u;
+    const unsigned long long key = keys[b];
+    double a[VM_ACC_STRIDE];
+#pragma unroll
+    for (int j = 0; j < VM_ACC_STRIDE; j++) a[j] = sums[(size_t)b * VM_ACC_STRIDE + j];
+    inc_write_record<MODE>(key, a, table, b);
+    if (is_new) {
+      local = atomicAdd(&s_cnt, 1);
+      if (grid && grid->enabled) {
+        unsigned long long word;
+        unsigned bit;
+        if (vm_grid_locate(*grid, (unsigned)(key & 0x1FFFFF), (unsigned)((key >> 21) & 0x1FFFFF), (unsigned)((key >> 42) & 0x1FFFFF), word, bit)) atomicOr(&bitmap[word], 1ull << bit);
+        else grid->enabled = 0;
+      }
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) s_base = s_cnt ? atomicAdd(num_voxels, s_cnt) : 0;
+  __syncthreads();
+  if (is_new) occupied[s_base + local] = (int)b;
+}
+
+// what the next counter set starts from when the map moves to the other buffers: no voxels yet, the running `dropped` / skipped counts kept
+__global__ void vm_rehash_begin_kernel(const int* __restrict__ cur_counters, int* __restrict__ next_counters, int* __restrict__ ctl) {
+  if (threadIdx.x == 0) { next_counters[0] = 0; next_counters[1] = cur_counters[1]; next_counters[2] = cur_counters[2]; ctl[2] = 0; }
+}
+
+struct VmPrune {
+  double center[3], radius, res;
+  int by_distance;         // drop voxels whose centre (c + 1) * res is further than `radius` from `center`
+  unsigned epoch, max_age;  // max_age > 0: drop voxels no insert has touched during the last max_age inserts
+};
+// One thread per bucket of the OLD table: a surviving bucket is claimed in the new keys (every key is unique: the claim is a creation),
+// its sums and stamp move, its record is recomputed at the new index and it joins the new compact list. The only pass proportional to the map.
+template <int MODE>
+__global__ __launch_bounds__(VM_FIN_THREADS) void vm_rehash_kernel(const unsigned long long* __restrict__ old_keys, const double* __restrict__ old_sums, const unsigned* __restrict__ old_stamps,
+                                                                   unsigned old_capacity, unsigned long long* __restrict__ new_keys, unsigned new_mask, double* __restrict__ new_sums,
+                                                                   unsigned* __restrict__ new_stamps, uint4* __restrict__ table, int* __restrict__ counters, int* __restrict__ occupied,
+                                                                   VmPrune prune, int* __restrict__ ctl) {
+  __shared__ int s_keep, s_drop, s_base;
+  if (threadIdx.x == 0) { s_keep = 0; s_drop = 0; }
+  __syncthreads();
+  const unsigned b = blockIdx.x * VM_FIN_THREADS + threadIdx.x;
+  unsigned long long key = FVH_EMPTY_KEY;
+  if (b < old_capacity) key = old_keys[b];
+  bool keep = key != FVH_EMPTY_KEY;
+  unsigned stamp = 0;
+  if (keep) {
+    stamp = old_stamps[b];
+    if (prune.by_distance) {
+      int cx, cy, cz;
+      unpack_key(key, cx, cy, cz);
+      const double dx = ((double)cx + 1.0) * prune.res - prune.center[0], dy = ((double)cy + 1.0) * prune.res - prune.center[1], dz = ((double)cz + 1.0) * prune.res - prune.center[2];
+      if (sqrt(dx * dx + dy * dy + dz * dz) > prune.radius) keep = false;
+    }
+    if (prune.max_age > 0u && prune.epoch - stamp >= prune.max_age) keep = false;
+    if (!keep) atomicAdd(&s_drop, 1);
+  }
+  unsigned nb = 0xFFFFFFFFu;
+  int local = 0;
+  if (keep) {
+    nb = inc_claim(new_keys, new_mask, key);
+    if (nb == 0xFFFFFFFFu) {
+      atomicAdd(counters + 1, 1);  // (cannot happen: the host sizes the new table for every bucket of the old one)
+    } else {
+      double a[VM_ACC_STRIDE];
+#pragma unroll
+      for (int j = 0; j < VM_ACC_STRIDE; j++) { a[j] = old_sums[(size_t)b * VM_ACC_STRIDE + j]; new_sums[(size_t)nb * VM_ACC_STRIDE + j] = a[j]; }
+      new_stamps[nb] = stamp;
+      inc_write_record<MODE>(key, a, table, nb);
+      local = atomicAdd(&s_keep, 1);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    s_base = s_keep ? atomicAdd(counters, s_keep) : 0;
+    if (s_drop) atomicAdd(ctl + 2, s_drop);
+  }
+  __syncthreads();
+  if (nb != 0xFFFFFFFFu) occupied[s_base + local] = (int)nb;
+}
+
 }  // namespace fvh

@@ -278,7 +278,21 @@ PYBIND11_MODULE(pygicp, m) {
       .def("prepare_next_source", [](VGICPCuda& v, const Points& p, int stages) { v.prepareNextSource(numpy2cloud(p), stages); }, py::arg("points"), py::arg("stages") = 2)
       .def("adopt_prepared_source", &VGICPCuda::adoptPreparedSource)
       .def("align_async", [](VGICPCuda& v, const Mat4& initial_guess) { v.alignAsync(numpy2mat4(initial_guess)); }, py::arg("initial_guess") = identity4())
-      .def("align_wait", [](VGICPCuda& v) { return mat4_to_numpy(v.alignWait()); });
+      .def("align_wait", [](VGICPCuda& v) { return mat4_to_numpy(v.alignWait()); })
+      // not in the reference: an incremental target map for scan-to-map loops (include/fast_vgicp_hip.h: fvh_vgicp_map_begin ...).
+      //   reg.begin_incremental_target(); reg.set_input_source(scan0); reg.insert_source_into_target(np.eye(4))
+      //   per scan: reg.set_input_source(scan); T = reg.align(guess); reg.insert_source_into_target(); reg.prune_target(T[:3, 3], radius)
+      .def("begin_incremental_target", &VGICPCuda::beginIncrementalTarget, py::arg("expected_voxels") = 0)
+      .def("insert_source_into_target", [](VGICPCuda& v, const py::object& T) {  // T = None: the final transformation of the last align
+        if (T.is_none()) v.insertSourceIntoTarget();
+        else v.insertSourceIntoTarget(numpy2mat4(T.cast<Mat4>()));
+      }, py::arg("T") = py::none())
+      .def("prune_target", [](VGICPCuda& v, const py::object& center, double radius, int max_age) {
+        if (center.is_none()) return v.pruneTarget(nullptr, radius, max_age);
+        const auto c = center.cast<py::array_t<double, py::array::c_style | py::array::forcecast>>();
+        if (c.size() != 3) throw std::invalid_argument("prune_target: center must have 3 elements");
+        return v.pruneTarget(c.data(), radius, max_age);
+      }, py::arg("center") = py::none(), py::arg("radius") = 0.0, py::arg("max_age") = 0);
 
   py::class_<GICP, Lsq, std::shared_ptr<GICP>>(m, "FastGICP")  // main.cpp:183-190
       .def(py::init([](int device) { return std::make_shared<GICP>(device); }), py::arg("device") = 0)

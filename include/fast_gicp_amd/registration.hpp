@@ -320,7 +320,7 @@ public:
 
   /// pcl::Registration::align
   void align(PointCloudSource& output, const Matrix4f& guess = Matrix4f::Identity()) {
-    if (!input_ || !target_) throw std::invalid_argument("align: source / target cloud not set");
+    if (!input_ || (!target_ && !has_device_target())) throw std::invalid_argument("align: source / target cloud not set");
     computeTransformation(output, guess);
   }
   /// pcl::Registration::getFitnessScore(max_range): mean squared exact-NN distance of T*source to the target
@@ -331,7 +331,7 @@ public:
   /// class's getters are left as the last of K align() calls leaves the device handle. 1 <= K <= 64. Classes whose device LM does not go
   /// through fvh_vgicp_align / fvh_ndt_align (FastGICP) throw.
   std::vector<MultiAlignResult> alignMulti(const std::vector<Matrix4f>& guesses) {
-    if (!input_ || !target_) throw std::invalid_argument("alignMulti: source / target cloud not set");
+    if (!input_ || (!target_ && !has_device_target())) throw std::invalid_argument("alignMulti: source / target cloud not set");
     const int k = (int)guesses.size();
     std::vector<double> g16(16 * (size_t)k);
     for (int i = 0; i < k; i++) Isometry3d::from(guesses[i]).to_colmajor16(&g16[16 * (size_t)i]);
@@ -423,6 +423,8 @@ protected:
   virtual double compute_error(const Isometry3d& trans) = 0;
   /// subclasses with a device-resident LM return true after updating x0 / converged_ / nr_iterations_ / final_hessian_
   virtual bool device_align(Isometry3d& x0) { (void)x0; return false; }
+  /// the registration target lives on the device without a host cloud behind it (FastVGICPCuda's incremental target map)
+  virtual bool has_device_target() const { return false; }
   /// alignMulti / alignBest: the subclass's fvh_*_align_multi and fvh_*_fitness_score
   virtual void device_align_multi(int k, const double* guesses16, const fvh_lm_params* p, fvh_lm_result* results, int* grid_blocks) {
     (void)k; (void)guesses16; (void)p; (void)results; (void)grid_blocks;
@@ -587,6 +589,7 @@ public:
   void setInputTarget(const PointCloudTargetConstPtr& cloud) override {  // :114-141
     if (cloud == target_) return;
     target_ = cloud;
+    incremental_target_ = false;  // (create_target_voxelmap below replaces an incremental map by the batch map of this cloud)
     const detail::XyzView<PointTarget> view(*cloud, scratch_xyz_);
     call(fvh_vgicp_set_target_cloud_strided(core_, view.data, (int)cloud->size(), view.stride), "set_target_cloud");
     switch (effective_neighbor_method(cloud->size())) {
@@ -614,6 +617,33 @@ public:
     return score;
   }
   fvh_vgicp* core() { return core_; }
+
+  // ---- incremental target map (no reference counterpart; C ABI: fvh_vgicp_map_begin / _insert_source / _prune). Scan-to-map loops:
+  //     beginIncrementalTarget(); setInputSource(scan 0); insertSourceIntoTarget(Identity);
+  //     per scan: setInputSource(scan); align(out, guess); insertSourceIntoTarget(); pruneTarget(position, radius);
+  // The map has no host cloud behind it: getInputTarget() is null, align() does not ask for one, swapSourceAndTarget() throws
+  // (FVH_ERR_BAD_STATE) and getFitnessScore() needs a target cloud as before. setInputTarget() ends the mode.
+  void beginIncrementalTarget(int expected_voxels = 0) {
+    call(fvh_vgicp_map_begin(core_, expected_voxels), "map_begin");
+    target_.reset();
+    incremental_target_ = true;
+  }
+  /// adds the current source (points + covariances as setInputSource left them) to the map at pose T
+  void insertSourceIntoTarget(const Matrix4f& T) {
+    if (!input_) throw std::invalid_argument("insertSourceIntoTarget: source cloud not set");
+    double T16[16];
+    Isometry3d::from(T).to_colmajor16(T16);
+    call(fvh_vgicp_map_insert_source(core_, T16), "map_insert_source");
+  }
+  /// ... at the final transformation of the last align()
+  void insertSourceIntoTarget() { insertSourceIntoTarget(this->final_transformation_); }
+  /// drops voxels further than `radius` from `center` (null: no distance rule) and those untouched by the last max_age inserts (<= 0: no age rule); returns the number removed
+  int pruneTarget(const double* center3, double radius, int max_age = 0) {
+    int removed = 0;
+    call(fvh_vgicp_map_prune(core_, center3, radius, max_age, &removed), "map_prune");
+    return removed;
+  }
+  bool hasIncrementalTarget() const { return incremental_target_; }
 
   // ---- scan streams as a two-stage pipeline (no reference counterpart; C ABI: fvh_vgicp_align_async / _wait, fvh_vgicp_prepare_source_device /
   // _adopt_prepared_source). kitti.cpp:95-128 with the preparation of scan k+1 hidden under the registration of scan k:
@@ -732,9 +762,11 @@ protected:
     }
     return neighbors;
   }
+  bool has_device_target() const override { return incremental_target_; }
   void call(int rc, const char* what) const { detail::check(rc, what, fvh_vgicp_last_error(core_)); }
 
 private:
+  bool incremental_target_ = false;                                                              // beginIncrementalTarget .. setInputTarget
   int k_correspondences_ = 20;                                                                   // :24
   double voxel_resolution_ = 1.0;                                                                // :25
   RegularizationMethod regularization_method_ = RegularizationMethod::PLANE;                     // :26

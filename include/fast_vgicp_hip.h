@@ -228,6 +228,50 @@ int fvh_vgicp_align_wait(fvh_vgicp* h, fvh_lm_result* result);
 int fvh_vgicp_prepare_source_device(fvh_vgicp* h, const float* d_xyz, int n, int stride_floats, int k, int regularization, int rbf, int stages);
 int fvh_vgicp_prepare_source(fvh_vgicp* h, const float* xyz, int n, int stride_floats, int k, int regularization, int rbf, int stages); /* a HOST cloud, consumed before the call returns */
 int fvh_vgicp_adopt_prepared_source(fvh_vgicp* h);
+/* new: an INCREMENTAL target voxel map (scan-to-map odometry / mapping: align scan k against a local map, add scan k at the pose found,
+ * drop what the vehicle left behind). The map keeps its per-voxel running sums, so adding a scan costs work proportional to the scan,
+ * not to the map, and no target CLOUD is needed: align, align_async / _wait, align_multi, update_correspondences, compute_error, the
+ * voxel getters and get_voxel_correspondences work on it as on a batch map.
+ *   map_begin          start (or restart) an empty incremental map at the handle's resolution and voxel accumulation mode. expected_voxels
+ *                      sizes the first table (<= 0: 16,384). Replaces whatever target map was live.
+ *   map_insert_source  add the CURRENT SOURCE (points + covariances) at pose T (4x4 double column-major, rigid). Afterwards the map is the
+ *                      map fvh_vgicp_create_target_voxelmap would build from the cloud of ALL points inserted so far, where an inserted
+ *                      point is p' = (float)(T p) and its covariance C' = (float)(R C R^T), both formed in fp64 and rounded once: same voxel
+ *                      set, same point counts exactly, means / covariances equal up to the order of the fp64 sums. MULTIPLICATIVE voxels
+ *                      accumulate C'^-1 and C'^-1 p' of those rounded values. The source's Morton order is used when it has one.
+ *   map_insert_cloud   the same for a cloud that is not the source: device or host points (stride 3 or 4 floats) + 9 doubles per point on
+ *                      the host, as fvh_vgicp_set_*_covariances.
+ *   map_prune          drop the voxels whose centre ((c + 1) * resolution per axis, fp64) is further than `radius` (Euclidean) from center3
+ *                      (NULL: no distance rule), and those no insert has touched during the last max_age inserts (<= 0: no age rule;
+ *                      1 keeps exactly what the last insert touched). A surviving voxel keeps its FULL sums. num_removed may be NULL.
+ *   map_get_info       any pointer may be NULL. num_points counts the points offered since map_begin (skipped ones included);
+ *                      num_dropped is the table-overflow counter and reads 0: capacity is secured BEFORE an insert launches, from a host-side
+ *                      upper bound of the voxel count (the table grows by a rehash when needed), so no point is ever dropped and no
+ *                      insert redone. Non-finite / out-of-range points are skipped and counted (fvh_vgicp_debug_get_skipped_points,
+ *                      cumulative since map_begin).
+ * Every insert and prune clears the stored correspondences (call update_correspondences / align again); a prune and a growing insert
+ * are the only passes proportional to the map. A large map (fvh_engine_params::bitmap_min_points) keeps a correct occupancy bitmap:
+ * new voxels inside its box set their bit, one outside switches it off until the next rehash (a prune, or an insert that grows the table)
+ * rebuilds it -- a map that is never pruned and never grows then runs without a bitmap from that insert on (correct, slower on maps that no
+ * longer fit the caches). The host keeps an upper bound of the voxel count that grows by the scan size per insert: when it says the table
+ * could pass a load factor of 0.5, the insert first reads the real count back (one stream synchronisation; in the steady state of a
+ * scan-to-map loop whose scans have more points than the map has voxels: every insert), and a prune reads its counts back as well.
+ * While an incremental map is live: fvh_vgicp_create_target_voxelmap replaces it by the batch map of the target cloud (the mode ends; a call
+ * refused because there is no target cloud / covariances leaves the incremental map as it was); fvh_vgicp_comm_init / _peer_attach are
+ * FVH_ERR_BAD_STATE (every rank would grow a private map: end the mode first);
+ * fvh_vgicp_swap_source_and_target / _gicp_swap_source_and_target are FVH_ERR_BAD_STATE (there is no cloud behind the map to become a
+ * source); a change of the resolution or between additive and multiplicative voxels is FVH_ERR_BAD_STATE (call map_begin again);
+ * fvh_vgicp_set_target_cloud* leaves the map alone (fvh_vgicp_fitness_score still needs a target cloud). With no incremental map live
+ * all of those behave as before.
+ * Refused by map_begin / map_insert_* / map_prune, the handle stays usable: multi-GPU handles (communicator, peers or tile attached) and
+ * fvh_vgicp_set_target_map_sharding (FVH_ERR_UNSUPPORTED); FVH_COMPUTE_CUDA_COMPAT (FVH_ERR_UNSUPPORTED: its voxel sums are float sums in point order, which an in-place map
+ * cannot reproduce); an align_async in flight, insert / prune without map_begin, a source without covariances (FVH_ERR_BAD_STATE); a
+ * null or non-finite T (FVH_ERR_INVALID_ARGUMENT). NDT handles have no incremental map (their maps are rebuilt per frame by design). */
+int fvh_vgicp_map_begin(fvh_vgicp* h, int expected_voxels);
+int fvh_vgicp_map_insert_source(fvh_vgicp* h, const double* T16);
+int fvh_vgicp_map_insert_cloud(fvh_vgicp* h, const float* xyz, int n, int stride_floats, const double* covs9, const double* T16, int on_device);
+int fvh_vgicp_map_prune(fvh_vgicp* h, const double* center3, double radius, int max_age, int* num_removed);
+int fvh_vgicp_map_get_info(fvh_vgicp* h, int* incremental, int* num_voxels, int* capacity, int* num_inserts, long long* num_points, int* num_dropped);
 /* setDebugPrint(true) on the device LM: with the trace on, an align records one row per trial step -- {inner iteration i, y0,
  * yi, rho, lambda, |d|}, the columns LsqRegistration prints (lsq_registration_impl.hpp:143-149) -- fetched afterwards
  * (rows6 may be NULL to query the count). */
