@@ -118,6 +118,61 @@ def _result_dict(r):
                 lm_failed=bool(r.lm_failed), num_launches=r.num_launches)
 
 
+# ---- map snapshot files (VGICPCore.map_save / map_load; FastVGICPCuda::saveTargetMap / loadTargetMap write the same bytes) ----
+# little-endian: magic "FVHVMAP\0" (8 bytes) | version u32 = 1 | mode i32 | num_inserts i32 | num_voxels i32 | num_points i64 | resolution f64
+# (40 bytes) | coords i32[n][3] | sums f64[n][10] | ages u32[n]          ("Map snapshot files")
+MAP_FILE_MAGIC = b"FVHVMAP\0"
+MAP_FILE_VERSION = 1
+_MAP_FILE_HEADER = np.dtype([("magic", "S8"), ("version", "<u4"), ("mode", "<i4"), ("num_inserts", "<i4"), ("num_voxels", "<i4"), ("num_points", "<i8"), ("resolution", "<f8")])
+
+
+def _snapshot_arrays(snapshot):
+    coords = np.ascontiguousarray(snapshot["coords"], dtype=np.int32).reshape(-1, 3)
+    sums = np.ascontiguousarray(snapshot["sums"], dtype=np.float64).reshape(-1, 10)
+    ages = snapshot.get("ages")
+    ages = np.zeros(len(coords), np.uint32) if ages is None else np.ascontiguousarray(ages, dtype=np.uint32).reshape(-1)
+    if not (len(coords) == len(sums) == len(ages)):
+        raise FvhError("map snapshot: coords, sums and ages differ in length (%d, %d, %d)" % (len(coords), len(sums), len(ages)))
+    return coords, sums, ages
+
+
+def write_map_file(path, snapshot):
+    """Write a snapshot (the dict VGICPCore.map_export returns) to `path`. Needs no GPU."""
+    coords, sums, ages = _snapshot_arrays(snapshot)
+    hdr = np.zeros(1, _MAP_FILE_HEADER)
+    hdr["magic"], hdr["version"], hdr["mode"], hdr["num_inserts"] = MAP_FILE_MAGIC, MAP_FILE_VERSION, int(snapshot["mode"]), int(snapshot["num_inserts"])
+    hdr["num_voxels"], hdr["num_points"], hdr["resolution"] = len(coords), int(snapshot["num_points"]), float(snapshot["resolution"])
+    with open(path, "wb") as f:
+        f.write(hdr.tobytes())
+        f.write(coords.astype("<i4", copy=False).tobytes())
+        f.write(sums.astype("<f8", copy=False).tobytes())
+        f.write(ages.astype("<u4", copy=False).tobytes())
+
+
+def read_map_file(path):
+    """-> the snapshot dict of write_map_file's file; FvhError for a file that is not one (magic, version, size). Needs no GPU."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    hs = _MAP_FILE_HEADER.itemsize
+    if len(raw) < hs:
+        raise FvhError("%s: not a map snapshot (shorter than the header)" % path)
+    # (magic compared on the raw bytes: numpy strips an S8's trailing NUL)
+    if raw[:8] != MAP_FILE_MAGIC:
+        raise FvhError("%s: not a map snapshot (magic)" % path)
+    hdr = np.frombuffer(raw, _MAP_FILE_HEADER, count=1)[0]
+    if int(hdr["version"]) != MAP_FILE_VERSION:
+        raise FvhError("%s: map snapshot version %d, this build reads %d" % (path, int(hdr["version"]), MAP_FILE_VERSION))
+    n = int(hdr["num_voxels"])
+    if n < 0 or len(raw) != hs + n * (12 + 80 + 4):
+        raise FvhError("%s: map snapshot truncated or corrupt (%d voxels need %d bytes, file has %d)" % (path, n, hs + max(n, 0) * 96, len(raw)))
+    o = hs
+    coords = np.frombuffer(raw, "<i4", 3 * n, o).reshape(n, 3).astype(np.int32); o += 12 * n
+    sums = np.frombuffer(raw, "<f8", 10 * n, o).reshape(n, 10).astype(np.float64); o += 80 * n
+    ages = np.frombuffer(raw, "<u4", n, o).astype(np.uint32)
+    return dict(resolution=float(hdr["resolution"]), mode=int(hdr["mode"]), num_inserts=int(hdr["num_inserts"]), num_points=int(hdr["num_points"]), num_voxels=n,
+                coords=coords, sums=sums, ages=ages)
+
+
 class _Core:
     _prefix = ""
 
@@ -492,6 +547,43 @@ class VGICPCore(_Core):
         npts = C.c_longlong(0)
         self._call("map_get_info", C.byref(inc), C.byref(nv), C.byref(cap), C.byref(ni), C.byref(npts), C.byref(dr))
         return dict(incremental=bool(inc.value), num_voxels=nv.value, capacity=cap.value, num_inserts=ni.value, num_points=npts.value, dropped=dr.value)
+
+    # ---- snapshots of the incremental map (fvh_vgicp_voxelmap_export / _import / _merge_from) ----
+    def map_export(self):
+        """The live incremental map as a snapshot: header fields + coords (n, 3) int32, sums (n, 10) float64 (the device's own per-voxel sums)
+        and ages (n,) uint32, rows in ascending packed-key order (z-major, then y, then x)."""
+        nv, mode, ni = C.c_int(0), C.c_int(0), C.c_int(0)
+        res, npts = C.c_double(0.0), C.c_longlong(0)
+        self._call("voxelmap_export", C.byref(nv), C.byref(res), C.byref(mode), C.byref(ni), C.byref(npts), None, None, None)
+        n = nv.value
+        coords, sums, ages = np.empty((n, 3), np.int32), np.empty((n, 10), np.float64), np.empty(n, np.uint32)
+        if n:
+            self._call("voxelmap_export", C.byref(nv), C.byref(res), C.byref(mode), C.byref(ni), C.byref(npts), _p(coords), _p(sums), _p(ages))
+        return dict(resolution=res.value, mode=mode.value, num_inserts=ni.value, num_points=npts.value, num_voxels=n, coords=coords, sums=sums, ages=ages)
+
+    def map_import(self, snapshot):
+        """ADD a snapshot's voxels into the live map (restore: map_begin() first): sums and counts add, ages and the insert count carry over."""
+        coords, sums, ages = _snapshot_arrays(snapshot)
+        n = len(coords)
+        self._call("voxelmap_import", n, _p(coords) if n else None, _p(sums) if n else None, _p(ages) if n else None, C.c_double(snapshot["resolution"]), int(snapshot["mode"]),
+                   int(snapshot["num_inserts"]), C.c_longlong(int(snapshot["num_points"])))
+
+    def map_merge_from(self, other):
+        """ADD the live map of `other` (a VGICPCore on the same device, same resolution and mode) into this one, device to device; `other` is unchanged."""
+        self._call("voxelmap_merge_from", other.h)
+
+    def map_save(self, path):
+        write_map_file(path, self.map_export())
+
+    def map_load(self, path):
+        """Add the file's map into the live map; a handle with no live map takes the file's resolution and mode and starts one sized for it."""
+        snap = read_map_file(path)
+        if not self.map_info()["incremental"]:
+            self.set_resolution(snap["resolution"])
+            self.set_voxel_accumulation_mode(VOXEL_MULTIPLICATIVE if snap["mode"] == 2 else VOXEL_ADDITIVE)
+            self.map_begin(max(snap["num_voxels"], 1))
+        self.map_import(snap)
+        return snap
 
     def get_voxelmap(self):
         n = C.c_int(0)

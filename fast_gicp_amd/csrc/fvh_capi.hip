@@ -487,6 +487,7 @@ struct fvh_vgicp {
   // Incremental target map (fvh_vgicp_map_*, host_incmap.inc.hpp): `voxelmap` keeps its sums and grows in place; there is no cloud behind it
   bool incremental() const { return voxelmap.inc.live && voxelmap.valid; }
   CloudDev insert_cloud;     // staging of fvh_vgicp_map_insert_cloud
+  hipEvent_t merge_ev[2] = {nullptr, nullptr};  // fvh_vgicp_voxelmap_merge_from: the other handle's stream -> ours before the kernel, ours -> its stream after it
   // the target cloud was replaced: the batch map built from the old one is dead; an incremental map never depended on it
   void target_replaced() { e.has_corr = false; if (!incremental()) voxelmap.invalidate(); gicp_records.invalidate(); }
   int build_map(double res, bool force_safe = false, hipStream_t on_side = nullptr, bool shard = false) {
@@ -624,6 +625,7 @@ int fvh_vgicp_destroy(fvh_vgicp* h) {
   if (h->pending.active) { h->pending.release_slots(); h->pending.active = false; }
   h->source.release(); h->target.release(); h->voxelmap.release(); h->gicp_records.release(); h->next_source.release(); h->next_map.release(); h->source_map.release(); h->insert_cloud.release();
   if (h->prep_done) (void)hipEventDestroy(h->prep_done);
+  for (hipEvent_t ev : h->merge_ev) if (ev) (void)hipEventDestroy(ev);
   h->e.shutdown();
   delete h;
   return FVH_OK;
@@ -699,6 +701,30 @@ int fvh_vgicp_map_get_info(fvh_vgicp* h, int* incremental, int* num_voxels, int*
   if (num_voxels) *num_voxels = cnt[0];
   if (num_dropped) *num_dropped = cnt[1];
   return FVH_OK;
+}
+// ---- snapshots of the incremental map: save / restore / merge (host_incmap.inc.hpp: "snapshots") ----
+int fvh_vgicp_voxelmap_export(fvh_vgicp* h, int* num_voxels, double* resolution, int* mode, int* num_inserts, long long* num_points, int* coords3, double* sums10, unsigned* ages) {
+  CHECK_HANDLE(h);
+  { const int rc = map_refusal(h, "voxelmap_export"); if (rc) return rc; }
+  return incmap_export(&h->e, h->voxelmap, num_voxels, resolution, mode, num_inserts, num_points, coords3, sums10, ages);
+}
+int fvh_vgicp_voxelmap_import(fvh_vgicp* h, int n, const int* coords3, const double* sums10, const unsigned* ages, double resolution, int mode, int num_inserts, long long num_points) {
+  CHECK_HANDLE(h);
+  { const int rc = map_refusal(h, "voxelmap_import"); if (rc) return rc; }
+  return incmap_import(&h->e, h->voxelmap, n, coords3, sums10, ages, resolution, mode, num_inserts, num_points);
+}
+int fvh_vgicp_voxelmap_merge_from(fvh_vgicp* h, fvh_vgicp* other) {
+  CHECK_HANDLE(h);
+  { const int rc = map_refusal(h, "voxelmap_merge_from"); if (rc) return rc; }
+  if (!other) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_merge_from: null other handle");
+  if (other == h) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_merge_from: a map cannot be merged into itself");
+  if (other->e.device != h->e.device) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_merge_from: the two handles are on different devices");
+  if (other->e.sharded() || other->shard_map || other->e.precision == FVH_COMPUTE_CUDA_COMPAT) return h->e.fail(FVH_ERR_UNSUPPORTED, "voxelmap_merge_from: the other handle is a multi-GPU / sharded / FVH_COMPUTE_CUDA_COMPAT handle");
+  if (other->e.async_in_flight) return h->e.fail(FVH_ERR_BAD_STATE, "voxelmap_merge_from: an align_async is in flight on the other handle: call fvh_vgicp_align_wait first");
+  { const int rc = other->e.settle(); if (rc) return h->e.fail(rc, "voxelmap_merge_from: the other handle: " + other->e.err); }
+  for (hipEvent_t& ev : h->merge_ev) if (!ev) HIP_OR_FAIL(&h->e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  other->e.quiet = false;  // (its stream now holds a wait)
+  return incmap_merge_from(&h->e, h->voxelmap, other->voxelmap, other->e.stream, h->merge_ev[0], h->merge_ev[1]);
 }
 int fvh_vgicp_set_voxel_accumulation_mode(fvh_vgicp* h, int mode) {
   CHECK_HANDLE(h);

@@ -201,3 +201,175 @@ int incmap_prune(Engine* e, VoxelMapDev& vm, const double* center3, double radiu
   if (num_removed) *num_removed = ctl[2];
   return FVH_OK;
 }
+
+// ---- snapshots of the live map (fvh_vgicp_voxelmap_export / _import / _merge_from; kernels_voxelmap.hpp: "snapshots") ------------------
+// A snapshot is the header {resolution, mode, num_inserts = epoch, num_points, num_voxels} and per voxel {coords[3], sums[10], age}, rows
+// in ascending packed-key order. Rows ADD into a live map of the same grid: import (host rows) and merge_from (another handle's map, read
+// in place) are one kernel + the insert's refresh.
+
+inline unsigned long long host_pack_key(int x, int y, int z) {
+  return (unsigned long long)(unsigned)(x + FVH_COORD_BIAS) | ((unsigned long long)(unsigned)(y + FVH_COORD_BIAS) << 21) | ((unsigned long long)(unsigned)(z + FVH_COORD_BIAS) << 42);
+}
+
+// room for `n` more voxels, secured BEFORE a launch as incmap_insert does it: host bound + n, a readback only when the bound asks for one,
+// growth by a rehash. Queues nothing that changes what the map holds.
+int incmap_secure(Engine* e, VoxelMapDev& vm, long long n, const char* who) {
+  if (vm.inc.voxel_bound + n > INCMAP_MAX_VOXELS || 2 * (vm.inc.voxel_bound + n) > (long long)vm.capacity) {
+    int cnt[3];
+    { int rc = incmap_read_counts(e, vm, cnt, nullptr); if (rc) return rc; }
+    vm.inc.voxel_bound = cnt[0];
+    if (vm.inc.voxel_bound + n > INCMAP_MAX_VOXELS) return e->fail(FVH_ERR_UNSUPPORTED, std::string(who) + ": the map would exceed 2^28 voxels");
+    if (2 * (vm.inc.voxel_bound + n) > (long long)vm.capacity) {
+      int rc = incmap_rehash(e, vm, incmap_capacity_for(vm.inc.voxel_bound + n), incmap_no_prune(vm));
+      if (rc) return rc;
+    }
+  }
+  return FVH_OK;
+}
+
+int incmap_export(Engine* e, VoxelMapDev& vm, int* num_voxels, double* resolution, int* mode, int* num_inserts, long long* num_points, int* coords3, double* sums10, unsigned* ages) {
+  if (!vm.inc.live || !vm.valid) return e->fail(FVH_ERR_BAD_STATE, "voxelmap_export: no incremental map is live (fvh_vgicp_map_begin)");
+  const bool rows = coords3 || sums10 || ages;
+  if (rows && !(coords3 && sums10 && ages)) return e->fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_export: coords3, sums10 and ages go together (all NULL: the header only)");
+  int cnt[3];
+  { int rc = incmap_read_counts(e, vm, cnt, nullptr); if (rc) return rc; }
+  vm.inc.voxel_bound = cnt[0];
+  const int n = cnt[0];
+  if (num_voxels) *num_voxels = n;
+  if (resolution) *resolution = vm.res;
+  if (mode) *mode = vm.inc.mode;
+  if (num_inserts) *num_inserts = (int)vm.inc.epoch;
+  if (num_points) *num_points = vm.inc.num_points;
+  if (!rows || n == 0) return FVH_OK;
+  const size_t sums_bytes = sizeof(double) * VM_ACC_STRIDE * (size_t)n, coords_bytes = sizeof(int) * 3 * (size_t)n, ages_bytes = sizeof(unsigned) * (size_t)n;
+  HIP_OR_FAIL(e, vm.inc.xfer.ensure(sums_bytes + coords_bytes + ages_bytes));
+  double* d_sums = vm.inc.xfer.as<double>();
+  int* d_coords = reinterpret_cast<int*>(static_cast<char*>(vm.inc.xfer.p) + sums_bytes);
+  unsigned* d_ages = reinterpret_cast<unsigned*>(static_cast<char*>(vm.inc.xfer.p) + sums_bytes + coords_bytes);
+  {
+    ProfScope ps(e, "map_export");
+    vm_export_kernel<<<(n + VM_SNAP_THREADS - 1) / VM_SNAP_THREADS, VM_SNAP_THREADS, 0, e->stream>>>(vm.keys_cur(), vm.inc.sums[vm.cur].as<double>(), vm.inc.stamps[vm.cur].as<unsigned>(), vm.occupied.as<int>(),
+                                                                                                      vm.counters_cur(), vm.inc.epoch, n, d_coords, d_sums, d_ages);
+  }
+  HIP_OR_FAIL(e, hipGetLastError());
+  // the rows arrive in the order of the compact list; the contract's order -- ascending packed key -- is made here, on the host
+  std::vector<double> h_sums((size_t)n * VM_ACC_STRIDE);
+  std::vector<int> h_coords((size_t)n * 3);
+  std::vector<unsigned> h_ages((size_t)n);
+  {
+    ProfScope ps(e, "map_export_copy");
+    HIP_OR_FAIL(e, hipMemcpyAsync(h_sums.data(), d_sums, sums_bytes, hipMemcpyDeviceToHost, e->stream));
+    HIP_OR_FAIL(e, hipMemcpyAsync(h_coords.data(), d_coords, coords_bytes, hipMemcpyDeviceToHost, e->stream));
+    HIP_OR_FAIL(e, hipMemcpyAsync(h_ages.data(), d_ages, ages_bytes, hipMemcpyDeviceToHost, e->stream));
+  }
+  HIP_OR_FAIL(e, hipStreamSynchronize(e->stream));
+  std::vector<std::pair<unsigned long long, int>> order((size_t)n);
+  for (int i = 0; i < n; i++) order[i] = {host_pack_key(h_coords[3 * (size_t)i], h_coords[3 * (size_t)i + 1], h_coords[3 * (size_t)i + 2]), i};
+  std::sort(order.begin(), order.end());
+  for (int r = 0; r < n; r++) {
+    const size_t i = (size_t)order[r].second;
+    std::memcpy(coords3 + 3 * (size_t)r, &h_coords[3 * i], 3 * sizeof(int));
+    std::memcpy(sums10 + VM_ACC_STRIDE * (size_t)r, &h_sums[VM_ACC_STRIDE * i], VM_ACC_STRIDE * sizeof(double));
+    ages[r] = h_ages[i];
+  }
+  return FVH_OK;
+}
+
+// what import and merge_from share once the rows are on the device: the new epoch, the launch, the insert's refresh and bookkeeping
+template <bool FROM_MAP>
+int incmap_add_rows(Engine* e, VoxelMapDev& vm, int n_rows, const int* d_coords, const double* d_sums, const unsigned* d_ages, const VoxelMapDev* from, unsigned in_epoch, long long in_points,
+                    const char* prof_class) {
+  vm.inc.epoch = std::max(vm.inc.epoch, in_epoch);
+  vm.inc.num_points += in_points;
+  vm.host_valid = false;
+  vm.has_canon = false;
+  e->has_corr = false;
+  if (n_rows == 0) return FVH_OK;
+  HIP_OR_FAIL(e, vm.inc.dirty.ensure(sizeof(unsigned) * (size_t)n_rows));
+  HIP_OR_FAIL(e, hipMemsetAsync(vm.inc.ctl.p, 0, sizeof(int), e->stream));  // the dirty count
+  unsigned long long* keys = vm.keys[vm.cur].as<unsigned long long>();
+  double* sums = vm.inc.sums[vm.cur].as<double>();
+  unsigned* stamps = vm.inc.stamps[vm.cur].as<unsigned>();
+  int* counters = vm.counters_cur();
+  int* ctl = vm.inc.ctl.as<int>();
+  unsigned* dirty = vm.inc.dirty.as<unsigned>();
+  VmGrid* grid = vm.has_bitmap ? vm.grid.as<VmGrid>() : nullptr;
+  unsigned long long* bitmap = vm.has_bitmap ? vm.bitmap.as<unsigned long long>() : nullptr;
+  const int blocks = (n_rows + VM_SNAP_THREADS - 1) / VM_SNAP_THREADS;
+  {
+    ProfScope ps(e, prof_class);
+    vm_import_kernel<FROM_MAP><<<blocks, VM_SNAP_THREADS, 0, e->stream>>>(d_coords, d_sums, d_ages, n_rows, from ? from->keys_cur() : nullptr, from ? from->occupied.as<int>() : nullptr,
+                                                                           from ? from->counters_cur() : nullptr, from ? from->inc.stamps[from->cur].as<unsigned>() : nullptr, in_epoch,
+                                                                           keys, vm.capacity - 1, sums, stamps, vm.inc.epoch, dirty, ctl, counters + 1);
+    if (vm.inc.mode == 2) vm_refresh_kernel<2><<<(n_rows + 255) / 256, 256, 0, e->stream>>>(dirty, ctl, keys, sums, vm.table.as<uint4>(), counters, vm.occupied.as<int>(), grid, bitmap);
+    else vm_refresh_kernel<0><<<(n_rows + 255) / 256, 256, 0, e->stream>>>(dirty, ctl, keys, sums, vm.table.as<uint4>(), counters, vm.occupied.as<int>(), grid, bitmap);
+  }
+  HIP_OR_FAIL(e, hipGetLastError());
+  vm.inc.voxel_bound += n_rows;
+  if (!vm.has_bitmap) return incmap_bitmap(e, vm);  // (as an insert: a map that has grown into bitmap territory gets its bitmap here)
+  return FVH_OK;
+}
+
+int incmap_import(Engine* e, VoxelMapDev& vm, int n, const int* coords3, const double* sums10, const unsigned* ages, double resolution, int mode, int num_inserts, long long num_points) {
+  if (!vm.inc.live || !vm.valid) return e->fail(FVH_ERR_BAD_STATE, "voxelmap_import: no incremental map is live (fvh_vgicp_map_begin)");
+  // everything is validated on the host before anything is queued: a refused import leaves the map as it was
+  if (n < 0) return e->fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_import: n < 0");
+  if ((long long)n > INCMAP_MAX_VOXELS) return e->fail(FVH_ERR_UNSUPPORTED, "voxelmap_import: more than 2^28 voxels");
+  if (n > 0 && (!coords3 || !sums10)) return e->fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_import: null coords3 / sums10 with n > 0");
+  if (!(resolution == vm.res)) return e->fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_import: the snapshot's resolution is not the live map's");
+  if (mode != vm.inc.mode) return e->fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_import: the snapshot's accumulation mode is not the live map's");
+  if (num_inserts < 0 || num_points < 0) return e->fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_import: negative num_inserts / num_points");
+  const int lim = FVH_COORD_BIAS - 4096;  // the range voxel_index_ok gives an inserted point
+  for (int i = 0; i < n; i++) {
+    const int* c = coords3 + 3 * (size_t)i;
+    const double* s = sums10 + VM_ACC_STRIDE * (size_t)i;
+    for (int a = 0; a < 3; a++)
+      if (c[a] <= -lim || c[a] >= lim) return e->fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_import: voxel " + std::to_string(i) + ": coordinate out of range (|c| < 2^20 - 4096)");
+    for (int j = 0; j < VM_ACC_STRIDE; j++)
+      if (!std::isfinite(s[j])) return e->fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_import: voxel " + std::to_string(i) + ": a sum is not finite");
+    if (!(s[9] >= 1.0) || s[9] != std::floor(s[9]) || s[9] > 2147483647.0) return e->fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_import: voxel " + std::to_string(i) + ": the count is not an integer >= 1");
+    if ((ages ? ages[i] : 0u) >= (unsigned)num_inserts) return e->fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_import: voxel " + std::to_string(i) + ": age >= num_inserts");
+  }
+  { int rc = incmap_secure(e, vm, n, "voxelmap_import"); if (rc) return rc; }
+  const size_t sums_bytes = sizeof(double) * VM_ACC_STRIDE * (size_t)n, coords_bytes = sizeof(int) * 3 * (size_t)n, ages_bytes = sizeof(unsigned) * (size_t)n;
+  double* d_sums = nullptr;
+  int* d_coords = nullptr;
+  unsigned* d_ages = nullptr;
+  if (n > 0) {
+    HIP_OR_FAIL(e, vm.inc.xfer.ensure(sums_bytes + coords_bytes + ages_bytes));
+    d_sums = vm.inc.xfer.as<double>();
+    d_coords = reinterpret_cast<int*>(static_cast<char*>(vm.inc.xfer.p) + sums_bytes);
+    HIP_OR_FAIL(e, hipMemcpyAsync(d_sums, sums10, sums_bytes, hipMemcpyHostToDevice, e->stream));
+    HIP_OR_FAIL(e, hipMemcpyAsync(d_coords, coords3, coords_bytes, hipMemcpyHostToDevice, e->stream));
+    if (ages) {
+      d_ages = reinterpret_cast<unsigned*>(static_cast<char*>(vm.inc.xfer.p) + sums_bytes + coords_bytes);
+      HIP_OR_FAIL(e, hipMemcpyAsync(d_ages, ages, ages_bytes, hipMemcpyHostToDevice, e->stream));
+    }
+    HIP_OR_FAIL(e, hipStreamSynchronize(e->stream));  // the caller's arrays are free again when the call returns
+  }
+  return incmap_add_rows<false>(e, vm, n, d_coords, d_sums, d_ages, nullptr, (unsigned)num_inserts, num_points, "map_import");
+}
+
+// `from` (a live map of another handle on the same device, stream from_stream) added into `vm`, device to device. The reads of `from` are
+// fenced on both sides: e's stream waits for what from_stream holds, and from_stream waits for the kernel.
+int incmap_merge_from(Engine* e, VoxelMapDev& vm, VoxelMapDev& from, hipStream_t from_stream, hipEvent_t ev_before, hipEvent_t ev_after) {
+  if (!vm.inc.live || !vm.valid) return e->fail(FVH_ERR_BAD_STATE, "voxelmap_merge_from: no incremental map is live (fvh_vgicp_map_begin)");
+  if (!from.inc.live || !from.valid) return e->fail(FVH_ERR_BAD_STATE, "voxelmap_merge_from: the other handle has no live incremental map (fvh_vgicp_map_begin)");
+  if (!(from.res == vm.res)) return e->fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_merge_from: the two maps differ in resolution");
+  if (from.inc.mode != vm.inc.mode) return e->fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_merge_from: the two maps differ in accumulation mode");
+  HIP_OR_FAIL(e, hipEventRecord(ev_before, from_stream));
+  HIP_OR_FAIL(e, hipStreamWaitEvent(e->stream, ev_before, 0));
+  // the other map's voxel count stays on the device: its host bound sizes the launch, a readback refines it only when it would force a growth
+  long long n_bound = from.inc.voxel_bound;
+  if (vm.inc.voxel_bound + n_bound > INCMAP_MAX_VOXELS || 2 * (vm.inc.voxel_bound + n_bound) > (long long)vm.capacity) {
+    int cnt[3];
+    HIP_OR_FAIL(e, hipMemcpyAsync(cnt, from.counters_cur(), 3 * sizeof(int), hipMemcpyDeviceToHost, e->stream));  // (e's stream: ordered after from_stream by the event)
+    HIP_OR_FAIL(e, hipStreamSynchronize(e->stream));
+    from.inc.voxel_bound = n_bound = cnt[0];
+  }
+  { int rc = incmap_secure(e, vm, n_bound, "voxelmap_merge_from"); if (rc) return rc; }
+  const int rc = incmap_add_rows<true>(e, vm, (int)n_bound, nullptr, from.inc.sums[from.cur].as<double>(), nullptr, &from, from.inc.epoch, from.inc.num_points, "map_merge");
+  HIP_OR_FAIL(e, hipEventRecord(ev_after, e->stream));
+  HIP_OR_FAIL(e, hipStreamWaitEvent(from_stream, ev_after, 0));
+  return rc;
+}

@@ -695,4 +695,98 @@ __global__ __launch_bounds__(VM_FIN_THREADS) void vm_rehash_kernel(const unsigne
   if (nb != 0xFFFFFFFFu) occupied[s_base + local] = (int)nb;
 }
 
+// ---- snapshots of an incremental map (fvh_vgicp_voxelmap_export / _import / _merge_from: host_incmap.inc.hpp) --------------------
+// A snapshot row is {coords[3], sums[10], age = epoch - stamp}. Both additive and multiplicative voxels are pure sums, so rows ADD into a
+// live map on the same grid: vm_import_kernel (one thread per incoming row: claim, stamp) -> the existing vm_refresh_kernel (records,
+// compact list, bitmap). The kernel needs no MODE: only the refresh turns sums into a record.
+// The ten sums of a row are 80 contiguous bytes. A thread per row would give every wave instruction 64 segments of 8 bytes, 80 bytes
+// apart -- the one-lane-per-row shape memory-side atomics are slowest at -- so the sums move in a second phase: the workgroup's 256 rows
+// are 2,560 values, value e belongs to row e / 10, and ten neighbouring lanes cover one row's 80 bytes (the dense side is fully coalesced).
+constexpr int VM_SNAP_THREADS = 256;
+
+// FROM_MAP false: rows i < n_rows of a host snapshot (in_coords, in_sums, in_ages; in_ages may be null = all 0).
+// FROM_MAP true : the compact list of ANOTHER live map, read in place: src_occupied[i < src_counters[0]] names the bucket whose key, sums
+//                 (in_sums = that map's sums) and stamp are row i; age = src_epoch - stamp.
+// A row's bucket is claimed (found or created), its stamp becomes max(old, epoch - age) -- never 0: the host refuses age >= epoch -- and
+// the bucket joins the dirty list, marked new when the old stamp was 0. A key listed twice is listed twice in `dirty` (room: one entry
+// per row), marked new once: the refresh then writes its record twice, from the same finished sums.
+// With unique keys every sum receives exactly one add: old + incoming, to the bit.
+template <bool FROM_MAP>
+__global__ __launch_bounds__(VM_SNAP_THREADS) void vm_import_kernel(const int* __restrict__ in_coords, const double* __restrict__ in_sums, const unsigned* __restrict__ in_ages, int n_rows,
+                                                                    const unsigned long long* __restrict__ src_keys, const int* __restrict__ src_occupied, const int* __restrict__ src_counters,
+                                                                    const unsigned* __restrict__ src_stamps, unsigned src_epoch,
+                                                                    unsigned long long* __restrict__ table_keys, unsigned mask, double* __restrict__ sums, unsigned* __restrict__ stamps,
+                                                                    unsigned epoch, unsigned* __restrict__ dirty, int* __restrict__ ctl, int* __restrict__ dropped) {
+  __shared__ unsigned s_dst[VM_SNAP_THREADS], s_src[VM_SNAP_THREADS];
+  __shared__ int s_cnt, s_base;
+  const int tid = threadIdx.x;
+  if (tid == 0) s_cnt = 0;
+  __syncthreads();
+  const int n = FROM_MAP ? min(src_counters[0], n_rows) : n_rows;  // (n_rows: what the host sized `dirty` and the grid for)
+  const int base = blockIdx.x * VM_SNAP_THREADS;
+  const int i = base + tid;
+  unsigned b = 0xFFFFFFFFu, sb = 0u, entry = 0u;
+  int local = -1;
+  if (i < n) {
+    unsigned long long key;
+    unsigned age;
+    if (FROM_MAP) {
+      sb = (unsigned)src_occupied[i];
+      key = src_keys[sb];
+      age = src_epoch - src_stamps[sb];
+    } else {
+      sb = (unsigned)i;
+      key = pack_key(in_coords[3 * (size_t)i], in_coords[3 * (size_t)i + 1], in_coords[3 * (size_t)i + 2]);
+      age = in_ages ? in_ages[i] : 0u;
+    }
+    b = inc_claim(table_keys, mask, key);
+    if (b != 0xFFFFFFFFu) {
+      const unsigned was = atomicMax(stamps + b, epoch - age);
+      entry = b | (was == 0u ? VM_INC_NEW : 0u);
+      local = atomicAdd(&s_cnt, 1);
+    } else {
+      atomicAdd(dropped, 1);  // (cannot happen: the host secures a load factor <= 0.5 before the launch)
+    }
+  }
+  s_dst[tid] = b;
+  s_src[tid] = sb;
+  __syncthreads();
+  if (tid == 0) s_base = s_cnt ? atomicAdd(ctl, s_cnt) : 0;
+  const int rows = min(VM_SNAP_THREADS, n - base);
+  for (int e = tid; e < rows * VM_ACC_STRIDE; e += VM_SNAP_THREADS) {
+    const int v = e / VM_ACC_STRIDE, j = e - v * VM_ACC_STRIDE;
+    const unsigned db = s_dst[v];
+    if (db == 0xFFFFFFFFu) continue;
+    atomicAdd(&sums[(size_t)db * VM_ACC_STRIDE + j], in_sums[(size_t)s_src[v] * VM_ACC_STRIDE + j]);
+  }
+  __syncthreads();
+  if (local >= 0) dirty[s_base + local] = entry;
+}
+
+// The compact list gathered into three dense arrays (rows in list order; the host sorts them by key): coords from the key, the ten sums,
+// age = epoch - stamp. n_rows: the voxel count the host read and sized the arrays for.
+__global__ __launch_bounds__(VM_SNAP_THREADS) void vm_export_kernel(const unsigned long long* __restrict__ keys, const double* __restrict__ sums, const unsigned* __restrict__ stamps,
+                                                                    const int* __restrict__ occupied, const int* __restrict__ counters, unsigned epoch, int n_rows,
+                                                                    int* __restrict__ out_coords, double* __restrict__ out_sums, unsigned* __restrict__ out_ages) {
+  __shared__ unsigned s_src[VM_SNAP_THREADS];
+  const int tid = threadIdx.x;
+  const int n = min(counters[0], n_rows);
+  const int base = blockIdx.x * VM_SNAP_THREADS;
+  const int i = base + tid;
+  if (i < n) {
+    const unsigned b = (unsigned)occupied[i];
+    int cx, cy, cz;
+    unpack_key(keys[b], cx, cy, cz);
+    out_coords[3 * (size_t)i] = cx; out_coords[3 * (size_t)i + 1] = cy; out_coords[3 * (size_t)i + 2] = cz;
+    out_ages[i] = epoch - stamps[b];
+    s_src[tid] = b;
+  }
+  __syncthreads();
+  const int rows = min(VM_SNAP_THREADS, n - base);
+  for (int e = tid; e < rows * VM_ACC_STRIDE; e += VM_SNAP_THREADS) {
+    const int v = e / VM_ACC_STRIDE, j = e - v * VM_ACC_STRIDE;
+    out_sums[(size_t)base * VM_ACC_STRIDE + e] = sums[(size_t)s_src[v] * VM_ACC_STRIDE + j];
+  }
+}
+
 }  // namespace fvh

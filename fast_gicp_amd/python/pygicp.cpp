@@ -292,7 +292,43 @@ PYBIND11_MODULE(pygicp, m) {
         const auto c = center.cast<py::array_t<double, py::array::c_style | py::array::forcecast>>();
         if (c.size() != 3) throw std::invalid_argument("prune_target: center must have 3 elements");
         return v.pruneTarget(c.data(), radius, max_age);
-      }, py::arg("center") = py::none(), py::arg("radius") = 0.0, py::arg("max_age") = 0);
+      }, py::arg("center") = py::none(), py::arg("radius") = 0.0, py::arg("max_age") = 0)
+      // snapshots of the incremental target: save / restore / merge (fvh_vgicp_voxelmap_export / _import / _merge_from). The dict is
+      // {resolution, mode, num_inserts, num_points, num_voxels, coords (n, 3) int32, sums (n, 10) float64, ages (n,) uint32}
+      .def("export_target_map", [](VGICPCuda& v) {
+        const fast_gicp::TargetMapSnapshot m = v.exportTargetMap();
+        const py::ssize_t n = (py::ssize_t)m.ages.size();
+        py::array_t<int> coords({n, (py::ssize_t)3});
+        py::array_t<double> sums({n, (py::ssize_t)10});
+        py::array_t<unsigned> ages(n);
+        if (n) {
+          std::memcpy(coords.mutable_data(), m.coords.data(), sizeof(int) * m.coords.size());
+          std::memcpy(sums.mutable_data(), m.sums.data(), sizeof(double) * m.sums.size());
+          std::memcpy(ages.mutable_data(), m.ages.data(), sizeof(unsigned) * m.ages.size());
+        }
+        py::dict d;
+        d["resolution"] = m.resolution; d["mode"] = m.mode; d["num_inserts"] = m.num_inserts; d["num_points"] = m.num_points; d["num_voxels"] = (int)n;
+        d["coords"] = coords; d["sums"] = sums; d["ages"] = ages;
+        return d;
+      })
+      .def("import_target_map", [](VGICPCuda& v, const py::dict& d) {
+        fast_gicp::TargetMapSnapshot m;
+        m.resolution = d["resolution"].cast<double>(); m.mode = d["mode"].cast<int>(); m.num_inserts = d["num_inserts"].cast<int>(); m.num_points = d["num_points"].cast<long long>();
+        const auto coords = d["coords"].cast<py::array_t<int, py::array::c_style | py::array::forcecast>>();
+        const auto sums = d["sums"].cast<py::array_t<double, py::array::c_style | py::array::forcecast>>();
+        m.coords.assign(coords.data(), coords.data() + coords.size());
+        m.sums.assign(sums.data(), sums.data() + sums.size());
+        if (d.contains("ages") && !d["ages"].is_none()) {
+          const auto ages = d["ages"].cast<py::array_t<unsigned, py::array::c_style | py::array::forcecast>>();
+          m.ages.assign(ages.data(), ages.data() + ages.size());
+        } else {
+          m.ages.assign(m.coords.size() / 3, 0u);
+        }
+        v.importTargetMap(m);
+      }, py::arg("snapshot"))
+      .def("merge_target_from", &VGICPCuda::mergeTargetFrom, py::arg("other"))
+      .def("save_target_map", &VGICPCuda::saveTargetMap, py::arg("path"))
+      .def("load_target_map", &VGICPCuda::loadTargetMap, py::arg("path"));
 
   py::class_<GICP, Lsq, std::shared_ptr<GICP>>(m, "FastGICP")  // main.cpp:183-190
       .def(py::init([](int device) { return std::make_shared<GICP>(device); }), py::arg("device") = 0)

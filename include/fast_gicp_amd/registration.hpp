@@ -19,6 +19,7 @@
 #if defined(__SSE2__)
 #include <immintrin.h>
 #endif
+#include <algorithm>
 #include <array>
 #include <chrono>
 #include <cmath>
@@ -513,6 +514,79 @@ inline void check(int rc, const char* what, const char* err) {
 }
 }  // namespace detail
 
+/// A snapshot of FastVGICPCuda's incremental target map (exportTargetMap / importTargetMap; C ABI: fvh_vgicp_voxelmap_export / _import):
+/// per voxel coords[3], the device's ten fp64 sums and an age, rows in ascending packed-key order (z-major, then y, then x).
+struct TargetMapSnapshot {
+  double resolution = 1.0;
+  int mode = 0;          // 0 additive, 2 multiplicative
+  int num_inserts = 0;   // the map's insert count
+  long long num_points = 0;
+  std::vector<int> coords;      // 3 per voxel
+  std::vector<double> sums;     // 10 per voxel: {sum p | sum C^-1 p (3), sum C | sum C^-1 (6), count}
+  std::vector<unsigned> ages;   // inserts since the voxel was last touched
+  int num_voxels() const { return (int)ages.size(); }
+};
+
+namespace detail {
+// Map snapshot files, little-endian (INTEGRATION.md "Map snapshot files"; fast_gicp_amd/capi.py write_map_file / read_map_file write the same bytes):
+// magic "FVHVMAP\0" | version u32 = 1 | mode i32 | num_inserts i32 | num_voxels i32 | num_points i64 | resolution f64 | coords | sums | ages
+constexpr char kMapFileMagic[8] = {'F', 'V', 'H', 'V', 'M', 'A', 'P', '\0'};
+constexpr unsigned kMapFileVersion = 1;
+constexpr size_t kMapFileHeaderBytes = 40;
+inline void write_map_file(const std::string& path, const TargetMapSnapshot& m) {
+  const size_t n = m.ages.size();
+  if (m.coords.size() != 3 * n || m.sums.size() != 10 * n) throw std::invalid_argument("write_map_file: coords, sums and ages differ in length");
+  unsigned char hdr[kMapFileHeaderBytes];
+  const unsigned version = kMapFileVersion;
+  const int nv = (int)n;
+  std::memcpy(hdr, kMapFileMagic, 8);
+  std::memcpy(hdr + 8, &version, 4);
+  std::memcpy(hdr + 12, &m.mode, 4);
+  std::memcpy(hdr + 16, &m.num_inserts, 4);
+  std::memcpy(hdr + 20, &nv, 4);
+  std::memcpy(hdr + 24, &m.num_points, 8);
+  std::memcpy(hdr + 32, &m.resolution, 8);
+  std::FILE* f = std::fopen(path.c_str(), "wb");
+  if (!f) throw std::runtime_error("write_map_file: cannot open " + path);
+  bool ok = std::fwrite(hdr, 1, sizeof(hdr), f) == sizeof(hdr);
+  if (n) {
+    ok = ok && std::fwrite(m.coords.data(), sizeof(int), 3 * n, f) == 3 * n;
+    ok = ok && std::fwrite(m.sums.data(), sizeof(double), 10 * n, f) == 10 * n;
+    ok = ok && std::fwrite(m.ages.data(), sizeof(unsigned), n, f) == n;
+  }
+  ok = (std::fclose(f) == 0) && ok;
+  if (!ok) throw std::runtime_error("write_map_file: write to " + path + " failed");
+}
+inline TargetMapSnapshot read_map_file(const std::string& path) {
+  std::FILE* f = std::fopen(path.c_str(), "rb");
+  if (!f) throw std::runtime_error("read_map_file: cannot open " + path);
+  struct Closer { std::FILE* f; ~Closer() { std::fclose(f); } } closer{f};
+  unsigned char hdr[kMapFileHeaderBytes];
+  if (std::fread(hdr, 1, sizeof(hdr), f) != sizeof(hdr)) throw std::runtime_error("read_map_file: " + path + " is not a map snapshot (shorter than the header)");
+  if (std::memcmp(hdr, kMapFileMagic, 8) != 0) throw std::runtime_error("read_map_file: " + path + " is not a map snapshot (magic)");
+  unsigned version = 0;
+  int nv = 0;
+  TargetMapSnapshot m;
+  std::memcpy(&version, hdr + 8, 4);
+  std::memcpy(&m.mode, hdr + 12, 4);
+  std::memcpy(&m.num_inserts, hdr + 16, 4);
+  std::memcpy(&nv, hdr + 20, 4);
+  std::memcpy(&m.num_points, hdr + 24, 8);
+  std::memcpy(&m.resolution, hdr + 32, 8);
+  if (version != kMapFileVersion) throw std::runtime_error("read_map_file: " + path + " has version " + std::to_string(version) + ", this build reads " + std::to_string(kMapFileVersion));
+  // the size is checked before anything is allocated from the header's count
+  if (std::fseek(f, 0, SEEK_END) != 0) throw std::runtime_error("read_map_file: cannot seek in " + path);
+  const long long size = (long long)std::ftell(f);
+  if (nv < 0 || size != (long long)kMapFileHeaderBytes + 96LL * nv) throw std::runtime_error("read_map_file: " + path + " is truncated or corrupt");
+  std::fseek(f, (long)kMapFileHeaderBytes, SEEK_SET);
+  const size_t n = (size_t)nv;
+  m.coords.resize(3 * n); m.sums.resize(10 * n); m.ages.resize(n);
+  if (n && (std::fread(m.coords.data(), sizeof(int), 3 * n, f) != 3 * n || std::fread(m.sums.data(), sizeof(double), 10 * n, f) != 10 * n || std::fread(m.ages.data(), sizeof(unsigned), n, f) != n))
+    throw std::runtime_error("read_map_file: " + path + " is truncated");
+  return m;
+}
+}  // namespace detail
+
 /// FastVGICPCuda (fast_vgicp_cuda.hpp:24-85, impl/fast_vgicp_cuda_impl.hpp)
 template <typename PointSource, typename PointTarget>
 class FastVGICPCuda : public LsqRegistration<PointSource, PointTarget> {
@@ -644,6 +718,38 @@ public:
     return removed;
   }
   bool hasIncrementalTarget() const { return incremental_target_; }
+
+  // ---- snapshots of the incremental target map (C ABI: fvh_vgicp_voxelmap_export / _import / _merge_from): save, restore, merge.
+  // Restore = loadTargetMap(path) on a fresh object, or beginIncrementalTarget() + importTargetMap(). Import and merge ADD: sums and
+  // counts add per voxel (exactly: both voxel types are pure sums), ages and the insert count carry over, so pruneTarget(max_age) means on
+  // a restored map what it meant on the original.
+  TargetMapSnapshot exportTargetMap() {
+    TargetMapSnapshot m;
+    int n = 0;
+    call(fvh_vgicp_voxelmap_export(core_, &n, &m.resolution, &m.mode, &m.num_inserts, &m.num_points, nullptr, nullptr, nullptr), "voxelmap_export");
+    m.coords.resize(3 * (size_t)n); m.sums.resize(10 * (size_t)n); m.ages.resize((size_t)n);
+    if (n) call(fvh_vgicp_voxelmap_export(core_, &n, &m.resolution, &m.mode, &m.num_inserts, &m.num_points, m.coords.data(), m.sums.data(), m.ages.data()), "voxelmap_export");
+    return m;
+  }
+  /// adds the snapshot's voxels into the live incremental target (same resolution and mode)
+  void importTargetMap(const TargetMapSnapshot& m) {
+    const size_t n = m.ages.size();
+    if (m.coords.size() != 3 * n || m.sums.size() != 10 * n) throw std::invalid_argument("importTargetMap: coords, sums and ages differ in length");
+    call(fvh_vgicp_voxelmap_import(core_, (int)n, n ? m.coords.data() : nullptr, n ? m.sums.data() : nullptr, n ? m.ages.data() : nullptr, m.resolution, m.mode, m.num_inserts, m.num_points), "voxelmap_import");
+  }
+  /// adds the live incremental target of `other` (same device, resolution and mode) into this one, device to device; `other` is unchanged
+  void mergeTargetFrom(FastVGICPCuda& other) { call(fvh_vgicp_voxelmap_merge_from(core_, other.core_), "voxelmap_merge_from"); }
+  void saveTargetMap(const std::string& path) { detail::write_map_file(path, exportTargetMap()); }
+  /// adds the file's map into the incremental target; an object without one takes the file's resolution and voxel mode and starts one sized for it
+  void loadTargetMap(const std::string& path) {
+    const TargetMapSnapshot m = detail::read_map_file(path);
+    if (!incremental_target_) {
+      call(fvh_vgicp_set_resolution(core_, m.resolution), "set_resolution");
+      call(fvh_vgicp_set_voxel_accumulation_mode(core_, m.mode == 2 ? 2 : 0), "set_voxel_accumulation_mode");
+      beginIncrementalTarget(std::max(m.num_voxels(), 1));
+    }
+    importTargetMap(m);
+  }
 
   // ---- scan streams as a two-stage pipeline (no reference counterpart; C ABI: fvh_vgicp_align_async / _wait, fvh_vgicp_prepare_source_device /
   // _adopt_prepared_source). kitti.cpp:95-128 with the preparation of scan k+1 hidden under the registration of scan k:

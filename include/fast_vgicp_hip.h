@@ -272,6 +272,28 @@ int fvh_vgicp_map_insert_source(fvh_vgicp* h, const double* T16);
 int fvh_vgicp_map_insert_cloud(fvh_vgicp* h, const float* xyz, int n, int stride_floats, const double* covs9, const double* T16, int on_device);
 int fvh_vgicp_map_prune(fvh_vgicp* h, const double* center3, double radius, int max_age, int* num_removed);
 int fvh_vgicp_map_get_info(fvh_vgicp* h, int* incremental, int* num_voxels, int* capacity, int* num_inserts, long long* num_points, int* num_dropped);
+/* Snapshots of the live incremental map: write it out, bring it back, add another map to it.
+ * A snapshot is a header -- resolution, mode (0 additive, 2 multiplicative), num_inserts (the map's insert count), num_points, num_voxels --
+ * and per voxel coords[3] (int32), sums[10] (fp64: {sum p | sum C^-1 p (3), sum C | sum C^-1 (6), count}, the device's own sums) and an age
+ * (inserts since the voxel was last touched; 0 = the last insert touched it). Rows come in ascending packed-key order (z-major, then y,
+ * then x), so two snapshots of equal maps are byte-equal.
+ *   _export: fills the header fields that are not NULL; coords3 / sums10 / ages (num_voxels rows; all three or none) receive the rows. Call it
+ *            with the arrays NULL first to learn num_voxels.
+ *   _import: ADDS n rows into the live map (restore = fvh_vgicp_map_begin + _import): a key already present gets sums += incoming (all ten,
+ *            the count included; a key listed twice adds twice), a new key is created; the map's insert count becomes max(own, num_inserts),
+ *            a voxel's last-touched stamp max(own, new insert count - age), num_points adds. fvh_vgicp_map_prune(max_age) then means on a
+ *            restored map what it meant on the original. Capacity is secured before the launch: nothing is dropped. ages may be NULL (all 0).
+ *   _merge_from: the same with the rows read in place from `other`'s live map, device to device; `other` is unchanged. A merged voxel has
+ *            the smaller of its two ages. Both streams are ordered around the read (a later insert into `other` cannot race it).
+ * With unique keys every sum receives exactly one fp64 add: the result is own + incoming to the bit, whatever the order.
+ * Refusals (the handle and its map stay as they were; host input is validated before anything is queued): no live incremental map, or an
+ * align_async in flight on either handle (FVH_ERR_BAD_STATE); resolution (bit-equal double) or mode different from the live map's, n < 0,
+ * NULL arrays with n > 0, |coordinate| >= 2^20 - 4096, a non-finite sum, a count that is not an integer >= 1, an age >= num_inserts,
+ * other == h, handles on different devices (FVH_ERR_INVALID_ARGUMENT); multi-GPU handles (communicator / peers / tile / map sharding),
+ * FVH_COMPUTE_CUDA_COMPAT, more than 2^28 voxels (FVH_ERR_UNSUPPORTED). */
+int fvh_vgicp_voxelmap_export(fvh_vgicp* h, int* num_voxels, double* resolution, int* mode, int* num_inserts, long long* num_points, int* coords3, double* sums10, unsigned* ages);
+int fvh_vgicp_voxelmap_import(fvh_vgicp* h, int n, const int* coords3, const double* sums10, const unsigned* ages, double resolution, int mode, int num_inserts, long long num_points);
+int fvh_vgicp_voxelmap_merge_from(fvh_vgicp* h, fvh_vgicp* other);
 /* setDebugPrint(true) on the device LM: with the trace on, an align records one row per trial step -- {inner iteration i, y0,
  * yi, rho, lambda, |d|}, the columns LsqRegistration prints (lsq_registration_impl.hpp:143-149) -- fetched afterwards
  * (rows6 may be NULL to query the count). */
