@@ -71,6 +71,8 @@ def load():
         for fn in (L.fvh_vgicp_align_multi, L.fvh_ndt_align_multi):
             fn.argtypes = ALIGN_MULTI_ARGTYPES
             fn.restype = C.c_int
+        L.fvh_debug_lm_replay.argtypes = LM_REPLAY_ARGTYPES
+        L.fvh_debug_lm_replay.restype = C.c_int
         _LIB = L
     return _LIB
 
@@ -370,6 +372,49 @@ def debug_xcd_local():
     w, a = C.c_int(0), C.c_int(0)
     load().fvh_debug_xcd_local(C.byref(w), C.byref(a))
     return w.value, a.value
+
+
+# fvh_debug_lm_replay(device, guess16, params, n_steps, sums, rows, steps_run)
+LM_REPLAY_ARGTYPES = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+LM_REPLAY_ROW = 133  # FVH_LM_REPLAY_ROW
+LM_REPLAY_INTS = ("phase", "outer_iter", "inner_iter", "converged", "lm_failed", "num_linearize", "num_error_evals", "nr_iterations", "corr_cur", "delta_converged")
+PH_LINEARIZE, PH_TRIAL, PH_DONE, PH_TRIAL_FINAL = 0, 1, 2, 6  # LmState::phase (kernels_cost.hpp)
+
+
+def _lm_replay_pose(a):
+    T = np.eye(4)
+    T[:3, :3] = a[:9].reshape(3, 3)
+    T[:3, 3] = a[9:12]
+    return T
+
+
+def lm_replay_row(row):
+    """One row of fvh_debug_lm_replay (layout: include/fast_vgicp_hip.h) as a dict: ints, floats, 4x4 poses, 6x6 H / final_H."""
+    row = np.asarray(row, np.float64)
+    d = {name: int(row[i]) for i, name in enumerate(LM_REPLAY_INTS)}
+    d.update({"lambda": float(row[10]), "nu": float(row[11]), "y0": float(row[12]), "d": row[13:19].copy()})
+    d.update(x0=_lm_replay_pose(row[19:31]), xi=_lm_replay_pose(row[31:43]), x_lin=_lm_replay_pose(row[43:55]))
+    d.update(H=row[55:91].reshape(6, 6).copy(), b=row[91:97].copy(), final_H=row[97:133].reshape(6, 6).copy())
+    return d
+
+
+def debug_lm_replay(guess, sums, device=0, **lm):
+    """The device LM step alone on scripted sums ((n_steps, 32) doubles, one row per evaluation): a list with one lm_replay_row dict per
+    step taken -- the replay stops when the state is done -- or, when max_iterations <= 0 ends it before any step, the initial state alone.
+    `lm`: the fvh_lm_params fields, as align()."""
+    s = np.ascontiguousarray(sums, dtype=np.float64)
+    if s.ndim != 2 or s.shape[1] != 32:
+        raise FvhError("debug_lm_replay: sums must be (n_steps, 32), got %s" % (s.shape,))
+    n = s.shape[0]
+    g = _IDENTITY16 if guess is None else _colmajor16(guess)
+    p = _lm_params(**lm)
+    rows = np.full((max(n, 1), LM_REPLAY_ROW), np.nan)
+    taken = C.c_int(-1)
+    fn = load().fvh_debug_lm_replay
+    rc = fn(int(device), _p(g), C.byref(p), n, _p(s), _p(rows), C.byref(taken))
+    if rc != 0:
+        raise FvhError("fvh_debug_lm_replay: status %d" % rc)
+    return [lm_replay_row(r) for r in rows[:max(taken.value, 1)]]
 
 
 def device_count():

@@ -1138,6 +1138,58 @@ int fvh_debug_slot_pool(int device, int* reserved, int* active, int* recent) {
   if (recent) *recent = c;
   return FVH_OK;
 }
+// ---- test hook: the LM step alone, on sums the caller scripts (the instantiation the RCCL route runs between two evaluations) ----
+static void lm_replay_row(const LmState& s, double* row) {
+  const int ints[10] = {s.phase, s.outer_iter, s.inner_iter, s.converged, s.lm_failed, s.num_linearize, s.num_error_evals, s.nr_iterations, s.corr_cur, s.delta_converged};
+  for (int i = 0; i < 10; i++) row[i] = (double)ints[i];
+  row[10] = s.lambda; row[11] = s.nu; row[12] = s.y0;
+  std::memcpy(row + 13, s.d, sizeof(double) * 6);
+  const PoseD* poses[3] = {&s.x0, &s.xi, &s.x_lin};
+  for (int k = 0; k < 3; k++) { std::memcpy(row + 19 + 12 * k, poses[k]->r, sizeof(double) * 9); std::memcpy(row + 28 + 12 * k, poses[k]->t, sizeof(double) * 3); }
+  std::memcpy(row + 55, s.H, sizeof(double) * 36);
+  std::memcpy(row + 91, s.b, sizeof(double) * 6);
+  std::memcpy(row + 97, s.final_H, sizeof(double) * 36);
+}
+static_assert(FVH_LM_REPLAY_ROW == 97 + 36, "fvh_debug_lm_replay: row layout");
+int fvh_debug_lm_replay(int device, const double* guess16, const fvh_lm_params* params, int n_steps, const double* sums, double* rows, int* steps_run) {
+  if (!guess16 || !params || !sums || !rows || !steps_run) return FVH_ERR_INVALID_ARGUMENT;
+  if (n_steps < 1 || n_steps > 256) return FVH_ERR_INVALID_ARGUMENT;
+  for (int i = 0; i < 16; i++) if (!std::isfinite(guess16[i])) return FVH_ERR_INVALID_ARGUMENT;
+  *steps_run = 0;
+  if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return FVH_ERR_HIP; }
+  const fvh_lm_params& p = *params;
+  hipStream_t stream = nullptr;
+  LmState* st = nullptr;
+  unsigned* ticket = nullptr;
+  LmState* h = new LmState;
+  bool ok = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) == hipSuccess;
+  ok = ok && hipMalloc(reinterpret_cast<void**>(&st), sizeof(LmState)) == hipSuccess && hipMalloc(reinterpret_cast<void**>(&ticket), 64) == hipSuccess;
+  ok = ok && hipMemsetAsync(st, 0, sizeof(LmState), stream) == hipSuccess && hipMemsetAsync(ticket, 0, 64, stream) == hipSuccess;
+  if (ok) {
+    lm_init_kernel<<<1, 64, 0, stream>>>(st, pose_from_colmajor16(guess16), p.rotation_epsilon, p.transformation_epsilon, p.lm_init_lambda_factor, p.max_iterations, p.lm_max_iterations, ticket, p.optimizer != 0 ? 1 : 0);
+    ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(h, st, sizeof(LmState), hipMemcpyDeviceToHost, stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
+  }
+  if (ok && h->phase == PH_DONE) lm_replay_row(*h, rows);  // max_iterations <= 0: no step to take, row 0 is the initial state
+  int taken = 0;
+  while (ok && h->phase != PH_DONE && taken < n_steps) {
+    ok = hipMemcpyAsync(st->sums, sums + (size_t)PART_STRIDE * taken, sizeof(double) * PART_STRIDE, hipMemcpyHostToDevice, stream) == hipSuccess;
+    if (!ok) break;
+    if (p.optimizer) lm_update_kernel<true><<<1, 64, 0, stream>>>(st); else lm_update_kernel<false><<<1, 64, 0, stream>>>(st);
+    ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(h, st, sizeof(LmState), hipMemcpyDeviceToHost, stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
+    if (!ok) break;
+    lm_replay_row(*h, rows + (size_t)FVH_LM_REPLAY_ROW * taken);
+    taken++;
+  }
+  if (!ok) (void)hipGetLastError();
+  if (stream) (void)hipStreamSynchronize(stream);
+  if (st) (void)hipFree(st);
+  if (ticket) (void)hipFree(ticket);
+  if (stream) (void)hipStreamDestroy(stream);
+  delete h;
+  if (!ok) return FVH_ERR_HIP;
+  *steps_run = taken;
+  return FVH_OK;
+}
 int fvh_vgicp_debug_get_table_capacity(fvh_vgicp* h, int* capacity) { CHECK_HANDLE(h); if (!capacity) return FVH_ERR_INVALID_ARGUMENT; *capacity = (int)h->voxelmap.capacity; return FVH_OK; }
 int fvh_vgicp_debug_get_skipped_points(fvh_vgicp* h, int* n) {
   CHECK_HANDLE(h);

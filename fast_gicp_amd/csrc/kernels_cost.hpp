@@ -249,7 +249,11 @@ __device__ __forceinline__ bool dev_is_converged(double rot_eps, double trans_ep
   for (int i = 0; i < 9; i++) rmax = fmax(rmax, fabs(delta.r[i] - ((i % 4 == 0) ? 1.0 : 0.0)));
 #pragma unroll
   for (int i = 0; i < 3; i++) tmax = fmax(tmax, fabs(delta.t[i]));
-  return fmax(rmax / rot_eps, tmax / trans_eps) < 1;
+  // std::max(r, t) is (r < t) ? t : r: a NaN rotation quotient (rot_eps = NaN) stays and the test fails, a NaN translation quotient is
+  // dropped -- fmax would drop either one. (Not reproduced: the reference scales every entry by 1 / eps BEFORE its maxCoeff, so with eps = 0 an
+  // entry that is exactly 0 next to nonzero ones puts a NaN inside Eigen's maxCoeff, whose NaN handling is unspecified; max-then-divide gives inf.)
+  const double qr = rmax / rot_eps, qt = tmax / trans_eps;
+  return (qr < qt ? qt : qr) < 1;
 }
 
 // sums -> symmetric 6x6 H (row-major) and b

@@ -332,6 +332,27 @@ int fvh_vgicp_debug_get_skipped_points(fvh_vgicp* h, int* n);  /* target points 
 int fvh_vgicp_debug_get_persist_aborts(fvh_vgicp* h, int* n);  /* persistent-LM launches whose barrier watchdog fired (each was redone with one launch per LM transition) */
 int fvh_vgicp_debug_get_persist_grid(fvh_vgicp* h, int* blocks, int* capacity);  /* workgroups of the last persistent-LM launch / co-resident workgroup capacity of the device for that kernel */
 int fvh_debug_slot_pool(int device, int* reserved, int* active, int* recent);    /* the process-wide pool that splits those workgroup slots between concurrent aligns: all zero when nothing is in flight */
+/* test hook: the device LM step (kernels_cost.hpp: dev_lm_step_wave -- LDL^T solve, se3_exp, the accept / reject / convergence machine of
+ * lsq_registration_impl.hpp:53-168) replayed ALONE on sums the caller scripts. No cost kernel runs: on a stream of its own the call
+ * initialises one LM state from guess16 (column-major, finite) and *params, then for step s = 0 .. n_steps - 1 copies sums[32 s .. 32 s + 31]
+ * into the state where a cost evaluation would have left them, launches the one-wave update kernel the RCCL route runs between two
+ * evaluations (the Gauss-Newton instantiation when params->optimizer != 0) and writes the state into rows[FVH_LM_REPLAY_ROW * s ...].
+ * A row of sums: [0] error, [1..6] b, [7..12] H rot-rot (xx xy xz yy yz zz), [13..21] H rot-trans (3x3 row-major), [22..27] H trans-trans
+ * (xx xy xz yy yz zz) of the linearisation this evaluation computed, [28] the trial error of a fused trial evaluation (a phase-6 trial, error
+ * only, carries it at [0]), [29..31] zero.
+ * A row of the result, all doubles:
+ *   [0] phase (0 linearize, 1 trial, 2 done, 6 final trial) [1] outer_iter [2] inner_iter [3] converged [4] lm_failed
+ *   [5] num_linearize [6] num_error_evals [7] nr_iterations [8] corr_cur [9] delta_converged
+ *   [10] lambda [11] nu [12] y0 [13..18] d (the step proposed last)
+ *   [19..30] x0, [31..42] xi, [43..54] x_lin: each the 9 rotation entries row-major, then the 3 translation entries
+ *   [55..90] H (6x6, as the state holds it: row-major, symmetric) [91..96] b [97..132] final_H (6x6)
+ * The replay stops once the state is done: *steps_run = steps taken (the last one is the step that ended the loop), rows beyond it are
+ * left untouched. max_iterations <= 0: the state is done before any step -- *steps_run = 0 and rows[0 .. FVH_LM_REPLAY_ROW) holds the
+ * initial state. Everything is freed before the call returns. FVH_ERR_INVALID_ARGUMENT: a null pointer, a non-finite guess, n_steps
+ * outside 1..256 (checked before the device is touched). */
+#define FVH_LM_REPLAY_ROW 133
+int fvh_debug_lm_replay(int device, const double* guess16, const fvh_lm_params* params, int n_steps, const double* sums /* n_steps x 32 */,
+                        double* rows /* n_steps x FVH_LM_REPLAY_ROW */, int* steps_run);
 /* persistent LM kernel, XCD-local hand-offs (kernels_cost.hpp): *wanted = 1 while the process still asks for them, *placement_aborts =
  * launches that ended because the dispatcher had not placed the workgroups of a group on one XCD (3 of those switch the flavour off) */
 int fvh_debug_xcd_local(int* wanted, int* placement_aborts);
