@@ -392,12 +392,15 @@ int calc_cov_rbf(Engine* e, CloudDev& c, double kernel_width, double max_dist, i
   c.has_cov_sorted = false;
   if (c.n) {
     const float md = (float)max_dist;
+    // Slots past the end of a ragged last tile are candidates at 3e18 (load_candidate: sq = 2.7e37) and lanes past the last box test +inf:
+    // the radius cut stays below both even when max_dist^2 overflows fp32 ("no limit"). Real clouds hold no pair 3e18 apart.
+    const float md_sq = fminf(md * md, 1e37f);
 #ifdef FVH_TEST_KERNELS  // test build only: FVH_RBF_MODE=0 full sweep, 2: eight queries per wave (both superseded by the one-query-per-wave sweep)
     static const int rbf_mode = (int)fvh_env_ll("FVH_RBF_MODE", 1);
     const int waves = (c.n + RBF_Q - 1) / RBF_Q;
     if (rbf_mode == 0 && !sharded) {
       ProfScope ps(e, "rbf");
-      cov_rbf_kernel<<<(waves + 3) / 4, 256, 0, e->stream>>>(c.pts.as<float4>(), c.n, (float)kernel_width, md * md, method, c.cov.as<float4>());
+      cov_rbf_kernel<<<(waves + 3) / 4, 256, 0, e->stream>>>(c.pts.as<float4>(), c.n, (float)kernel_width, md_sq, method, c.cov.as<float4>());
     } else
 #endif
     {
@@ -423,14 +426,14 @@ int calc_cov_rbf(Engine* e, CloudDev& c, double kernel_width, double max_dist, i
       const Tile t = peer_tile(e, c.n);
       ProfScope ps(e, "rbf");
 #ifdef FVH_TEST_KERNELS
-      if (rbf_mode == 2 && !sharded) cov_rbf_tiled_kernel<<<(waves + 3) / 4, 256, 0, e->stream>>>(c.sorted.as<float4>(), c.bbox.as<float4>(), c.n, (float)kernel_width, md * md, method, c.cov.as<float4>());
+      if (rbf_mode == 2 && !sharded) cov_rbf_tiled_kernel<<<(waves + 3) / 4, 256, 0, e->stream>>>(c.sorted.as<float4>(), c.bbox.as<float4>(), c.n, (float)kernel_width, md_sq, method, c.cov.as<float4>());
       else
 #endif
       if (t.hi > t.lo) {
         // sweep (one query per wave) -> ten totals per query; regularisation with one thread per query
         HIP_OR_FAIL(e, e->rbf_sums.ensure(sizeof(double) * 10 * (size_t)c.n));
         // (single-wave workgroups, which shortened the k-NN kernel, change nothing here: 152 us either way -- this sweep keeps the VALU pipes 95 % busy)
-        cov_rbf1_kernel<<<(t.hi - t.lo + 3) / 4, 256, 0, e->stream>>>(c.sorted.as<float4>(), c.bbox.as<float4>(), c.bbox2.as<float4>(), c.n, (float)kernel_width, md * md, method, c.cov.as<float4>(), t.lo, t.hi,
+        cov_rbf1_kernel<<<(t.hi - t.lo + 3) / 4, 256, 0, e->stream>>>(c.sorted.as<float4>(), c.bbox.as<float4>(), c.bbox2.as<float4>(), c.n, (float)kernel_width, md_sq, method, c.cov.as<float4>(), t.lo, t.hi,
                                                                       e->rbf_sums.as<double>());
         float4* cov_sorted = nullptr;
         if (!sharded && coherent_order(c, e->params.coherent_min_points)) { HIP_OR_FAIL(e, c.cov_sorted.ensure(sizeof(float4) * 2 * (size_t)c.n)); cov_sorted = c.cov_sorted.as<float4>(); }

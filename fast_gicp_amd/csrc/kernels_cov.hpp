@@ -977,6 +977,8 @@ __global__ __launch_bounds__(256) void cov_rbf_tiled_kernel(const float4* __rest
 // tile box against the group's box and ends with 80 wave reductions: 420 us at 100k points against 190 us for k-NN +
 // covariance). Lane l accumulates the candidates it sees at position l of every tile within max_dist, in ascending
 // tile order -- the arithmetic of cov_rbf_tiled_kernel, term by term (tiles it skips would have contributed weight 0).
+// max_dist_sq is finite and below the squared distance of a padded slot (calc_cov_rbf clamps it): `sq > max_dist_sq` is what keeps
+// the padding of a ragged last tile out of the sums when kernel_width == 0, and `+inf <= max_dist_sq` never passes a box test.
 // The wave of a query ends with ten wave totals {W, X, Y, Z, XX, ..., ZZ}. They go to `sums` (SoA: sums[k * n + q]) and
 // cov_rbf_finish_kernel turns them into the regularised covariance with one THREAD per query: the eigen-decomposition of the
 // PLANE regularisation is ~1,000 dependent fp64 instructions, and run by lane 0 of a one-query wave it cost a full wave's issue
