@@ -16,6 +16,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -77,7 +78,7 @@ struct Engine {
   unsigned long long* result_dev = nullptr;  // its device address
   // align_multi (fvh_*_align_multi): the per-align buffers once per hypothesis -- states, partial / row regions, tickets, broadcast areas,
   // correspondence buffers, mapped result blocks (kernels_cost.hpp: GangParams) and the guesses. Grown once per K (never while an align_async is
-  // in flight: the C ABI refuses the call), freed with the handle.
+  // in flight -- Pipeline::in_flight(): CHECK_HANDLE refuses the call), freed with the handle.
   int multi_cap = 0;
   DevBuf multi_state, multi_partials, multi_ticket, multi_bcast, multi_corr, multi_guess;
   void* multi_pinned = nullptr;                    // K states (copies of the device states) + K guesses
@@ -166,7 +167,6 @@ struct Engine {
   DevBuf gather_stage;  // RCCL route: covariances of the whole cloud in Morton order (ncclAllGather in place)
   hipStream_t side = nullptr;
   hipEvent_t side_done = nullptr;
-  bool async_in_flight = false;    // fvh_vgicp_align_async .. _align_wait: the handle's clouds, map and LM state belong to the running kernel
   // A persistent LM grid that takes more than 3/4 of the device's co-resident workgroup slots must not share the chip with another stream's
   // kernels while it is being DISPATCHED: with every XCD nearly full the dispatcher places workgroups wherever room appears, the
   // block -> XCD pattern the XCD-local hand-offs rely on (kernels_cost.hpp) no longer holds, and the launch ends in its watchdog (measured with
@@ -455,16 +455,15 @@ struct fvh_vgicp {
   double gicp_max_dist = 3.4028234663852886e38;
   // Pipelined scan streams (fvh_vgicp_prepare_source_device / _adopt_prepared_source / _align_async / _align_wait): the NEXT source cloud -- its
   // Morton order, neighbour lists, covariances AND its own voxel map, which swap_source_and_target() needs one registration later -- is
-  // prepared in `next_source` / `next_map` on the handle's second stream (Engine::side) while the LM kernel of the current pair runs on the
+  // prepared in `pipe` (host_stages.inc.hpp: Pipeline) on the handle's second stream while the LM kernel of the current pair runs on the
   // main one. `source_map` is the map that came with the adopted source: swap_source_and_target() then swaps maps instead of building one.
-  CloudDev next_source;
-  VoxelMapDev next_map, source_map;
-  bool next_ready = false;
-  hipEvent_t prep_done = nullptr;
-  AlignCtx pending;
+  Pipeline pipe;
+  VoxelMapDev source_map;
+  bool in_flight() const { return pipe.in_flight(); }
+  static constexpr const char* align_wait_fn = "fvh_vgicp_align_wait";
   void source_changed() { source_map.invalidate(); }
   bool live_map_stale = false;  // the target's covariances changed after `voxelmap` was built (legal: the map stays as built until create_target_voxelmap -- but it must not be carried over a swap)
-  void map_rules_changed() { source_map.invalidate(); next_map.invalidate(); next_ready = false; }  // accumulation mode / precision: prepared maps were built under the old rule
+  void map_rules_changed() { source_map.invalidate(); pipe.invalidate(); }  // accumulation mode / precision: prepared maps were built under the old rule
   CostSource cost_source() const {
     // multi-GPU: the tiles are ranges of the Morton order whatever the size of the cloud (spatially compact shards)
     const int* order = e.sharded() ? (source.has_sorted ? source.order.as<int>() : nullptr) : coherent_order(source, e.params.coherent_min_points);
@@ -517,13 +516,14 @@ struct fvh_ndt {
   int distance_mode = FVH_NDT_D2D;  // ndt_cuda.cu:21
   CloudDev source, target;
   VoxelMapDev source_vm, target_vm;
-  // Pipelined frame streams (fvh_ndt_prepare_source_device / _adopt_prepared_source): the NEXT source cloud and its voxel map are built
-  // in this slot on the handle's second stream (Engine::side) while the LM kernel of the current frame runs on the main one
-  CloudDev next_source;
-  VoxelMapDev next_vm;
-  bool next_ready = false;
-  hipEvent_t prep_done = nullptr;
-  AlignCtx pending;  // fvh_ndt_align_async .. fvh_ndt_align_wait
+  // Pipelined frame streams (fvh_ndt_prepare_source* / _adopt_prepared_source / _align_async / _align_wait): the NEXT source cloud and its
+  // voxel map are built in `pipe` on the handle's second stream while the LM kernel of the current frame runs on the main one
+  Pipeline pipe;
+  bool in_flight() const { return pipe.in_flight(); }
+  static constexpr const char* align_wait_fn = "fvh_ndt_align_wait";
+  // the instantiation of the handle's distance mode: f(std::integral_constant<int, MODE_NDT_P2D or MODE_NDT_D2D>{})
+  template <class F>
+  int by_mode(F&& f) const { return distance_mode == FVH_NDT_P2D ? f(std::integral_constant<int, MODE_NDT_P2D>{}) : f(std::integral_constant<int, MODE_NDT_D2D>{}); }
   CostSource cost_source() const {
     const bool tiled = e.tile_n > 1;  // fvh_ndt_set_source_tile: this handle evaluates one spatial tile of the source
     if (distance_mode == FVH_NDT_P2D) {
@@ -569,14 +569,18 @@ struct fvh_ndt {
 struct fvh_voxelgrid {
   Engine e;
   DownsampleDev d;
+  bool in_flight() const { return false; }  // (a filter has no pipeline: CHECK_HANDLE never refuses on it)
+  static constexpr const char* align_wait_fn = "";
 };
 
 // CHECK_HANDLE_SOURCE_CHAIN: the calls that only touch the SOURCE cloud -- they may run beside a target-map build on the side
 // stream (Engine::side); every other call orders the main stream after that build first.
+// Between align_async and align_wait the handle's clouds, maps and LM state belong to the running LM kernel: both refuse, before they touch
+// anything. (What stays legal in between goes through CHECK_HANDLE_HOST_ONLY or takes no guard at all.)
 #define CHECK_HANDLE_SOURCE_CHAIN(h) \
   if (!(h)) return FVH_ERR_INVALID_ARGUMENT; \
   { hipError_t _e = hipSetDevice((h)->e.device); if (_e != hipSuccess) return (h)->e.hipfail(_e, "hipSetDevice"); } \
-  if ((h)->e.async_in_flight) return (h)->e.fail(FVH_ERR_BAD_STATE, "an align_async is in flight: call fvh_vgicp_align_wait first"); \
+  if ((h)->in_flight()) return (h)->e.fail(FVH_ERR_BAD_STATE, std::string("an align_async is in flight: call ") + (h)->align_wait_fn + " first"); \
   (h)->e.was_quiet = (h)->e.quiet; (h)->e.quiet = false;
 // CHECK_HANDLE_HOST_ONLY: plain host-side setters that queue nothing: they leave the engine's stream bookkeeping alone.
 #define CHECK_HANDLE_HOST_ONLY(h) \
@@ -622,9 +626,8 @@ int fvh_vgicp_destroy(fvh_vgicp* h) {
   h->e.deferred = nullptr;
   if (h->e.side) (void)hipStreamSynchronize(h->e.side);
   if (h->e.stream) (void)hipStreamSynchronize(h->e.stream);
-  if (h->pending.active) { h->pending.release_slots(); h->pending.active = false; }
-  h->source.release(); h->target.release(); h->voxelmap.release(); h->gicp_records.release(); h->next_source.release(); h->next_map.release(); h->source_map.release(); h->insert_cloud.release();
-  if (h->prep_done) (void)hipEventDestroy(h->prep_done);
+  h->pipe.release();
+  h->source.release(); h->target.release(); h->voxelmap.release(); h->gicp_records.release(); h->source_map.release(); h->insert_cloud.release();
   for (hipEvent_t ev : h->merge_ev) if (ev) (void)hipEventDestroy(ev);
   h->e.shutdown();
   delete h;
@@ -720,7 +723,7 @@ int fvh_vgicp_voxelmap_merge_from(fvh_vgicp* h, fvh_vgicp* other) {
   if (other == h) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_merge_from: a map cannot be merged into itself");
   if (other->e.device != h->e.device) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_merge_from: the two handles are on different devices");
   if (other->e.sharded() || other->shard_map || other->e.precision == FVH_COMPUTE_CUDA_COMPAT) return h->e.fail(FVH_ERR_UNSUPPORTED, "voxelmap_merge_from: the other handle is a multi-GPU / sharded / FVH_COMPUTE_CUDA_COMPAT handle");
-  if (other->e.async_in_flight) return h->e.fail(FVH_ERR_BAD_STATE, "voxelmap_merge_from: an align_async is in flight on the other handle: call fvh_vgicp_align_wait first");
+  if (other->in_flight()) return h->e.fail(FVH_ERR_BAD_STATE, "voxelmap_merge_from: an align_async is in flight on the other handle: call fvh_vgicp_align_wait first");
   { const int rc = other->e.settle(); if (rc) return h->e.fail(rc, "voxelmap_merge_from: the other handle: " + other->e.err); }
   for (hipEvent_t& ev : h->merge_ev) if (!ev) HIP_OR_FAIL(&h->e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
   other->e.quiet = false;  // (its stream now holds a wait)
@@ -811,12 +814,18 @@ static int uploaded(Engine* e, CloudDev& c, int rc) {
   if (!e->device_search_seen && !e->sharded() && c.n < e->params.coherent_min_points) return FVH_OK;  // nobody may ever need the order: it stays lazy (ensure_sorted where it is consumed)
   return ensure_sorted(e, c);
 }
-int fvh_vgicp_set_source_cloud(fvh_vgicp* h, const float* xyz, int n) { CHECK_HANDLE_SOURCE_CHAIN(h); h->e.has_corr = false; cloud_replaced(h->source); h->source_changed(); return uploaded(&h->e, h->source, upload_cloud(&h->e, h->source, xyz, n, 3, false)); }
-int fvh_vgicp_set_target_cloud(fvh_vgicp* h, const float* xyz, int n) { CHECK_HANDLE(h); h->target_replaced(); cloud_replaced(h->target); return uploaded(&h->e, h->target, upload_cloud(&h->e, h->target, xyz, n, 3, false)); }
-int fvh_vgicp_set_source_cloud_strided(fvh_vgicp* h, const float* xyz, int n, int stride) { CHECK_HANDLE_SOURCE_CHAIN(h); h->e.has_corr = false; cloud_replaced(h->source); h->source_changed(); return uploaded(&h->e, h->source, upload_cloud(&h->e, h->source, xyz, n, stride, false)); }
-int fvh_vgicp_set_target_cloud_strided(fvh_vgicp* h, const float* xyz, int n, int stride) { CHECK_HANDLE(h); h->target_replaced(); cloud_replaced(h->target); return uploaded(&h->e, h->target, upload_cloud(&h->e, h->target, xyz, n, stride, false)); }
-int fvh_vgicp_set_source_cloud_device(fvh_vgicp* h, const float* d, int n, int stride) { CHECK_HANDLE_SOURCE_CHAIN(h); h->e.has_corr = false; cloud_replaced(h->source); h->source_changed(); return uploaded(&h->e, h->source, upload_cloud(&h->e, h->source, d, n, stride, true)); }
-int fvh_vgicp_set_target_cloud_device(fvh_vgicp* h, const float* d, int n, int stride) { CHECK_HANDLE(h); h->target_replaced(); cloud_replaced(h->target); return uploaded(&h->e, h->target, upload_cloud(&h->e, h->target, d, n, stride, true)); }
+static int vgicp_set_cloud(fvh_vgicp* h, bool is_target, const float* xyz, int n, int stride, bool on_device) {
+  CloudDev& c = is_target ? h->target : h->source;
+  if (is_target) h->target_replaced(); else { h->e.has_corr = false; h->source_changed(); }
+  cloud_replaced(c);
+  return uploaded(&h->e, c, upload_cloud(&h->e, c, xyz, n, stride, on_device));
+}
+int fvh_vgicp_set_source_cloud(fvh_vgicp* h, const float* xyz, int n) { CHECK_HANDLE_SOURCE_CHAIN(h); return vgicp_set_cloud(h, false, xyz, n, 3, false); }
+int fvh_vgicp_set_target_cloud(fvh_vgicp* h, const float* xyz, int n) { CHECK_HANDLE(h); return vgicp_set_cloud(h, true, xyz, n, 3, false); }
+int fvh_vgicp_set_source_cloud_strided(fvh_vgicp* h, const float* xyz, int n, int stride) { CHECK_HANDLE_SOURCE_CHAIN(h); return vgicp_set_cloud(h, false, xyz, n, stride, false); }
+int fvh_vgicp_set_target_cloud_strided(fvh_vgicp* h, const float* xyz, int n, int stride) { CHECK_HANDLE(h); return vgicp_set_cloud(h, true, xyz, n, stride, false); }
+int fvh_vgicp_set_source_cloud_device(fvh_vgicp* h, const float* d, int n, int stride) { CHECK_HANDLE_SOURCE_CHAIN(h); return vgicp_set_cloud(h, false, d, n, stride, true); }
+int fvh_vgicp_set_target_cloud_device(fvh_vgicp* h, const float* d, int n, int stride) { CHECK_HANDLE(h); return vgicp_set_cloud(h, true, d, n, stride, true); }
 int fvh_vgicp_set_source_neighbors(fvh_vgicp* h, int k, const int* idx) { CHECK_HANDLE(h); return set_neighbors(&h->e, h->source, k, idx); }
 int fvh_vgicp_set_target_neighbors(fvh_vgicp* h, int k, const int* idx) { CHECK_HANDLE(h); return set_neighbors(&h->e, h->target, k, idx); }
 int fvh_vgicp_find_source_neighbors(fvh_vgicp* h, int k) { CHECK_HANDLE_SOURCE_CHAIN(h); return h->e.after_source_chain_call(find_neighbors(&h->e, h->source, k)); }
@@ -982,7 +991,7 @@ int fvh_vgicp_align(fvh_vgicp* h, const double* guess, const fvh_lm_params* p, f
     rc = h->build_map(h->resolution);
     if (rc) return rc;
   }
-  h->e.crowd_fence = h->next_ready ? h->prep_done : nullptr;  // (a preparation still running on the second stream: a grid that crowds the chip waits for it)
+  h->pipe.arm_crowd_fence(&h->e);
   const int rc = do_align<MODE_VGICP>(&h->e, h->cost_source(), h->voxelmap, guess, p, r, h->rebuild_safe());
   // the result is on the host: everything this handle queued has run (of a persistent launch only the workgroups' exit remains,
   // and they touch neither clouds nor the map any more)
@@ -1002,7 +1011,7 @@ int fvh_vgicp_align_multi(fvh_vgicp* h, int k, const double* guesses16, const fv
   { const int rc = check_multi_args(&h->e, k, guesses16, results); if (rc) return rc; }
   if (h->e.sharded()) return h->e.fail(FVH_ERR_UNSUPPORTED, "align_multi: not on a multi-GPU handle");
   if (!h->source.has_pts || !h->source.has_cov) return h->e.fail(FVH_ERR_BAD_STATE, "align: source cloud/covariances not set");
-  h->e.crowd_fence = h->next_ready ? h->prep_done : nullptr;
+  h->pipe.arm_crowd_fence(&h->e);
   const int rc = do_align_multi<MODE_VGICP>(&h->e, h->cost_source(), h->voxelmap, k, guesses16, p, results, grid_blocks_out, h->rebuild_safe());
   if (rc == FVH_OK) h->e.quiet = true;
   return rc;
@@ -1017,16 +1026,11 @@ int fvh_vgicp_align_async(fvh_vgicp* h, const double* guess, const fvh_lm_params
   CHECK_HANDLE(h);
   if (h->e.sharded()) return h->e.fail(FVH_ERR_UNSUPPORTED, "align_async: not on a multi-GPU handle");
   if (!h->source.has_pts || !h->source.has_cov) return h->e.fail(FVH_ERR_BAD_STATE, "align: source cloud/covariances not set");
-  h->e.crowd_fence = h->next_ready ? h->prep_done : nullptr;
-  const int rc = align_begin<MODE_VGICP>(&h->e, h->pending, h->cost_source(), h->voxelmap, guess, p);
-  if (rc == FVH_OK) h->e.async_in_flight = true;
-  return rc;
+  return h->pipe.align_async<MODE_VGICP>(&h->e, h->cost_source(), h->voxelmap, guess, p);
 }
 int fvh_vgicp_align_wait(fvh_vgicp* h, fvh_lm_result* r) {
   CHECK_HANDLE_HOST_ONLY(h);
-  if (!h->pending.active) return h->e.fail(FVH_ERR_BAD_STATE, "align_wait: no align_async in flight");
-  h->e.async_in_flight = false;
-  const int rc = align_finish<MODE_VGICP>(&h->e, h->pending, h->cost_source(), h->voxelmap, r, h->rebuild_safe());
+  const int rc = h->pipe.align_wait<MODE_VGICP>(&h->e, h->cost_source(), h->voxelmap, r, h->rebuild_safe());
   if (rc == FVH_OK) h->e.quiet = true;
   return rc;
 }
@@ -1035,15 +1039,10 @@ static int vgicp_prepare(fvh_vgicp* h, const float* d_xyz, int n, int stride, bo
   Engine* e = &h->e;
   if (stages < 1 || stages > 3) return e->fail(FVH_ERR_INVALID_ARGUMENT, "prepare_source: stages must be 1 (order + neighbours), 2 (+ covariances) or 3 (+ voxel map)");
   if (e->sharded()) return e->fail(FVH_ERR_UNSUPPORTED, "prepare_source: not on a multi-GPU handle");
-  hipStream_t ps = e->side_stream();  // null (FVH_SIDE_STREAM=0): in order on the main stream -- correct, nothing overlaps
-  if (ps == nullptr && h->pending.active) return e->fail(FVH_ERR_BAD_STATE, "prepare_source: this handle has no second stream; call it outside align_async .. align_wait");
-  if (!h->prep_done) HIP_OR_FAIL(e, hipEventCreateWithFlags(&h->prep_done, hipEventDisableTiming));
-  // a target-map build that swap_source_and_target() deferred goes first (same stream: in order)
-  if (e->deferred) { const int rc = e->after_source_chain_call(FVH_OK); if (rc) return rc; }
-  { const int rc = e->feeder_stream(&ps); if (rc) return rc; }
-  h->next_ready = false;
-  h->next_map.invalidate();
-  cloud_replaced(h->next_source);
+  Pipeline& pl = h->pipe;
+  hipStream_t ps = nullptr;
+  { const int rc = pl.begin_prepare(e, &ps); if (rc) return rc; }
+  cloud_replaced(pl.next_source);
   // The stages below are the ones the sequential calls run; they launch on the handle's current stream: for the length of this call that is
   // the second one. The scratch they use (sort keys / histograms, the RBF sums) is not touched by a running LM kernel.
   struct StreamSwap { Engine* e; hipStream_t main; ~StreamSwap() { e->stream = main; } } swap{e, e->stream};
@@ -1054,25 +1053,23 @@ static int vgicp_prepare(fvh_vgicp* h, const float* d_xyz, int n, int stride, bo
   // covariances behind it ran AFTER the LM kernel instead of beside it: 5,760 registrations/s against 6,990 with the passes.
   struct SortMode { Engine* e; int saved; ~SortMode() { e->params.sort_mode = saved; } } sort_mode{e, e->params.sort_mode};
   if (ps != nullptr) e->params.sort_mode = 0;  // (also when the align is launched right AFTER this call: the chain then runs beside it all the same)
-  int rc = upload_cloud(e, h->next_source, d_xyz, n, stride, on_device, true, ps);
+  int rc = upload_cloud(e, pl.next_source, d_xyz, n, stride, on_device, true, ps);
   if (rc || n == 0) return rc ? rc : e->fail(FVH_ERR_INVALID_ARGUMENT, "prepare_source: empty cloud");
-  rc = ensure_sorted(e, h->next_source);
+  rc = ensure_sorted(e, pl.next_source);
   if (rc) return rc;
-  if (rbf) { if (stages >= 2) rc = calc_cov_rbf(e, h->next_source, h->kernel_width, h->kernel_max_dist, regularization); }
+  if (rbf) { if (stages >= 2) rc = calc_cov_rbf(e, pl.next_source, h->kernel_width, h->kernel_max_dist, regularization); }
   else {
-    rc = find_neighbors(e, h->next_source, k);
-    if (!rc && stages >= 2) rc = calc_cov_knn(e, h->next_source, regularization);
+    rc = find_neighbors(e, pl.next_source, k);
+    if (!rc && stages >= 2) rc = calc_cov_knn(e, pl.next_source, regularization);
   }
   if (rc) return rc;
   if (stages >= 3) {
-    if (h->next_map.nv_hint < 0) h->next_map.nv_hint = std::max(h->voxelmap.nv_hint, h->source_map.nv_hint);
-    rc = h->voxel_mode == 2 ? build_voxelmap<2>(e, h->next_source, h->next_map, h->resolution, false, false, ps, false, /*detached=*/true)
-                            : build_voxelmap<0>(e, h->next_source, h->next_map, h->resolution, false, false, ps, false, /*detached=*/true);
+    if (pl.next_map.nv_hint < 0) pl.next_map.nv_hint = std::max(h->voxelmap.nv_hint, h->source_map.nv_hint);
+    rc = h->voxel_mode == 2 ? build_voxelmap<2>(e, pl.next_source, pl.next_map, h->resolution, false, false, ps, false, /*detached=*/true)
+                            : build_voxelmap<0>(e, pl.next_source, pl.next_map, h->resolution, false, false, ps, false, /*detached=*/true);
     if (rc) return rc;
   }
-  HIP_OR_FAIL(e, hipEventRecord(h->prep_done, e->stream));
-  h->next_ready = true;
-  return FVH_OK;
+  return pl.end_prepare(e, ps);
 }
 int fvh_vgicp_prepare_source_device(fvh_vgicp* h, const float* d_xyz, int n, int stride, int k, int regularization, int rbf, int stages) { return vgicp_prepare(h, d_xyz, n, stride, true, k, regularization, rbf, stages); }
 // the same for a HOST cloud (what the reference's callers hold): consumed before the call returns (a memcpy into the handle's pinned staging
@@ -1080,22 +1077,7 @@ int fvh_vgicp_prepare_source_device(fvh_vgicp* h, const float* d_xyz, int n, int
 int fvh_vgicp_prepare_source(fvh_vgicp* h, const float* xyz, int n, int stride, int k, int regularization, int rbf, int stages) { return vgicp_prepare(h, xyz, n, stride, false, k, regularization, rbf, stages); }
 int fvh_vgicp_adopt_prepared_source(fvh_vgicp* h) {
   CHECK_HANDLE(h);  // (a map build swap_source_and_target() deferred runs here, in order on the main stream: queued on the second one it reached the LM kernel 10 us later -- measured)
-  Engine* e = &h->e;
-  if (!h->next_ready) return e->fail(FVH_ERR_BAD_STATE, "adopt_prepared_source: nothing prepared (fvh_vgicp_prepare_source_device)");
-  h->next_ready = false;
-  h->source.swap(h->next_source);
-  std::swap(h->source_map, h->next_map);
-  e->has_corr = false;
-  // As a rule the preparation ended while the last align was still running: the host sees that at no cost. Otherwise the main stream waits.
-  if (e->side) {
-    hipError_t q = hipErrorNotReady;
-    for (int spins = 0; spins < 64 && q == hipErrorNotReady; spins++) q = hipEventQuery(h->prep_done);
-    if (q != hipSuccess) {
-      (void)hipGetLastError();
-      HIP_OR_FAIL(e, hipStreamWaitEvent(e->stream, h->prep_done, 0));
-    }
-  }
-  return FVH_OK;
+  return h->pipe.adopt(&h->e, h->source, h->source_map, "fvh_vgicp_prepare_source_device");
 }
 static int get_lm_trace(Engine* e, int* n, double* rows6) {
   if (!n) return e->fail(FVH_ERR_INVALID_ARGUMENT, "get_lm_trace: null count");
@@ -1356,8 +1338,6 @@ int fvh_vgicp_peer_detach(fvh_vgicp* h) { CHECK_HANDLE(h); h->e.peer_detach(); h
 int fvh_vgicp_comm_destroy(fvh_vgicp* h) { CHECK_HANDLE(h); if (h->e.comm) { g_rccl.CommDestroy(h->e.comm); h->e.comm = nullptr; } h->e.nranks = 1; h->e.rank = 0; return FVH_OK; }
 
 // ---- NDT ---------------------------------------------------------------------------------------
-// between fvh_ndt_align_async and fvh_ndt_align_wait the handle's clouds, maps and state belong to the running LM kernel
-#define NDT_NOT_PENDING(h) if ((h)->pending.active) return (h)->e.fail(FVH_ERR_BAD_STATE, "an align_async is in flight: call fvh_ndt_align_wait first");
 int fvh_ndt_create(int device, fvh_ndt** out) {
   if (!out) return FVH_ERR_INVALID_ARGUMENT;
   *out = nullptr;
@@ -1374,48 +1354,52 @@ int fvh_ndt_destroy(fvh_ndt* h) {
   (void)hipSetDevice(h->e.device);
   if (h->e.stream) (void)hipStreamSynchronize(h->e.stream);
   if (h->e.side) (void)hipStreamSynchronize(h->e.side);
-  if (h->pending.active) { h->pending.release_slots(); h->pending.active = false; }
-  h->source.release(); h->target.release(); h->source_vm.release(); h->target_vm.release(); h->next_source.release(); h->next_vm.release();
-  if (h->prep_done) (void)hipEventDestroy(h->prep_done);
+  h->pipe.release();
+  h->source.release(); h->target.release(); h->source_vm.release(); h->target_vm.release();
   h->e.shutdown();
   delete h;
   return FVH_OK;
 }
 const char* fvh_ndt_last_error(const fvh_ndt* h) { return h ? h->e.err.c_str() : "null handle"; }
-int fvh_ndt_set_distance_mode(fvh_ndt* h, int m) { CHECK_HANDLE(h); NDT_NOT_PENDING(h); if (m != FVH_NDT_P2D && m != FVH_NDT_D2D) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "bad distance mode"); h->distance_mode = m; h->e.has_corr = false; return FVH_OK; }
-int fvh_ndt_set_resolution(fvh_ndt* h, double r) { CHECK_HANDLE(h); NDT_NOT_PENDING(h); if (!(r > 0)) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "resolution must be > 0"); h->resolution = r; return FVH_OK; }
-int fvh_ndt_set_neighbor_search_method(fvh_ndt* h, int m, double radius) { CHECK_HANDLE(h); NDT_NOT_PENDING(h); return h->e.set_offsets(m, radius); }
+int fvh_ndt_set_distance_mode(fvh_ndt* h, int m) { CHECK_HANDLE(h); if (m != FVH_NDT_P2D && m != FVH_NDT_D2D) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "bad distance mode"); h->distance_mode = m; h->e.has_corr = false; return FVH_OK; }
+int fvh_ndt_set_resolution(fvh_ndt* h, double r) { CHECK_HANDLE(h); if (!(r > 0)) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "resolution must be > 0"); h->resolution = r; return FVH_OK; }
+int fvh_ndt_set_neighbor_search_method(fvh_ndt* h, int m, double radius) { CHECK_HANDLE(h); return h->e.set_offsets(m, radius); }
 int fvh_ndt_set_precision(fvh_ndt* h, int p) {
-  CHECK_HANDLE(h); NDT_NOT_PENDING(h);
+  CHECK_HANDLE(h);
   if (p != FVH_COMPUTE_FP64 && p != FVH_COMPUTE_FP32 && p != FVH_COMPUTE_CUDA_COMPAT) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "bad precision");
   if ((p == FVH_COMPUTE_CUDA_COMPAT) != (h->e.precision == FVH_COMPUTE_CUDA_COMPAT)) { h->source_vm.invalidate(); h->target_vm.invalidate(); h->e.has_corr = false; }  // the voxel records of the two arithmetics differ
   h->e.precision = p;
   return FVH_OK;
 }
 int fvh_ndt_get_engine_params(fvh_ndt* h, fvh_engine_params* out) { CHECK_HANDLE_HOST_ONLY(h); return get_engine_params(&h->e, out); }
-int fvh_ndt_set_engine_params(fvh_ndt* h, const fvh_engine_params* p) { CHECK_HANDLE(h); NDT_NOT_PENDING(h); return set_engine_params(&h->e, p); }
+int fvh_ndt_set_engine_params(fvh_ndt* h, const fvh_engine_params* p) { CHECK_HANDLE(h); return set_engine_params(&h->e, p); }
 int fvh_ndt_swap_source_and_target(fvh_ndt* h) {
-  CHECK_HANDLE(h); NDT_NOT_PENDING(h);
+  CHECK_HANDLE(h);
   h->source.swap(h->target);
   std::swap(h->source_vm, h->target_vm);
   h->e.has_corr = false;
   return FVH_OK;
 }
-int fvh_ndt_set_source_cloud(fvh_ndt* h, const float* xyz, int n) { CHECK_HANDLE(h); NDT_NOT_PENDING(h); h->e.has_corr = false; h->source_vm.invalidate(); return upload_cloud(&h->e, h->source, xyz, n, 3, false, false); }
-int fvh_ndt_set_target_cloud(fvh_ndt* h, const float* xyz, int n) { CHECK_HANDLE(h); NDT_NOT_PENDING(h); h->e.has_corr = false; h->target_vm.invalidate(); return upload_cloud(&h->e, h->target, xyz, n, 3, false, false); }
-int fvh_ndt_set_source_cloud_strided(fvh_ndt* h, const float* xyz, int n, int s) { CHECK_HANDLE(h); NDT_NOT_PENDING(h); h->e.has_corr = false; h->source_vm.invalidate(); return upload_cloud(&h->e, h->source, xyz, n, s, false, false); }
-int fvh_ndt_set_target_cloud_strided(fvh_ndt* h, const float* xyz, int n, int s) { CHECK_HANDLE(h); NDT_NOT_PENDING(h); h->e.has_corr = false; h->target_vm.invalidate(); return upload_cloud(&h->e, h->target, xyz, n, s, false, false); }
-int fvh_ndt_set_source_cloud_device(fvh_ndt* h, const float* d, int n, int s) { CHECK_HANDLE(h); NDT_NOT_PENDING(h); h->e.has_corr = false; h->source_vm.invalidate(); return upload_cloud(&h->e, h->source, d, n, s, true, false); }
-int fvh_ndt_set_target_cloud_device(fvh_ndt* h, const float* d, int n, int s) { CHECK_HANDLE(h); NDT_NOT_PENDING(h); h->e.has_corr = false; h->target_vm.invalidate(); return upload_cloud(&h->e, h->target, d, n, s, true, false); }
+static int ndt_set_cloud(fvh_ndt* h, bool is_target, const float* xyz, int n, int stride, bool on_device) {
+  h->e.has_corr = false;
+  (is_target ? h->target_vm : h->source_vm).invalidate();
+  return upload_cloud(&h->e, is_target ? h->target : h->source, xyz, n, stride, on_device, false);
+}
+int fvh_ndt_set_source_cloud(fvh_ndt* h, const float* xyz, int n) { CHECK_HANDLE(h); return ndt_set_cloud(h, false, xyz, n, 3, false); }
+int fvh_ndt_set_target_cloud(fvh_ndt* h, const float* xyz, int n) { CHECK_HANDLE(h); return ndt_set_cloud(h, true, xyz, n, 3, false); }
+int fvh_ndt_set_source_cloud_strided(fvh_ndt* h, const float* xyz, int n, int s) { CHECK_HANDLE(h); return ndt_set_cloud(h, false, xyz, n, s, false); }
+int fvh_ndt_set_target_cloud_strided(fvh_ndt* h, const float* xyz, int n, int s) { CHECK_HANDLE(h); return ndt_set_cloud(h, true, xyz, n, s, false); }
+int fvh_ndt_set_source_cloud_device(fvh_ndt* h, const float* d, int n, int s) { CHECK_HANDLE(h); return ndt_set_cloud(h, false, d, n, s, true); }
+int fvh_ndt_set_target_cloud_device(fvh_ndt* h, const float* d, int n, int s) { CHECK_HANDLE(h); return ndt_set_cloud(h, true, d, n, s, true); }
 int fvh_ndt_create_source_voxelmap(fvh_ndt* h) {
-  CHECK_HANDLE(h); NDT_NOT_PENDING(h);
+  CHECK_HANDLE(h);
   // a swapped-in target map has no compact arrays: rebuild in that case
   if (h->distance_mode == FVH_NDT_P2D) return FVH_OK;  // ndt_cuda.cu:122
   if (h->source_vm.valid && h->source_vm.compact_pts.p) return FVH_OK;
   return build_voxelmap<1>(&h->e, h->source, h->source_vm, h->resolution, true);
 }
 int fvh_ndt_create_target_voxelmap(fvh_ndt* h) {
-  CHECK_HANDLE(h); NDT_NOT_PENDING(h);
+  CHECK_HANDLE(h);
   if (h->target_vm.valid) return FVH_OK;  // ndt_cuda.cu:133-135
   return build_voxelmap<1>(&h->e, h->target, h->target_vm, h->resolution, true);
 }
@@ -1442,7 +1426,7 @@ static int ndt_ready(fvh_ndt* h) {
 // sums (err, H, b) -- the caller adds them over the ranks (fast_gicp_amd/distributed.py: ShardedNDT, host route); with a communicator
 // attached (fvh_ndt_comm_init with the same nranks) align() all-reduces them on the device between the launches of the LM loop.
 int fvh_ndt_set_source_tile(fvh_ndt* h, int rank, int nranks) {
-  CHECK_HANDLE(h); NDT_NOT_PENDING(h);
+  CHECK_HANDLE(h);
   if (nranks < 1 || rank < 0 || rank >= nranks) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "set_source_tile: need 0 <= rank < nranks");
   if (h->e.comm && nranks > 1 && (nranks != h->e.nranks || rank != h->e.rank)) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "set_source_tile: rank / nranks differ from the attached communicator's");
   h->e.tile_rank = nranks > 1 ? rank : 0;
@@ -1451,56 +1435,48 @@ int fvh_ndt_set_source_tile(fvh_ndt* h, int rank, int nranks) {
   return FVH_OK;
 }
 int fvh_ndt_update_correspondences(fvh_ndt* h, const double* T) {
-  CHECK_HANDLE(h); NDT_NOT_PENDING(h);
+  CHECK_HANDLE(h);
   int rc = ndt_ready(h); if (rc) return rc;
-  if (h->distance_mode == FVH_NDT_P2D) return do_update_correspondences<MODE_NDT_P2D>(&h->e, h->cost_source(), h->target_vm, T);
-  return do_update_correspondences<MODE_NDT_D2D>(&h->e, h->cost_source(), h->target_vm, T);
+  return h->by_mode([&](auto m) { return do_update_correspondences<decltype(m)::value>(&h->e, h->cost_source(), h->target_vm, T); });
 }
 int fvh_ndt_compute_error(fvh_ndt* h, const double* T, double* H, double* b, double* err) {
-  CHECK_HANDLE(h); NDT_NOT_PENDING(h);
+  CHECK_HANDLE(h);
   int rc = ndt_ready(h); if (rc) return rc;
-  if (h->distance_mode == FVH_NDT_P2D) return do_compute_error<MODE_NDT_P2D>(&h->e, h->cost_source(), h->target_vm, T, H, b, err, h->rebuild_safe());
-  return do_compute_error<MODE_NDT_D2D>(&h->e, h->cost_source(), h->target_vm, T, H, b, err, h->rebuild_safe());
+  return h->by_mode([&](auto m) { return do_compute_error<decltype(m)::value>(&h->e, h->cost_source(), h->target_vm, T, H, b, err, h->rebuild_safe()); });
 }
 int fvh_ndt_align(fvh_ndt* h, const double* guess, const fvh_lm_params* p, fvh_lm_result* r) {
-  CHECK_HANDLE(h); NDT_NOT_PENDING(h);
+  CHECK_HANDLE(h);
   if (h->e.tile_n > 1 && !h->e.comm) return h->e.fail(FVH_ERR_BAD_STATE, "align: this handle evaluates one tile of the source (fvh_ndt_set_source_tile) and has no communicator: its sums are "
                                                                         "partial -- all-reduce update_correspondences / compute_error over the ranks, or attach one (fvh_ndt_comm_init)");
   int rc = fvh_ndt_create_voxelmaps(h);  // NDTCuda::computeTransformation (ndt_cuda_impl.hpp:76-79)
   if (rc) return rc;
   rc = ndt_ready(h); if (rc) return rc;
-  h->e.crowd_fence = h->next_ready ? h->prep_done : nullptr;  // (a preparation still running on the second stream: a grid that crowds the chip waits for it)
-  if (h->distance_mode == FVH_NDT_P2D) return do_align<MODE_NDT_P2D>(&h->e, h->cost_source(), h->target_vm, guess, p, r, h->rebuild_safe());
-  return do_align<MODE_NDT_D2D>(&h->e, h->cost_source(), h->target_vm, guess, p, r, h->rebuild_safe());
+  h->pipe.arm_crowd_fence(&h->e);
+  return h->by_mode([&](auto m) { return do_align<decltype(m)::value>(&h->e, h->cost_source(), h->target_vm, guess, p, r, h->rebuild_safe()); });
 }
 int fvh_ndt_align_multi(fvh_ndt* h, int k, const double* guesses16, const fvh_lm_params* p, fvh_lm_result* results, int* grid_blocks_out) {
-  CHECK_HANDLE(h); NDT_NOT_PENDING(h);
+  CHECK_HANDLE(h);
   { const int rc = check_multi_args(&h->e, k, guesses16, results); if (rc) return rc; }
   if (h->e.sharded()) return h->e.fail(FVH_ERR_UNSUPPORTED, "align_multi: not on a tiled / multi-GPU handle (fvh_ndt_set_source_tile, fvh_ndt_comm_init)");
   int rc = fvh_ndt_create_voxelmaps(h);
   if (rc) return rc;
   rc = ndt_ready(h); if (rc) return rc;
-  h->e.crowd_fence = h->next_ready ? h->prep_done : nullptr;
-  if (h->distance_mode == FVH_NDT_P2D) return do_align_multi<MODE_NDT_P2D>(&h->e, h->cost_source(), h->target_vm, k, guesses16, p, results, grid_blocks_out, h->rebuild_safe());
-  return do_align_multi<MODE_NDT_D2D>(&h->e, h->cost_source(), h->target_vm, k, guesses16, p, results, grid_blocks_out, h->rebuild_safe());
+  h->pipe.arm_crowd_fence(&h->e);
+  return h->by_mode([&](auto m) { return do_align_multi<decltype(m)::value>(&h->e, h->cost_source(), h->target_vm, k, guesses16, p, results, grid_blocks_out, h->rebuild_safe()); });
 }
 // ---- pipelined frame streams: align = launch + wait; the next source is prepared beside the running LM kernel ----
 int fvh_ndt_align_async(fvh_ndt* h, const double* guess, const fvh_lm_params* p) {
+  if (h && h->in_flight()) return h->e.fail(FVH_ERR_BAD_STATE, "align_async: the previous align_async has not been waited for");
   CHECK_HANDLE(h);
   if (h->e.tile_n > 1) return h->e.fail(FVH_ERR_UNSUPPORTED, "align_async: not on a tiled handle (fvh_ndt_set_source_tile)");
-  if (h->pending.active) return h->e.fail(FVH_ERR_BAD_STATE, "align_async: the previous align_async has not been waited for");
   int rc = fvh_ndt_create_voxelmaps(h);
   if (rc) return rc;
   rc = ndt_ready(h); if (rc) return rc;
-  h->e.crowd_fence = h->next_ready ? h->prep_done : nullptr;
-  if (h->distance_mode == FVH_NDT_P2D) return align_begin<MODE_NDT_P2D>(&h->e, h->pending, h->cost_source(), h->target_vm, guess, p);
-  return align_begin<MODE_NDT_D2D>(&h->e, h->pending, h->cost_source(), h->target_vm, guess, p);
+  return h->by_mode([&](auto m) { return h->pipe.align_async<decltype(m)::value>(&h->e, h->cost_source(), h->target_vm, guess, p); });
 }
 int fvh_ndt_align_wait(fvh_ndt* h, fvh_lm_result* r) {
   CHECK_HANDLE_HOST_ONLY(h);
-  if (!h->pending.active) return h->e.fail(FVH_ERR_BAD_STATE, "align_wait: no align_async in flight");
-  if (h->distance_mode == FVH_NDT_P2D) return align_finish<MODE_NDT_P2D>(&h->e, h->pending, h->cost_source(), h->target_vm, r, h->rebuild_safe());
-  return align_finish<MODE_NDT_D2D>(&h->e, h->pending, h->cost_source(), h->target_vm, r, h->rebuild_safe());
+  return h->by_mode([&](auto m) { return h->pipe.align_wait<decltype(m)::value>(&h->e, h->cost_source(), h->target_vm, r, h->rebuild_safe()); });
 }
 // The output of the voxel-grid filter's last ApproximateVoxelGrid call becomes cloud `c` of this handle WITHOUT a copy: the emit kernel wrote
 // it as float4 too (kernels_downsample.hpp), and that buffer is swapped with the cloud's (the filter gets the cloud's old buffer as its next
@@ -1526,24 +1502,18 @@ static int take_filter_output(Engine* e, fvh_voxelgrid* vg, CloudDev& c, hipStre
 static int ndt_prepare(fvh_ndt* h, const float* d_xyz, int n, int stride, bool on_device, fvh_voxelgrid* from_filter = nullptr) {
   CHECK_HANDLE_HOST_ONLY(h);  // (touches the prepared slot and the second stream only: legal between align_async and align_wait)
   Engine* e = &h->e;
-  hipStream_t ps = e->side_stream();  // null (multi-GPU handle, FVH_SIDE_STREAM=0): in order on the main stream -- correct, nothing overlaps
-  if (ps == nullptr && h->pending.active) return e->fail(FVH_ERR_BAD_STATE, "prepare_source: this handle has no second stream; call it outside align_async .. align_wait");
-  if (!h->prep_done) HIP_OR_FAIL(e, hipEventCreateWithFlags(&h->prep_done, hipEventDisableTiming));
-  { const int rc0 = e->feeder_stream(&ps); if (rc0) return rc0; }  // (the main stream instead, behind an LM grid that crowds the chip: Engine::lm_crowds_chip)
-  h->next_ready = false;
-  h->next_vm.invalidate();
-  int rc = from_filter ? take_filter_output(e, from_filter, h->next_source, ps ? ps : e->stream) : upload_cloud(e, h->next_source, d_xyz, n, stride, on_device, false, ps);
+  Pipeline& pl = h->pipe;
+  hipStream_t ps = nullptr;
+  int rc = pl.begin_prepare(e, &ps);
   if (rc) return rc;
-  {
-    // D2D registers the map itself; in both modes it is the TARGET map of the frame after (swap_source_and_target): built here it is
-    // hidden too. Its table is sized like the maps of the frames before it (the voxel count the last align saw).
-    if (h->next_vm.nv_hint < 0) h->next_vm.nv_hint = std::max(h->source_vm.nv_hint, h->target_vm.nv_hint);
-    rc = build_voxelmap<1>(e, h->next_source, h->next_vm, h->resolution, true, false, ps, false, /*detached=*/true);
-    if (rc) return rc;
-  }
-  HIP_OR_FAIL(e, hipEventRecord(h->prep_done, ps ? ps : e->stream));
-  h->next_ready = true;
-  return FVH_OK;
+  rc = from_filter ? take_filter_output(e, from_filter, pl.next_source, ps ? ps : e->stream) : upload_cloud(e, pl.next_source, d_xyz, n, stride, on_device, false, ps);
+  if (rc) return rc;
+  // D2D registers the map itself; in both modes it is the TARGET map of the frame after (swap_source_and_target): built here it is
+  // hidden too. Its table is sized like the maps of the frames before it (the voxel count the last align saw).
+  if (pl.next_map.nv_hint < 0) pl.next_map.nv_hint = std::max(h->source_vm.nv_hint, h->target_vm.nv_hint);
+  rc = build_voxelmap<1>(e, pl.next_source, pl.next_map, h->resolution, true, false, ps, false, /*detached=*/true);
+  if (rc) return rc;
+  return pl.end_prepare(e, ps);
 }
 int fvh_ndt_prepare_source_device(fvh_ndt* h, const float* d_xyz, int n, int stride) { return ndt_prepare(h, d_xyz, n, stride, true); }
 int fvh_ndt_prepare_source(fvh_ndt* h, const float* xyz, int n, int stride) { return ndt_prepare(h, xyz, n, stride, false); }  // a HOST cloud, consumed before the call returns
@@ -1551,34 +1521,19 @@ int fvh_ndt_prepare_source_from_voxelgrid(fvh_ndt* h, fvh_voxelgrid* vg) {
   if (h && !vg) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "from_voxelgrid: null filter handle");
   return ndt_prepare(h, nullptr, 0, 3, true, vg);
 }
-int fvh_ndt_set_source_cloud_from_voxelgrid(fvh_ndt* h, fvh_voxelgrid* vg) { CHECK_HANDLE(h); NDT_NOT_PENDING(h); h->e.has_corr = false; h->source_vm.invalidate(); return take_filter_output(&h->e, vg, h->source, h->e.stream); }
-int fvh_ndt_set_target_cloud_from_voxelgrid(fvh_ndt* h, fvh_voxelgrid* vg) { CHECK_HANDLE(h); NDT_NOT_PENDING(h); h->e.has_corr = false; h->target_vm.invalidate(); return take_filter_output(&h->e, vg, h->target, h->e.stream); }
+int fvh_ndt_set_source_cloud_from_voxelgrid(fvh_ndt* h, fvh_voxelgrid* vg) { CHECK_HANDLE(h); h->e.has_corr = false; h->source_vm.invalidate(); return take_filter_output(&h->e, vg, h->source, h->e.stream); }
+int fvh_ndt_set_target_cloud_from_voxelgrid(fvh_ndt* h, fvh_voxelgrid* vg) { CHECK_HANDLE(h); h->e.has_corr = false; h->target_vm.invalidate(); return take_filter_output(&h->e, vg, h->target, h->e.stream); }
 int fvh_ndt_adopt_prepared_source(fvh_ndt* h) {
+  if (h && h->in_flight()) return h->e.fail(FVH_ERR_BAD_STATE, "adopt_prepared_source: an align_async is in flight");
   CHECK_HANDLE(h);
-  Engine* e = &h->e;
-  if (h->pending.active) return e->fail(FVH_ERR_BAD_STATE, "adopt_prepared_source: an align_async is in flight");
-  if (!h->next_ready) return e->fail(FVH_ERR_BAD_STATE, "adopt_prepared_source: nothing prepared (fvh_ndt_prepare_source_device)");
-  h->next_ready = false;
-  h->source.swap(h->next_source);
-  std::swap(h->source_vm, h->next_vm);
-  e->has_corr = false;
-  // As a rule the preparation ended while the last align was still running: the host sees that at no cost. Otherwise the main stream waits.
-  if (e->side) {
-    hipError_t q = hipErrorNotReady;
-    for (int spins = 0; spins < 64 && q == hipErrorNotReady; spins++) q = hipEventQuery(h->prep_done);
-    if (q != hipSuccess) {
-      (void)hipGetLastError();
-      HIP_OR_FAIL(e, hipStreamWaitEvent(e->stream, h->prep_done, 0));
-    }
-  }
-  return FVH_OK;
+  return h->pipe.adopt(&h->e, h->source, h->source_vm, "fvh_ndt_prepare_source_device");
 }
-int fvh_ndt_debug_set_voxel_hint(fvh_ndt* h, int which, int num_voxels) { CHECK_HANDLE(h); NDT_NOT_PENDING(h); (which ? h->target_vm : h->source_vm).nv_hint = num_voxels; return FVH_OK; }
-int fvh_ndt_set_lm_trace(fvh_ndt* h, int on) { CHECK_HANDLE(h); NDT_NOT_PENDING(h); h->e.lm_trace_on = on != 0; return FVH_OK; }
-int fvh_ndt_get_lm_trace(fvh_ndt* h, int* n, double* rows6) { CHECK_HANDLE(h); NDT_NOT_PENDING(h); return get_lm_trace(&h->e, n, rows6); }
-int fvh_ndt_fitness_score(fvh_ndt* h, const double* T, double max_range, double* score) { CHECK_HANDLE(h); NDT_NOT_PENDING(h); return do_fitness(&h->e, h->source, h->target, T, max_range, score); }
+int fvh_ndt_debug_set_voxel_hint(fvh_ndt* h, int which, int num_voxels) { CHECK_HANDLE(h); (which ? h->target_vm : h->source_vm).nv_hint = num_voxels; return FVH_OK; }
+int fvh_ndt_set_lm_trace(fvh_ndt* h, int on) { CHECK_HANDLE(h); h->e.lm_trace_on = on != 0; return FVH_OK; }
+int fvh_ndt_get_lm_trace(fvh_ndt* h, int* n, double* rows6) { CHECK_HANDLE(h); return get_lm_trace(&h->e, n, rows6); }
+int fvh_ndt_fitness_score(fvh_ndt* h, const double* T, double max_range, double* score) { CHECK_HANDLE(h); return do_fitness(&h->e, h->source, h->target, T, max_range, score); }
 int fvh_ndt_get_num_voxels(fvh_ndt* h, int which, int* n) {
-  CHECK_HANDLE(h); NDT_NOT_PENDING(h);
+  CHECK_HANDLE(h);
   if (!n) return FVH_ERR_INVALID_ARGUMENT;
   VoxelMapDev& vm = which ? h->target_vm : h->source_vm;
   const Rebuild rb = h->rebuild_safe();
@@ -1587,12 +1542,12 @@ int fvh_ndt_get_num_voxels(fvh_ndt* h, int which, int* n) {
   return FVH_OK;
 }
 int fvh_ndt_get_voxels(fvh_ndt* h, int which, int* coords3, int* num_points, float* means3, float* covs9) {
-  CHECK_HANDLE(h); NDT_NOT_PENDING(h);
+  CHECK_HANDLE(h);
   const Rebuild rb = h->rebuild_safe();
   return get_voxels_host(&h->e, which ? h->target_vm : h->source_vm, coords3, num_points, means3, covs9, &rb);
 }
 int fvh_ndt_get_num_correspondences(fvh_ndt* h, int* n) {
-  CHECK_HANDLE(h); NDT_NOT_PENDING(h);
+  CHECK_HANDLE(h);
   if (h->e.tile_n > 1) return h->e.fail(FVH_ERR_UNSUPPORTED, "correspondence getters: not on a tiled handle (only its tile's rows of the list exist)");
   if (!n) return FVH_ERR_INVALID_ARGUMENT;
   std::vector<int> corr;
@@ -1611,7 +1566,7 @@ int fvh_ndt_get_num_correspondences(fvh_ndt* h, int* n) {
 }
 // offset-major then source element, invalid pairs removed (ndt_cuda.cu:142-161 builds the list with the functor of find_voxel_correspondences.cu:84-111)
 int fvh_ndt_get_voxel_correspondences(fvh_ndt* h, int* pairs) {
-  CHECK_HANDLE(h); NDT_NOT_PENDING(h);
+  CHECK_HANDLE(h);
   if (h->e.tile_n > 1) return h->e.fail(FVH_ERR_UNSUPPORTED, "correspondence getters: not on a tiled handle (only its tile's rows of the list exist)");
   if (!pairs) return FVH_ERR_INVALID_ARGUMENT;
   const Rebuild rb = h->rebuild_safe();
@@ -1640,16 +1595,16 @@ int fvh_ndt_get_voxel_correspondences(fvh_ndt* h, int* pairs) {
     }
   return FVH_OK;
 }
-int fvh_ndt_profile_enable(fvh_ndt* h, int on) { CHECK_HANDLE(h); NDT_NOT_PENDING(h); h->e.prof.on = on != 0; h->e.prof.cost_only = on == 2; return FVH_OK; }
-int fvh_ndt_profile_reset(fvh_ndt* h) { CHECK_HANDLE(h); NDT_NOT_PENDING(h); HIP_OR_FAIL(&h->e, hipStreamSynchronize(h->e.stream)); h->e.prof.reset(); return FVH_OK; }
-int fvh_ndt_profile_get(fvh_ndt* h, const char* cls, double* ms, int* n) { CHECK_HANDLE(h); NDT_NOT_PENDING(h); return profile_get(&h->e, cls, ms, n); }
-int fvh_ndt_synchronize(fvh_ndt* h) { CHECK_HANDLE(h); NDT_NOT_PENDING(h); HIP_OR_FAIL(&h->e, hipStreamSynchronize(h->e.stream)); h->e.gang_clear(); return FVH_OK; }
+int fvh_ndt_profile_enable(fvh_ndt* h, int on) { CHECK_HANDLE(h); h->e.prof.on = on != 0; h->e.prof.cost_only = on == 2; return FVH_OK; }
+int fvh_ndt_profile_reset(fvh_ndt* h) { CHECK_HANDLE(h); HIP_OR_FAIL(&h->e, hipStreamSynchronize(h->e.stream)); h->e.prof.reset(); return FVH_OK; }
+int fvh_ndt_profile_get(fvh_ndt* h, const char* cls, double* ms, int* n) { CHECK_HANDLE(h); return profile_get(&h->e, cls, ms, n); }
+int fvh_ndt_synchronize(fvh_ndt* h) { CHECK_HANDLE(h); HIP_OR_FAIL(&h->e, hipStreamSynchronize(h->e.stream)); h->e.gang_clear(); return FVH_OK; }
 int fvh_ndt_comm_init(fvh_ndt* h, const void* id, int nranks, int rank) {
-  CHECK_HANDLE(h); NDT_NOT_PENDING(h);
+  CHECK_HANDLE(h);
   if (h->e.tile_n > 1 && (h->e.tile_n != nranks || h->e.tile_rank != rank)) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "comm_init: rank / nranks differ from fvh_ndt_set_source_tile's");
   return comm_init(&h->e, id, nranks, rank);
 }
-int fvh_ndt_comm_destroy(fvh_ndt* h) { CHECK_HANDLE(h); NDT_NOT_PENDING(h); if (h->e.comm) { g_rccl.CommDestroy(h->e.comm); h->e.comm = nullptr; } h->e.nranks = 1; h->e.rank = 0; return FVH_OK; }
+int fvh_ndt_comm_destroy(fvh_ndt* h) { CHECK_HANDLE(h); if (h->e.comm) { g_rccl.CommDestroy(h->e.comm); h->e.comm = nullptr; } h->e.nranks = 1; h->e.rank = 0; return FVH_OK; }
 
 // ---- voxel-grid downsampling ----
 int fvh_voxelgrid_create(int device, fvh_voxelgrid** out) {
@@ -1696,42 +1651,20 @@ int fvh_voxelgrid_filter_device(fvh_voxelgrid* h, int method, const float* d_xyz
 // from the scan kernel, one kernel before the centroids exist): set_*_cloud_device + align are queued behind the emit kernel
 // while it runs -- no idle stream between the filter and the registration. The output buffer is complete in stream order only:
 // without a shared stream the call is the synchronous one.
-int fvh_voxelgrid_share_stream_with_ndt(fvh_voxelgrid* h, fvh_ndt* other) {
-  CHECK_HANDLE(h);
-  HIP_OR_FAIL(&h->e, hipStreamSynchronize(h->e.stream));
-  if (other && other->e.device != h->e.device) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "share_stream: the two handles live on different devices");
-  h->e.stream = other ? other->e.stream : h->e.owned_stream;  // null: back to the filter's own stream
-  h->e.stream_owner = other ? &other->e : nullptr;
+// `other` null (share_stream only): back to the filter's own stream
+static int share_stream(Engine* self, Engine* other, bool prepare_stream) {
+  HIP_OR_FAIL(self, hipStreamSynchronize(self->stream));
+  if (prepare_stream && !other) return self->fail(FVH_ERR_INVALID_ARGUMENT, "share_prepare_stream: null registration handle");
+  if (other && other->device != self->device) return self->fail(FVH_ERR_INVALID_ARGUMENT, "share_stream: the two handles live on different devices");
+  hipStream_t const ps = prepare_stream ? other->side_stream() : nullptr;
+  self->stream = ps ? ps : (other ? other->stream : self->owned_stream);
+  self->stream_owner = other;
   return FVH_OK;
 }
-int fvh_voxelgrid_share_prepare_stream_with_ndt(fvh_voxelgrid* h, fvh_ndt* other) {
-  CHECK_HANDLE(h);
-  HIP_OR_FAIL(&h->e, hipStreamSynchronize(h->e.stream));
-  if (!other) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "share_prepare_stream: null registration handle");
-  if (other->e.device != h->e.device) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "share_stream: the two handles live on different devices");
-  hipStream_t ps = other->e.side_stream();
-  h->e.stream = ps ? ps : other->e.stream;
-  h->e.stream_owner = &other->e;
-  return FVH_OK;
-}
-int fvh_voxelgrid_share_prepare_stream_with_vgicp(fvh_voxelgrid* h, fvh_vgicp* other) {
-  CHECK_HANDLE(h);
-  HIP_OR_FAIL(&h->e, hipStreamSynchronize(h->e.stream));
-  if (!other) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "share_prepare_stream: null registration handle");
-  if (other->e.device != h->e.device) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "share_stream: the two handles live on different devices");
-  hipStream_t ps = other->e.side_stream();
-  h->e.stream = ps ? ps : other->e.stream;
-  h->e.stream_owner = &other->e;
-  return FVH_OK;
-}
-int fvh_voxelgrid_share_stream_with_vgicp(fvh_voxelgrid* h, fvh_vgicp* other) {
-  CHECK_HANDLE(h);
-  HIP_OR_FAIL(&h->e, hipStreamSynchronize(h->e.stream));
-  if (other && other->e.device != h->e.device) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "share_stream: the two handles live on different devices");
-  h->e.stream = other ? other->e.stream : h->e.owned_stream;
-  h->e.stream_owner = other ? &other->e : nullptr;
-  return FVH_OK;
-}
+int fvh_voxelgrid_share_stream_with_ndt(fvh_voxelgrid* h, fvh_ndt* other) { CHECK_HANDLE(h); return share_stream(&h->e, other ? &other->e : nullptr, false); }
+int fvh_voxelgrid_share_stream_with_vgicp(fvh_voxelgrid* h, fvh_vgicp* other) { CHECK_HANDLE(h); return share_stream(&h->e, other ? &other->e : nullptr, false); }
+int fvh_voxelgrid_share_prepare_stream_with_ndt(fvh_voxelgrid* h, fvh_ndt* other) { CHECK_HANDLE(h); return share_stream(&h->e, other ? &other->e : nullptr, true); }
+int fvh_voxelgrid_share_prepare_stream_with_vgicp(fvh_voxelgrid* h, fvh_vgicp* other) { CHECK_HANDLE(h); return share_stream(&h->e, other ? &other->e : nullptr, true); }
 int fvh_voxelgrid_filter_device_async(fvh_voxelgrid* h, int method, const float* d_xyz, int n, int stride, float leaf, int* out_n) {
   CHECK_HANDLE(h);
   const bool shared = h->e.stream != h->e.owned_stream;

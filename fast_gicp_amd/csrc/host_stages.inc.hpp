@@ -1152,6 +1152,74 @@ int do_align(Engine* e, const CostSource& src, VoxelMapDev& vm, const double* gu
   return align_finish<MODE>(e, c, src, vm, result, rebuild_safe);
 }
 
+// The pipelined half of a registration handle (fvh_{vgicp,ndt}_prepare_source* / _adopt_prepared_source / _align_async / _align_wait): the NEXT
+// source cloud and its voxel map are prepared in this slot on the handle's second stream (Engine::side) while the LM kernel of the current
+// pair, launched by align_async(), runs on the main one. Both handle types hold one. What a preparation consists of -- the stages between
+// begin_prepare() and end_prepare() -- is the handle's business.
+struct Pipeline {
+  CloudDev next_source;
+  VoxelMapDev next_map;
+  bool next_ready = false;         // a preparation was queued (`prep_done`: the event behind it) and has not been adopted yet
+  hipEvent_t prep_done = nullptr;
+  AlignCtx pending;                // align_async() .. align_wait()
+  // an align_async has not been waited for: the handle's clouds, maps and LM state belong to the running kernel (CHECK_HANDLE refuses on it)
+  bool in_flight() const { return pending.active; }
+  void invalidate() { next_map.invalidate(); next_ready = false; }
+  // before every align launch: a grid that crowds the chip waits for a preparation that may still run on the second stream (Engine::lm_crowds_chip)
+  void arm_crowd_fence(Engine* e) const { e->crowd_fence = next_ready ? prep_done : nullptr; }
+  // Head of a preparation: *ps = the stream to queue it on -- the second one, or null: in order on the main stream (the handle has no second
+  // stream -- FVH_SIDE_STREAM=0, multi-GPU -- which is correct, nothing overlaps; or an LM grid that crowds the chip is in flight). Empties the slot.
+  int begin_prepare(Engine* e, hipStream_t* ps) {
+    if (e->side_stream() == nullptr && in_flight()) return e->fail(FVH_ERR_BAD_STATE, "prepare_source: this handle has no second stream; call it outside align_async .. align_wait");
+    if (!prep_done) HIP_OR_FAIL(e, hipEventCreateWithFlags(&prep_done, hipEventDisableTiming));
+    // a target-map build that swap_source_and_target() deferred goes first (same stream: in order)
+    if (e->deferred) { const int rc = e->after_source_chain_call(FVH_OK); if (rc) return rc; }
+    { const int rc = e->feeder_stream(ps); if (rc) return rc; }
+    invalidate();
+    return FVH_OK;
+  }
+  int end_prepare(Engine* e, hipStream_t ps) {
+    HIP_OR_FAIL(e, hipEventRecord(prep_done, ps ? ps : e->stream));
+    next_ready = true;
+    return FVH_OK;
+  }
+  // the prepared cloud and its map change places with the handle's source and the map that goes with it
+  int adopt(Engine* e, CloudDev& source, VoxelMapDev& source_map, const char* prepare_fn) {
+    if (!next_ready) return e->fail(FVH_ERR_BAD_STATE, std::string("adopt_prepared_source: nothing prepared (") + prepare_fn + ")");
+    next_ready = false;
+    source.swap(next_source);
+    std::swap(source_map, next_map);
+    e->has_corr = false;
+    // As a rule the preparation ended while the last align was still running: the host sees that at no cost. Otherwise the main stream waits.
+    if (e->side) {
+      hipError_t q = hipErrorNotReady;
+      for (int spins = 0; spins < 64 && q == hipErrorNotReady; spins++) q = hipEventQuery(prep_done);
+      if (q != hipSuccess) {
+        (void)hipGetLastError();
+        HIP_OR_FAIL(e, hipStreamWaitEvent(e->stream, prep_done, 0));
+      }
+    }
+    return FVH_OK;
+  }
+  template <int MODE>
+  int align_async(Engine* e, const CostSource& src, VoxelMapDev& vm, const double* guess16, const fvh_lm_params* params) {
+    arm_crowd_fence(e);
+    return align_begin<MODE>(e, pending, src, vm, guess16, params);
+  }
+  // A refused call changes nothing: the align stays in flight (and its slots granted) until a call with a result to fill collects it
+  template <int MODE>
+  int align_wait(Engine* e, const CostSource& src, VoxelMapDev& vm, fvh_lm_result* result, const Rebuild& rebuild_safe) {
+    if (!result) return e->fail(FVH_ERR_INVALID_ARGUMENT, "align_wait: null result");
+    if (!in_flight()) return e->fail(FVH_ERR_BAD_STATE, "align_wait: no align_async in flight");
+    return align_finish<MODE>(e, pending, src, vm, result, rebuild_safe);
+  }
+  void release() {  // (destroy: both streams have drained)
+    if (pending.active) { pending.release_slots(); pending.active = false; }
+    next_source.release(); next_map.release();
+    if (prep_done) { (void)hipEventDestroy(prep_done); prep_done = nullptr; }
+  }
+};
+
 // ---- align_multi: K independent LM problems on the same prepared clouds (K initial guesses) in one launch of lm_gang_kernel ----
 // The plan is the one a single align makes (nb_h workgroups, default_groups(nb_h) groups), shrunk -- when the K gangs do not fit the co-resident
 // slots together -- to what the pool grants (nb_h >= 8), else the K gangs take the multi-launch route (one launch per LM transition over all of

@@ -344,3 +344,226 @@ def test_a_preparation_never_runs_beside_an_lm_grid_that_crowds_the_chip():
         nxt = 1 - nxt
     assert c.debug_persist_aborts() == 0
     c.close()
+
+
+# ---- align_async .. align_wait: one guard for both handle types ----
+_KINDS = ["vgicp", "ndt_d2d", "ndt_p2d"]
+_BAD_STATE, _INVALID_ARGUMENT = 2, 1
+_RESULT_KEYS = ("T", "H", "final_error", "nr_iterations", "num_linearize", "num_error_evals")
+
+
+def _small_core(kind, tgt, src):
+    """A handle ready to align the small pair (a few workgroups), without a second stream."""
+    from fast_gicp_amd import capi
+    if kind == "vgicp":
+        c = capi.VGICPCore(0)
+        c.set_resolution(1.0); c.set_neighbor_search_method(capi.DIRECT7)
+        c.set_engine_params(side_stream=0)
+        c.set_target_cloud(tgt); c.find_target_neighbors(20); c.calculate_target_covariances(); c.create_target_voxelmap()
+        c.set_source_cloud(src); c.find_source_neighbors(20); c.calculate_source_covariances()
+    else:
+        c = capi.NDTCore(0)
+        c.set_distance_mode(capi.NDT_D2D if kind == "ndt_d2d" else capi.NDT_P2D); c.set_neighbor_search_method(capi.DIRECT7); c.set_resolution(1.0)
+        c.set_engine_params(side_stream=0)
+        c.set_target_cloud(tgt); c.set_source_cloud(src)
+    return c
+
+
+@pytest.fixture(scope="module")
+def small_pair():
+    tgt, src, _ = util.synthetic_pair(700, 700, extent=20.0)
+    return tgt, src
+
+
+@pytest.fixture(scope="module")
+def sync_results(small_pair):
+    """align() of the small pair on a handle of its own, per handle kind: what the first align_async / align_wait of a fresh handle must return."""
+    out = {}
+    for kind in _KINDS:
+        c = _small_core(kind, *small_pair)
+        r = c.align()
+        out[kind] = {k: np.copy(r[k]) for k in _RESULT_KEYS}
+        c.close()
+    return out
+
+
+def _assert_same_result(r, ref, kind):
+    for k in _RESULT_KEYS:
+        print(kind, k, "async", np.asarray(r[k]).ravel()[:4], "sync", np.asarray(ref[k]).ravel()[:4])
+    for k in _RESULT_KEYS:
+        assert np.array_equal(r[k], ref[k], equal_nan=True), (kind, k, r[k], ref[k])  # (equal_nan: a NaN the synchronous align returns must come back as a NaN)
+
+
+def _in_flight_calls(kind, c, a):
+    """name -> (what must happen between align_async and align_wait, the call): every public method of the handle's class.
+    "generic": refused by the guard of CHECK_HANDLE, "specific": refused with a text of the call's own, "legal": succeeds.
+    (This handle has no second stream: prepare_source* are refused while the align is pending, with their own text.)"""
+    G, S, L = "generic", "specific", "legal"
+    eye = np.eye(4)
+    t = {
+        # ---- shared ----
+        "get_engine_params": (L, lambda: c.get_engine_params()),
+        "set_engine_params": (G, lambda: c.set_engine_params(side_stream=0)),
+        "set_neighbor_search_method": (G, lambda: c.set_neighbor_search_method(1)),
+        "set_precision": (G, lambda: c.set_precision(0)),
+        "swap_source_and_target": (G, lambda: c.swap_source_and_target()),
+        "set_source_cloud": (G, lambda: c.set_source_cloud(a.src)),
+        "set_target_cloud": (G, lambda: c.set_target_cloud(a.src)),
+        "set_source_cloud_device": (G, lambda: c.set_source_cloud_device(a.d_src.data_ptr(), len(a.src), 3)),
+        "set_target_cloud_device": (G, lambda: c.set_target_cloud_device(a.d_src.data_ptr(), len(a.src), 3)),
+        "update_correspondences": (G, lambda: c.update_correspondences(eye)),
+        "compute_error": (G, lambda: c.compute_error(eye)),
+        "linearize": (G, lambda: c.linearize(eye)),
+        "align": (G, lambda: c.align()),
+        "align_multi": (G, lambda: c.align_multi(eye[None])),
+        "fitness_score": (G, lambda: c.fitness_score(eye)),
+        "synchronize": (G, lambda: c.synchronize()),
+        "set_lm_trace": (G, lambda: c.set_lm_trace(False)),
+        "get_lm_trace": (G, lambda: c.get_lm_trace()),
+        "profile_reset": (G, lambda: c.profile_reset()),
+        "profile_get": (G, lambda: c.profile_get("cost")),
+        "comm_init": (G, lambda: c.comm_init(bytes(128), 1, 0)),
+        "comm_destroy": (G, lambda: c.comm_destroy()),
+        "get_num_correspondences": (G, lambda: c.get_num_correspondences()),
+        "get_voxel_correspondences": (G, lambda: c.get_voxel_correspondences()),
+        "adopt_prepared_source": (G if kind == "vgicp" else S, lambda: c.adopt_prepared_source()),
+        "align_async": (G if kind == "vgicp" else S, lambda: c.align_async()),
+    }
+    if kind == "vgicp":
+        covs = np.tile(np.eye(3), (len(a.src), 1, 1))
+        nbrs = np.zeros((len(a.src), 20), np.int32)
+        t.update({
+            "set_resolution": (L, lambda: c.set_resolution(1.0)),
+            "set_kernel_params": (L, lambda: c.set_kernel_params(0.25, 3.0)),
+            "profile_enable": (L, lambda: c.profile_enable(False)),
+            "num_points": (L, lambda: c.num_points("source")),
+            "prepare_source": (S, lambda: c.prepare_source(a.src)),
+            "prepare_source_device": (S, lambda: c.prepare_source_device(a.d_src.data_ptr(), len(a.src), 3)),
+            "peer_export": (G, lambda: c.peer_export(64)),
+            "peer_attach": (G, lambda: c.peer_attach(1, 0, 1, [bytes(64)])),
+            "peer_detach": (G, lambda: c.peer_detach()),
+            "peer_selfcheck": (G, lambda: c.peer_selfcheck(0.1)),
+            "set_target_map_sharding": (G, lambda: c.set_target_map_sharding(False)),
+            "debug_spatial_order": (G, lambda: c.debug_spatial_order("source")),
+            "debug_live_map_voxels": (G, lambda: c.debug_live_map_voxels()),
+            "debug_map_shard": (G, lambda: c.debug_map_shard()),
+            "set_voxel_accumulation_mode": (G, lambda: c.set_voxel_accumulation_mode(0)),
+            "set_source_neighbors": (G, lambda: c.set_source_neighbors(20, nbrs)),
+            "set_target_neighbors": (G, lambda: c.set_target_neighbors(20, nbrs)),
+            "find_source_neighbors": (G, lambda: c.find_source_neighbors(20)),
+            "find_target_neighbors": (G, lambda: c.find_target_neighbors(20)),
+            "calculate_source_covariances": (G, lambda: c.calculate_source_covariances()),
+            "calculate_target_covariances": (G, lambda: c.calculate_target_covariances()),
+            "calculate_source_covariances_rbf": (G, lambda: c.calculate_source_covariances_rbf()),
+            "calculate_target_covariances_rbf": (G, lambda: c.calculate_target_covariances_rbf()),
+            "set_source_covariances": (G, lambda: c.set_source_covariances(covs)),
+            "set_target_covariances": (G, lambda: c.set_target_covariances(covs)),
+            "get_neighbors": (G, lambda: c.get_neighbors("source")),
+            "get_covariances": (G, lambda: c.get_covariances("source")),
+            "create_target_voxelmap": (G, lambda: c.create_target_voxelmap()),
+            "map_begin": (G, lambda: c.map_begin()),
+            "map_insert_source": (G, lambda: c.map_insert_source()),
+            "map_insert_cloud": (G, lambda: c.map_insert_cloud(a.src, covs)),
+            "map_prune": (G, lambda: c.map_prune(max_age=1)),
+            "map_info": (G, lambda: c.map_info()),
+            "map_export": (G, lambda: c.map_export()),
+            "map_import": (G, lambda: c.map_import(a.snapshot)),
+            "map_merge_from": (G, lambda: c.map_merge_from(a.other)),
+            "map_save": (G, lambda: c.map_save(a.map_file + ".out")),
+            "map_load": (G, lambda: c.map_load(a.map_file)),
+            "get_voxelmap": (G, lambda: c.get_voxelmap()),
+            "debug_set_voxel_hint": (G, lambda: c.debug_set_voxel_hint(1000)),
+            "gicp_set_max_correspondence_distance": (G, lambda: c.gicp_set_max_correspondence_distance(1.0)),
+            "gicp_swap_source_and_target": (G, lambda: c.gicp_swap_source_and_target()),
+            "gicp_update_correspondences": (G, lambda: c.gicp_update_correspondences(eye)),
+            "gicp_compute_error": (G, lambda: c.gicp_compute_error(eye)),
+            "gicp_linearize": (G, lambda: c.gicp_linearize(eye)),
+            "gicp_align": (G, lambda: c.gicp_align()),
+            "gicp_get_correspondences": (G, lambda: c.gicp_get_correspondences()),
+            "debug_persist_aborts": (G, lambda: c.debug_persist_aborts()),
+            "debug_persist_grid": (G, lambda: c.debug_persist_grid()),
+            "debug_table_capacity": (G, lambda: c.debug_table_capacity()),
+            "debug_skipped_points": (G, lambda: c.debug_skipped_points()),
+        })
+    else:
+        t.update({
+            "set_resolution": (G, lambda: c.set_resolution(1.0)),
+            "profile_enable": (G, lambda: c.profile_enable(False)),
+            "prepare_source": (S, lambda: c.prepare_source(a.src)),
+            "prepare_source_device": (S, lambda: c.prepare_source_device(a.d_src.data_ptr(), len(a.src), 3)),
+            "prepare_source_from_voxelgrid": (S, lambda: c.prepare_source_from_voxelgrid(a.vg)),
+            "set_source_cloud_from_voxelgrid": (G, lambda: c.set_source_cloud_from_voxelgrid(a.vg)),
+            "set_target_cloud_from_voxelgrid": (G, lambda: c.set_target_cloud_from_voxelgrid(a.vg)),
+            "set_distance_mode": (G, lambda: c.set_distance_mode(1)),
+            "create_voxelmaps": (G, lambda: c.create_voxelmaps()),
+            "create_target_voxelmap": (G, lambda: c.create_target_voxelmap()),
+            "create_source_voxelmap": (G, lambda: c.create_source_voxelmap()),
+            "debug_set_voxel_hint": (G, lambda: c.debug_set_voxel_hint("source", 1000)),
+            "set_source_tile": (G, lambda: c.set_source_tile(0, 1)),
+            "get_num_voxels": (G, lambda: c.get_num_voxels("target")),
+            "get_voxelmap": (G, lambda: c.get_voxelmap("target")),
+        })
+    return t
+
+
+_NOT_IN_THE_TABLE = {"close": "destroys the handle (legal at any time): called last", "align_wait": "ends the state under test: called last"}
+
+
+@pytest.mark.parametrize("kind", _KINDS)
+def test_in_flight_guard_is_the_same_on_both_handle_types(kind, small_pair, sync_results, tmp_path):
+    """Between align_async and align_wait every entry point that touches the handle's clouds, maps or LM state is refused with BAD_STATE by
+    ONE guard, whose text names the handle type's own align_wait; the few calls that stay legal succeed; and none of it disturbs the
+    running align: align_wait returns what a synchronous align() of the same pair returns, bit for bit."""
+    import re
+    import types
+    import torch
+    from fast_gicp_amd import capi
+    tgt, src = small_pair
+    a = types.SimpleNamespace(src=src, d_src=torch.from_numpy(src).to(torch.device("cuda", 0)).contiguous(), vg=capi.VoxelGrid(0), other=capi.VGICPCore(0),
+                              snapshot=dict(resolution=1.0, mode=0, num_inserts=0, num_points=0, coords=np.zeros((0, 3), np.int32), sums=np.zeros((0, 10))),
+                              map_file=str(tmp_path / "empty.fvhmap"))
+    capi.write_map_file(a.map_file, a.snapshot)
+    c = _small_core(kind, tgt, src)
+    calls = _in_flight_calls(kind, c, a)
+    public = {m for m in dir(type(c)) if not m.startswith("_")}
+    assert set(calls) == public - set(_NOT_IN_THE_TABLE), (sorted(public - set(_NOT_IN_THE_TABLE) - set(calls)), sorted(set(calls) - public))
+    wait_fn = "fvh_vgicp_align_wait" if kind == "vgicp" else "fvh_ndt_align_wait"
+    c.align_async()
+    for name, (expect, call) in sorted(calls.items()):
+        if expect == "legal":
+            call()
+            continue
+        with pytest.raises(capi.FvhError) as ei:
+            call()
+        msg = str(ei.value)
+        assert re.search(r"status (\d+)", msg).group(1) == str(_BAD_STATE), (name, msg)
+        assert "align_async" in msg, (name, msg)
+        if expect == "generic":
+            assert wait_fn in msg, (name, msg)
+    if kind == "vgicp":
+        assert c.num_points("source") == len(src)
+        with pytest.raises(capi.FvhError, match="align_async is in flight on the other handle"):
+            a.other.map_merge_from(c)  # (the other handle's guard)
+    _assert_same_result(c.align_wait(), sync_results[kind], kind)
+    assert capi.debug_slot_pool(0)[:2] == (0, 0)
+    c.swap_source_and_target()  # the handle is the caller's again
+    c.close(); a.other.close(); a.vg.close()
+
+
+@pytest.mark.parametrize("kind", _KINDS)
+def test_align_wait_with_null_result_keeps_the_align_collectable(kind, small_pair, sync_results):
+    """fvh_*_align_wait(h, NULL) is refused with INVALID_ARGUMENT and changes nothing: the align stays in flight (setters are still refused,
+    the slot pool still shows its grant) and a following align_wait with a result to fill returns the synchronous align()'s, bit for bit."""
+    from fast_gicp_amd import capi
+    tgt, src = small_pair
+    c = _small_core(kind, tgt, src)
+    c.align_async()
+    granted = capi.debug_slot_pool(0)
+    assert granted[0] > 0 and granted[1] == 1, granted  # (the persistent route: its workgroup slots are held until the result is collected)
+    assert getattr(c._lib, c._prefix + "align_wait")(c.h, None) == _INVALID_ARGUMENT
+    with pytest.raises(capi.FvhError, match="align_async is in flight"):
+        c.set_source_cloud(src)
+    assert capi.debug_slot_pool(0) == granted
+    _assert_same_result(c.align_wait(), sync_results[kind], kind)
+    assert capi.debug_slot_pool(0)[:2] == (0, 0)
+    c.close()
