@@ -435,6 +435,9 @@ inline void pose_to_colmajor16(const PoseD& p, double* T) {
   for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) T[j * 4 + i] = p.r[i * 3 + j]; T[12 + i] = p.t[i]; T[i * 4 + 3] = 0.0; }
   T[15] = 1.0;
 }
+inline void pose_to_rowmajor12f(const double* T16, float* T12) {  // what the search kernels read: trans.cast<float>(), 3 x 4
+  for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) T12[i * 4 + j] = (float)T16[j * 4 + i]; T12[i * 4 + 3] = (float)T16[12 + i]; }
+}
 
 #include "host_stages.inc.hpp"
 #include "host_incmap.inc.hpp"
@@ -1148,7 +1151,7 @@ int fvh_debug_lm_replay(int device, const double* guess16, const fvh_lm_params* 
   ok = ok && hipMalloc(reinterpret_cast<void**>(&st), sizeof(LmState)) == hipSuccess && hipMalloc(reinterpret_cast<void**>(&ticket), 64) == hipSuccess;
   ok = ok && hipMemsetAsync(st, 0, sizeof(LmState), stream) == hipSuccess && hipMemsetAsync(ticket, 0, 64, stream) == hipSuccess;
   if (ok) {
-    lm_init_kernel<<<1, 64, 0, stream>>>(st, pose_from_colmajor16(guess16), p.rotation_epsilon, p.transformation_epsilon, p.lm_init_lambda_factor, p.max_iterations, p.lm_max_iterations, ticket, p.optimizer != 0 ? 1 : 0);
+    launch_lm_init(stream, st, pose_from_colmajor16(guess16), p, ticket);
     ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(h, st, sizeof(LmState), hipMemcpyDeviceToHost, stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
   }
   if (ok && h->phase == PH_DONE) lm_replay_row(*h, rows);  // max_iterations <= 0: no step to take, row 0 is the initial state
@@ -1156,7 +1159,7 @@ int fvh_debug_lm_replay(int device, const double* guess16, const fvh_lm_params* 
   while (ok && h->phase != PH_DONE && taken < n_steps) {
     ok = hipMemcpyAsync(st->sums, sums + (size_t)PART_STRIDE * taken, sizeof(double) * PART_STRIDE, hipMemcpyHostToDevice, stream) == hipSuccess;
     if (!ok) break;
-    if (p.optimizer) lm_update_kernel<true><<<1, 64, 0, stream>>>(st); else lm_update_kernel<false><<<1, 64, 0, stream>>>(st);
+    launch_lm_update(stream, st, p);
     ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(h, st, sizeof(LmState), hipMemcpyDeviceToHost, stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
     if (!ok) break;
     lm_replay_row(*h, rows + (size_t)FVH_LM_REPLAY_ROW * taken);

@@ -26,7 +26,9 @@ int gicp_prepare(Engine* e, CloudDev& src, CloudDev& tgt, VoxelMapDev& records, 
 // lsq_registration_impl.hpp:53-168). Per LM transition TWO launches and no host round trip: nn1_corr_kernel searches the
 // nearest target point of every source point at the pose the LM state on the device says comes next (x0 for a linearisation,
 // the trial pose for the fused trial + speculative linearisation) and the cost kernel consumes those ids (external_find).
-// Round 1 drove this from the host: two blocking round trips per iteration.
+// Round 1 drove this from the host: two blocking round trips per iteration. The loop itself -- batches of steps, the readback behind each,
+// the budget, what the handle holds afterwards -- is the driver align() takes on its multi-launch route (host_stages.inc.hpp:
+// run_transitions, leave_handle, fill_result); this file's part is what one step queues. There is no persistent route here.
 int gicp_align(Engine* e, CloudDev& src, CloudDev& tgt, VoxelMapDev& records, const CostSource& cs, double max_dist, const double* guess16, const fvh_lm_params* params,
                fvh_lm_result* result) {
   if (!guess16 || !result) return e->fail(FVH_ERR_INVALID_ARGUMENT, "gicp_align: null argument");
@@ -35,57 +37,37 @@ int gicp_align(Engine* e, CloudDev& src, CloudDev& tgt, VoxelMapDev& records, co
   fvh_lm_params p;
   if (params) p = *params; else fvh_default_lm_params(&p);
   e->align_optimizer = p.optimizer != 0 ? 1 : 0;
-  LmState* st = e->state.as<LmState>();
+  const LmBuffers buf = single_buffers(e);
+  LmState* const st = buf.dev;
   const PoseD guess = pose_from_colmajor16(guess16);
   float T12[12];
-  for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) T12[i * 4 + j] = (float)guess16[j * 4 + i]; T12[i * 4 + 3] = (float)guess16[12 + i]; }
+  pose_to_rowmajor12f(guess16, T12);
   char* base = (char*)e->fit.p;
   HIP_OR_FAIL(e, hipMemcpyAsync(base + 16, T12, sizeof(T12), hipMemcpyHostToDevice, e->stream));
   const double thr = std::min(max_dist, 1.8446743e19);
   const LmLink link{&st->phase, &st->corr_cur, st->x0.r, st->xi.r, (size_t)src.n};
-  const long long budget = (long long)std::max(p.max_iterations, 0) * (1 + (long long)std::max(p.lm_max_iterations, 0)) + 1;
+  const long long budget = lm_budget(p);
   if (e->lm_trace_on) HIP_OR_FAIL(e, e->lm_trace.ensure(sizeof(double) * 6 * (size_t)std::max<long long>(budget, 1)));
   e->lm_trace_rows = 0;
-  LmState* h = reinterpret_cast<LmState*>(e->pinned);
-  if (p.max_iterations <= 0) {
-    lm_init_kernel<<<1, 64, 0, e->stream>>>(st, guess, p.rotation_epsilon, p.transformation_epsilon, p.lm_init_lambda_factor, p.max_iterations, p.lm_max_iterations, e->ticket.as<unsigned>(), p.optimizer != 0 ? 1 : 0);
+  const bool degenerate = p.max_iterations <= 0;
+  if (degenerate) {
+    launch_lm_init(e->stream, st, guess, p, e->ticket.as<unsigned>());
     HIP_OR_FAIL(e, hipGetLastError());
   }
   long long launched = 0;
-  int batch = e->last_steps > 0 ? std::max(e->last_steps, e->prev_steps) + 1 : 8;
-  for (;;) {
-    for (int s = 0; s < batch && p.max_iterations > 0; s++) {
-      const bool first = (launched == 0 && s == 0);
-      {
-        ProfScope ps(e, "gicp_nn");
-        launch_nn1(e, src, tgt, reinterpret_cast<const float*>(base + 16), thr * thr, e->corr.as<int>(), nullptr, first ? LmLink{nullptr, nullptr, nullptr, nullptr, 0} : link);
-      }
-      rc = launch_cost<MODE_VGICP>(e, cs, records, -1, first ? &guess : nullptr, nullptr, first ? &p : nullptr);
-      if (rc) return rc;
+  rc = run_transitions(e, buf, budget, &launched, [&](long long, bool first) {
+    if (degenerate) return (int)FVH_OK;  // nothing to queue: the loop reads the initialised state back and ends
+    {
+      ProfScope ps(e, "gicp_nn");
+      launch_nn1(e, src, tgt, reinterpret_cast<const float*>(base + 16), thr * thr, e->corr.as<int>(), nullptr, first ? LmLink{nullptr, nullptr, nullptr, nullptr, 0} : link);
     }
-    launched += batch;
-    HIP_OR_FAIL(e, hipMemcpyAsync(h, st, sizeof(LmState), hipMemcpyDeviceToHost, e->stream));
-    HIP_OR_FAIL(e, hipStreamSynchronize(e->stream));
-    if (h->phase == PH_DONE || launched >= budget || p.max_iterations <= 0) break;
-    batch = 3;
-  }
-  e->prev_steps = e->last_steps;
-  e->last_steps = p.optimizer ? std::max(1, (int)h->num_linearize) : 1 + h->num_error_evals;
-  e->lin = h->x_lin;
-  e->corr_sel = h->corr_cur;
-  e->has_corr = true;
-  e->corr_kind = 1;
-  e->corr_n_src = src.n;
-  pose_to_colmajor16(h->x0, result->T);
-  for (int i = 0; i < 6; i++) for (int j = 0; j < 6; j++) result->H[j * 6 + i] = h->final_H[i * 6 + j];
-  result->final_error = h->y0;
-  result->converged = h->converged;
-  result->nr_iterations = h->nr_iterations;
-  result->num_linearize = h->num_linearize;
-  result->num_error_evals = h->num_error_evals;
-  result->lm_failed = h->lm_failed;
-  result->num_launches = (int)(2 * launched);
-  e->lm_trace_rows = e->lm_trace_on ? h->num_error_evals : 0;
+    return launch_cost<MODE_VGICP>(e, cs, records, -1, first ? &guess : nullptr, nullptr, first ? &p : nullptr);
+  });
+  if (rc) return rc;
+  const LmState& h = *buf.host;
+  leave_handle(e, h, p, 1, src.n);
+  fill_result(h, 2 * launched, result);  // (a search and a cost launch per step)
+  e->lm_trace_rows = e->lm_trace_on ? h.num_error_evals : 0;
   return FVH_OK;
 }
 
@@ -94,7 +76,7 @@ int gicp_update_correspondences(Engine* e, CloudDev& src, CloudDev& tgt, VoxelMa
   int rc = gicp_prepare(e, src, tgt, records, max_dist, "gicp_update_correspondences");
   if (rc) return rc;
   float T12[12];
-  for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) T12[i * 4 + j] = (float)T16[j * 4 + i]; T12[i * 4 + 3] = (float)T16[12 + i]; }  // trans.cast<float>()
+  pose_to_rowmajor12f(T16, T12);
   char* base = (char*)e->fit.p;
   HIP_OR_FAIL(e, hipMemcpyAsync(base + 16, T12, sizeof(T12), hipMemcpyHostToDevice, e->stream));
   const double thr = std::min(max_dist, 1.8446743e19);  // threshold^2 must stay finite in fp64 (reference default: float max)

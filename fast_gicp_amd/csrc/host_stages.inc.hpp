@@ -719,6 +719,10 @@ inline CostShape cost_shape(const Engine* e, const CostSource& src, int mode = M
   return s;
 }
 
+// a run-time flag as a type, for a generic lambda that names a kernel instantiation (the style of fvh_ndt::by_mode)
+template <class F>
+void by_flag(bool on, F&& f) { if (on) f(std::true_type{}); else f(std::false_type{}); }
+
 // align_multi: K hypotheses in one launch of lm_gang_kernel (kernels_cost.hpp), each on its slice of the handle's multi_* buffers
 struct MultiLaunch { int k; };
 
@@ -815,7 +819,6 @@ int launch_cost(Engine* e, const CostSource& src, const VoxelMapDev& vm, int hos
     const int everywhere = e->params.lm_everywhere;
     P.lm_everywhere = (persistent && P.ng > 1 && (everywhere == 2 || (everywhere == 1 && blocks <= 2 * cus))) ? 1 : 0;
   }
-  const int launch_blocks = blocks;
   if (persistent && plan) P.xcd_local = plan->local;
   GangParams G{blocks, nullptr};
   const int gangs = multi ? multi->k : 1;
@@ -847,30 +850,20 @@ int launch_cost(Engine* e, const CostSource& src, const VoxelMapDev& vm, int hos
     P.launch_tag = ++e->persist_seq;
     e->last_persist_blocks = blocks;
     (void)e->gang_begin(false);  // (the persistent launches share the chip through the SlotPool; other handles' cooperative sorts stay away while this runs)
-    {
-      ProfScope ps(e, "cost");
-      // (items of ONE offset take the instantiation unrolled for one lookup; both routes of an align pick by the same shape.
-      // Gauss-Newton aligns take their own instantiations: the Levenberg-Marquardt ones do not carry the other optimiser's code)
-#define FVH_LAUNCH_COST(KERNEL, PERS, GRID, ...)                                                                                      \
-  do {                                                                                                                                \
-    const bool f32 = e->float_cost();                                                                                                 \
-    if ((host_phase < 0 ? e->align_optimizer : 0) == 0) {                                                                             \
-      if (P.group == 1) { if (f32) KERNEL<float, MODE, PERS, 1><<<GRID, 256, 0, e->stream>>>(__VA_ARGS__); else KERNEL<double, MODE, PERS, 1><<<GRID, 256, 0, e->stream>>>(__VA_ARGS__); } \
-      else { if (f32) KERNEL<float, MODE, PERS><<<GRID, 256, 0, e->stream>>>(__VA_ARGS__); else KERNEL<double, MODE, PERS><<<GRID, 256, 0, e->stream>>>(__VA_ARGS__); }                    \
-    } else {                                                                                                                          \
-      if (P.group == 1) { if (f32) KERNEL<float, MODE, PERS, 1, true><<<GRID, 256, 0, e->stream>>>(__VA_ARGS__); else KERNEL<double, MODE, PERS, 1, true><<<GRID, 256, 0, e->stream>>>(__VA_ARGS__); } \
-      else { if (f32) KERNEL<float, MODE, PERS, COST_CH, true><<<GRID, 256, 0, e->stream>>>(__VA_ARGS__); else KERNEL<double, MODE, PERS, COST_CH, true><<<GRID, 256, 0, e->stream>>>(__VA_ARGS__); } \
-    }                                                                                                                                 \
-  } while (0)
-      if (multi) FVH_LAUNCH_COST(lm_gang_kernel, true, gangs * launch_blocks, P, G);
-      else FVH_LAUNCH_COST(cost_kernel, true, launch_blocks, P);
-    }
-    e->gang_end();
-  } else {
-    ProfScope ps(e, "cost");
-    if (multi) FVH_LAUNCH_COST(lm_gang_kernel, false, gangs * blocks, P, G);
-    else FVH_LAUNCH_COST(cost_kernel, false, blocks, P);
   }
+  {
+    ProfScope ps(e, "cost");
+    // (items of ONE offset take the instantiation unrolled for one lookup; both routes of an align pick by the same shape.
+    // Gauss-Newton aligns take their own instantiations: the Levenberg-Marquardt ones do not carry the other optimiser's code)
+    const bool gauss_newton = (host_phase < 0 ? e->align_optimizer : 0) != 0;
+    by_flag(e->float_cost(), [&](auto f32) { by_flag(P.group == 1, [&](auto one) { by_flag(gauss_newton, [&](auto gn) { by_flag(persistent, [&](auto pers) {
+      using Real = std::conditional_t<decltype(f32)::value, float, double>;
+      constexpr int CH = decltype(one)::value ? 1 : COST_CH;
+      if (multi) lm_gang_kernel<Real, MODE, decltype(pers)::value, CH, decltype(gn)::value><<<gangs * blocks, 256, 0, e->stream>>>(P, G);
+      else cost_kernel<Real, MODE, decltype(pers)::value, CH, decltype(gn)::value><<<blocks, 256, 0, e->stream>>>(P);
+    }); }); }); });
+  }
+  if (persistent) e->gang_end();
   HIP_OR_FAIL(e, hipGetLastError());
   return FVH_OK;
 }
@@ -958,6 +951,112 @@ template <int MODE>
 int do_align(Engine* e, const CostSource& src, VoxelMapDev& vm, const double* guess16, const fvh_lm_params* params, fvh_lm_result* result, const Rebuild& rebuild_safe,
              bool retried = false, bool no_persist = false, const GridPlan* forced_plan = nullptr);
 
+// ---- the host-side LM driver: what align (align_begin / align_finish), do_align_multi and gicp_align (host_gicp.inc.hpp) share ----
+// launches a whole LM loop may take, one per transition
+inline long long lm_budget(const fvh_lm_params& p) { return (long long)std::max(p.max_iterations, 0) * (1 + (long long)std::max(p.lm_max_iterations, 0)) + 1; }
+// the LM state at the guess (max_iterations <= 0 -- nothing to launch: only the state has to say "done" -- and fvh_debug_lm_replay)
+inline void launch_lm_init(hipStream_t on, LmState* st, const PoseD& guess, const fvh_lm_params& p, unsigned* ticket) {
+  lm_init_kernel<<<1, 64, 0, on>>>(st, guess, p.rotation_epsilon, p.transformation_epsilon, p.lm_init_lambda_factor, p.max_iterations, p.lm_max_iterations, ticket, p.optimizer != 0 ? 1 : 0);
+}
+// the LM step alone, on sums that arrived from outside the cost kernel (RCCL all-reduce, fvh_debug_lm_replay)
+inline void launch_lm_update(hipStream_t on, LmState* st, const fvh_lm_params& p) {
+  if (p.optimizer) lm_update_kernel<true><<<1, 64, 0, on>>>(st); else lm_update_kernel<false><<<1, 64, 0, on>>>(st);
+}
+
+// Where a driver's K LM states live: on the device, their pinned host copies, and the mapped block a persistent launch writes them to
+// (state + sequence word per hypothesis, `stride` 64-bit words apart).
+struct LmBuffers { LmState* dev; LmState* host; const void* result; size_t stride; int k; };
+inline LmBuffers single_buffers(Engine* e) { return {e->state.as<LmState>(), reinterpret_cast<LmState*>(e->pinned), e->result_host, 0, 1}; }
+inline LmBuffers multi_buffers(Engine* e, int K) { return {e->multi_state.as<LmState>(), static_cast<LmState*>(e->multi_pinned), e->multi_result_host, GANG_RESULT_WORDS, K}; }
+
+inline int read_states(Engine* e, const LmBuffers& b) {
+  HIP_OR_FAIL(e, hipMemcpyAsync(b.host, b.dev, sizeof(LmState) * b.k, hipMemcpyDeviceToHost, e->stream));
+  HIP_OR_FAIL(e, hipStreamSynchronize(e->stream));
+  return FVH_OK;
+}
+
+// The K states of the persistent launch just queued, into b.host. Zero-copy: spin on the sequence words the kernel writes after the states
+// (mapped pinned memory); if the stream drains without them (watchdog abort), or without zero-copy, the states are copied.
+int collect_persistent(Engine* e, const LmBuffers& b) {
+  bool have = false;
+  if (b.result && e->zero_copy_armed) {
+    volatile unsigned long long* words = static_cast<volatile unsigned long long*>(const_cast<void*>(b.result));
+    const size_t seq_at = sizeof(LmState) / 8;
+    if (e->params.host_wait_block != 0) (void)hipStreamSynchronize(e->stream);  // sleep in hipStreamSynchronize instead of spinning a core on the result words
+    // (the stream is only asked now and then -- it answers "drained" when a launch ended without its result word, i.e. aborted: every query
+    // takes the runtime's lock, which concurrent aligns of other host threads also need for their launches)
+    // KNOWN DEFECT: result_query_spins > 2^63 overflows `m` to 0 and this loop never ends.
+    const unsigned long long query_mask = [&] { unsigned long long m = 1; while (m < e->params.result_query_spins) m <<= 1; return m - 1; }();
+    auto all_in = [&] { for (int k = 0; k < b.k; k++) if (words[(size_t)k * b.stride + seq_at] != e->persist_seq) return false; return true; };
+    for (unsigned long long spins = 0;; spins++) {
+      if (all_in()) { have = true; break; }
+      if ((spins & query_mask) == query_mask && hipStreamQuery(e->stream) != hipErrorNotReady) { have = all_in(); break; }  // drained (or failed: the copy below reports it)
+    }
+    if (have) {
+      std::atomic_thread_fence(std::memory_order_acquire);
+      for (int k = 0; k < b.k; k++) {
+        std::memcpy(b.host + k, static_cast<const char*>(b.result) + sizeof(unsigned long long) * b.stride * k, sizeof(LmState) - 8);
+        b.host[k].gen = 0; b.host[k].aborted = 0;
+      }
+    }
+  }
+  return have ? FVH_OK : read_states(e, b);
+}
+
+// After collect_persistent(): did every state end? If not the barrier watchdog fired (workgroups not co-resident -- typically ANOTHER PROCESS on
+// the same GPU, which the SlotPool cannot see) and the caller redoes the work with one launch per transition; the handle backs off: it skips the
+// persistent route for 1, 2, 4, ... 64 aligns before trying again, so a shared GPU costs one stall now and then instead of one per registration.
+inline bool persistent_ended_clean(Engine* e, const LmBuffers& b) {
+  bool clean = true;
+  for (int k = 0; k < b.k; k++) clean = clean && !b.host[k].aborted && b.host[k].phase == PH_DONE;
+  if (clean) { e->persist_backoff = 0; return true; }  // the device is ours again
+  e->persist_aborts++;
+  e->persist_backoff = std::min(std::max(2 * e->persist_backoff, 1), 64);
+  e->persist_skip = e->persist_backoff;
+  return false;
+}
+
+// One launch per LM transition: queue(i, first) queues step i (`first`: it carries the guess and the LM parameters and (re)initialises the device
+// state). Steps go out in batches with a readback of the states behind each -- the first as long as the last two aligns needed, so that the
+// usual align reads back once -- until every state is done (steps queued behind that return at once), one says `aborted`, or the budget is
+// spent. *launched: the steps queued.
+template <class Queue>
+int run_transitions(Engine* e, const LmBuffers& b, long long budget, long long* launched, Queue&& queue) {
+  *launched = 0;
+  for (int batch = e->last_steps > 0 ? std::max(e->last_steps, e->prev_steps) + 1 : 8;; batch = 3) {
+    for (int s = 0; s < batch; s++) { const int rc = queue(*launched + s, *launched + s == 0); if (rc) return rc; }
+    *launched += batch;
+    { const int rc = read_states(e, b); if (rc) return rc; }
+    bool done = true, aborted = false;
+    for (int k = 0; k < b.k; k++) { done = done && b.host[k].phase == PH_DONE; aborted = aborted || b.host[k].aborted; }
+    if (done || aborted || *launched >= budget) return FVH_OK;
+  }
+}
+
+inline void fill_result(const LmState& h, long long launches, fvh_lm_result* r) {
+  pose_to_colmajor16(h.x0, r->T);
+  for (int i = 0; i < 6; i++) for (int j = 0; j < 6; j++) r->H[j * 6 + i] = h.final_H[i * 6 + j];
+  r->final_error = h.y0;
+  r->converged = h.converged;
+  r->nr_iterations = h.nr_iterations;
+  r->num_linearize = h.num_linearize;
+  r->num_error_evals = h.num_error_evals;
+  r->lm_failed = h.lm_failed;
+  r->num_launches = (int)launches;
+}
+
+// What an align that ended in state `h` leaves on the handle: the launches it needed (the next per-transition loop's first batch) and the
+// correspondences of its last consumed linearisation, which stay valid for compute_error(). `corr_kind`: 0 voxel-bucket ids, 1 nearest target points.
+inline void leave_handle(Engine* e, const LmState& h, const fvh_lm_params& p, int corr_kind, int n_src) {
+  e->prev_steps = e->last_steps;
+  e->last_steps = p.optimizer ? std::max(1, (int)h.num_linearize) : 1 + h.num_error_evals;  // the first linearize + one fused launch per trial (Gauss-Newton: one per linearisation)
+  e->lin = h.x_lin;
+  e->corr_sel = h.corr_cur;
+  e->has_corr = true;
+  e->corr_kind = corr_kind;
+  e->corr_n_src = n_src;
+}
+
 // first half: validate, pick the route and the grid, launch the persistent LM kernel (the multi-launch route queues nothing here)
 template <int MODE>
 int align_begin(Engine* e, AlignCtx& c, const CostSource& src, VoxelMapDev& vm, const double* guess16, const fvh_lm_params* params,
@@ -974,21 +1073,18 @@ int align_begin(Engine* e, AlignCtx& c, const CostSource& src, VoxelMapDev& vm, 
   e->align_optimizer = p.optimizer != 0 ? 1 : 0;  // (every launch of this align -- begin, finish, fall-backs -- takes that optimiser's instantiation)
   c.retried = retried; c.no_persist = no_persist; c.grant_dev = e->device;
   HIP_OR_FAIL(e, e->corr.ensure(2 * sizeof(int) * (size_t)std::max(src.n_upper, 1) * e->n_off));
-  LmState* st = e->state.as<LmState>();
   const PoseD guess = pose_from_colmajor16(guess16);
-  c.degenerate = p.max_iterations <= 0;  // nothing to launch: only the state has to say "done"
+  c.degenerate = p.max_iterations <= 0;
   if (c.degenerate) {
-    lm_init_kernel<<<1, 64, 0, e->stream>>>(st, guess, p.rotation_epsilon, p.transformation_epsilon, p.lm_init_lambda_factor, p.max_iterations, p.lm_max_iterations, e->ticket.as<unsigned>(), p.optimizer != 0 ? 1 : 0);
+    launch_lm_init(e->stream, e->state.as<LmState>(), guess, p, e->ticket.as<unsigned>());
     HIP_OR_FAIL(e, hipGetLastError());
   }
-  c.budget = (long long)std::max(p.max_iterations, 0) * (1 + (long long)std::max(p.lm_max_iterations, 0)) + 1;
+  c.budget = lm_budget(p);
   if (e->lm_trace_on) HIP_OR_FAIL(e, e->lm_trace.ensure(sizeof(double) * 6 * (size_t)std::max<long long>(c.budget, 1)));
   e->lm_trace_rows = 0;
   // One persistent launch for the whole LM loop when the problem is in the latency-bound regime and there is no RCCL
   // collective between evaluations. Concurrent aligns of this process (several handles, several host threads) split the
-  // device's co-resident workgroup slots (SlotPool); after a watchdog abort -- typically ANOTHER PROCESS on the same GPU, which
-  // the pool cannot see -- the handle backs off: it skips the persistent route for 1, 2, 4, ... 64 aligns before trying again,
-  // so a shared GPU costs one 50 ms stall now and then instead of one per registration.
+  // device's co-resident workgroup slots (SlotPool); after a watchdog abort the handle backs off (persistent_ended_clean).
   const int persist_env = e->params.persistent;
   c.sharded = MODE == MODE_VGICP && e->peer.attached() && src.shardable;
   c.persistent = persist_env != 0 && !c.degenerate && !e->comm && !no_persist && c.budget < 4000 && (long long)src.n_upper * e->n_off <= PERSIST_MAX_ITEMS;
@@ -1034,43 +1130,16 @@ int align_finish(Engine* e, AlignCtx& c, const CostSource& src, VoxelMapDev& vm,
   if (!result) return e->fail(FVH_ERR_INVALID_ARGUMENT, "align: null argument");
   const fvh_lm_params& p = c.p;
   e->align_optimizer = p.optimizer != 0 ? 1 : 0;
-  const bool persistent = c.persistent, sharded = c.sharded, degenerate = c.degenerate;
-  const long long budget = c.budget;
+  const bool persistent = c.persistent, sharded = c.sharded;
   const PoseD guess = pose_from_colmajor16(c.guess16);
-  LmState* st = e->state.as<LmState>();
-  long long launched = 0;
-  int batch = e->last_steps > 0 ? std::max(e->last_steps, e->prev_steps) + 1 : 8;
-  LmState* h = reinterpret_cast<LmState*>(e->pinned);
+  const LmBuffers buf = single_buffers(e);
+  LmState* const st = buf.dev;
+  LmState* const h = buf.host;
+  long long launched = 1;
   if (persistent) {
-    bool have_result = false;
-    if (e->result_dev && e->zero_copy_armed) {
-      // spin on the sequence word the kernel writes after the state (mapped pinned memory); if the stream drains without it
-      // (watchdog abort) fall through to the copy
-      volatile unsigned long long* seq = reinterpret_cast<volatile unsigned long long*>(e->result_host) + sizeof(LmState) / 8;
-      const bool block = e->params.host_wait_block != 0;  // sleep in hipStreamSynchronize instead of spinning a core on the result word
-      if (block) (void)hipStreamSynchronize(e->stream);
-      // (the stream is only asked now and then -- it answers "drained" when a launch ended without its result word, i.e. aborted: every query
-      // takes the runtime's lock, which concurrent aligns of other host threads also need for their launches)
-      const unsigned long long query_mask = [&] { unsigned long long m = 1; while (m < e->params.result_query_spins) m <<= 1; return m - 1; }();
-      for (unsigned long long spins = 0;; spins++) {
-        if (*seq == e->persist_seq) { have_result = true; break; }
-        if ((spins & query_mask) == query_mask && hipStreamQuery(e->stream) != hipErrorNotReady) { have_result = (*seq == e->persist_seq); break; }  // drained (or failed: the copy below reports it)
-      }
-      if (have_result) {
-        std::atomic_thread_fence(std::memory_order_acquire);
-        std::memcpy(h, e->result_host, sizeof(LmState) - 8);
-        h->gen = 0; h->aborted = 0;
-      }
-    }
-    if (!have_result) {
-      HIP_OR_FAIL(e, hipMemcpyAsync(h, st, sizeof(LmState), hipMemcpyDeviceToHost, e->stream));
-      HIP_OR_FAIL(e, hipStreamSynchronize(e->stream));
-    }
-    if (h->aborted || h->phase != PH_DONE) {  // the barrier watchdog fired (workgroups not co-resident): redo with one launch per transition
-      e->persist_aborts++;
+    { const int rc = collect_persistent(e, buf); if (rc) return rc; }
+    if (!persistent_ended_clean(e, buf)) {  // redo with one launch per transition
       e->abort_word_dirty = true;
-      e->persist_backoff = std::min(std::max(2 * e->persist_backoff, 1), 64);
-      e->persist_skip = e->persist_backoff;
       // multi-GPU: an abort on ANY rank reaches every rank within a watchdog period (its mailbox stays empty), so all ranks
       // arrive here and restart together; the exchange counter jumps past whatever this launch may have used
       if (sharded) e->peer.x = (e->peer.x + 8192) & ~1ull;
@@ -1080,32 +1149,22 @@ int align_finish(Engine* e, AlignCtx& c, const CostSource& src, VoxelMapDev& vm,
       c.release_slots();
       return do_align<MODE>(e, src, vm, c.guess16, &p, result, rebuild_safe, retried, true, &plan);  // the same layout: the same partition of the items, the same sums
     }
-    launched = 1;
-    e->persist_backoff = 0;  // a clean persistent run: the device is ours again
     if (sharded) e->peer.x += (unsigned long long)(p.optimizer ? h->num_linearize : 1 + h->num_error_evals);  // one exchange per trip
-  }
-  while (!persistent) {
-    for (int s = 0; s < batch; s++) {
-      // the first launch carries the initial guess and the LM parameters and (re)initialises the device state
-      const bool first = (launched == 0 && s == 0 && !degenerate);
-      int rc = launch_cost<MODE>(e, src, vm, -1, first ? &guess : nullptr, nullptr, first ? &p : nullptr, false, e->peer.x + (unsigned long long)(launched + s), c.forced ? &c.plan : nullptr);
-      if (rc) return rc;
-      if (e->comm) {
-        rc = allreduce_sums(e);
-        if (rc) return rc;
-        if (p.optimizer) lm_update_kernel<true><<<1, 64, 0, e->stream>>>(st); else lm_update_kernel<false><<<1, 64, 0, e->stream>>>(st);
-      }
-    }
-    launched += batch;
-    HIP_OR_FAIL(e, hipMemcpyAsync(h, st, sizeof(LmState), hipMemcpyDeviceToHost, e->stream));
-    HIP_OR_FAIL(e, hipStreamSynchronize(e->stream));
+  } else {
+    const int rc = run_transitions(e, buf, c.budget, &launched, [&](long long i, bool first) {
+      first = first && !c.degenerate;  // (its state is initialised already)
+      int rc = launch_cost<MODE>(e, src, vm, -1, first ? &guess : nullptr, nullptr, first ? &p : nullptr, false, e->peer.x + (unsigned long long)i, c.forced ? &c.plan : nullptr);
+      if (rc || !e->comm) return rc;
+      rc = allreduce_sums(e);
+      if (!rc) launch_lm_update(e->stream, st, p);
+      return rc;
+    });
+    if (rc) return rc;
     if (h->aborted) {  // (only the peer exchange raises it on this route)
       e->abort_word_dirty = true;
       e->peer.x = (e->peer.x + 8192) & ~1ull;
       return e->fail(FVH_ERR_COMM, "align: a peer rank did not deliver its sums (every rank must make the same sequence of calls)");
     }
-    if (h->phase == PH_DONE || launched >= budget) break;
-    batch = 3;
   }
   if (!persistent && sharded && h->num_linearize > 0) e->peer.x += (unsigned long long)(p.optimizer ? h->num_linearize : 1 + h->num_error_evals);  // launches after PH_DONE leave before the exchange
   vm.nv_hint = h->vm_num_voxels;
@@ -1122,22 +1181,8 @@ int align_finish(Engine* e, AlignCtx& c, const CostSource& src, VoxelMapDev& vm,
     return do_align<MODE>(e, fresh, vm, c.guess16, &p, result, rebuild_safe, true, no_persist, forced ? &plan : nullptr);
   }
   e->gang_clear();
-  e->prev_steps = e->last_steps;
-  e->last_steps = p.optimizer ? std::max(1, (int)h->num_linearize) : 1 + h->num_error_evals;  // launches this align needed: the first linearize + one fused launch per trial (Gauss-Newton: one per linearisation)
-  e->lin = h->x_lin;
-  e->corr_sel = h->corr_cur;
-  e->has_corr = true;  // correspondences of the last consumed linearisation stay valid for compute_error()
-  e->corr_kind = 0;    // voxel-bucket ids (a nearest-point list of an earlier gicp_update_correspondences is gone)
-  e->corr_n_src = src.n_upper;
-  pose_to_colmajor16(h->x0, result->T);
-  for (int i = 0; i < 6; i++) for (int j = 0; j < 6; j++) result->H[j * 6 + i] = h->final_H[i * 6 + j];
-  result->final_error = h->y0;
-  result->converged = h->converged;
-  result->nr_iterations = h->nr_iterations;
-  result->num_linearize = h->num_linearize;
-  result->num_error_evals = h->num_error_evals;
-  result->lm_failed = h->lm_failed;
-  result->num_launches = (int)launched;
+  leave_handle(e, *h, p, 0 /* (a nearest-point list of an earlier gicp_update_correspondences is gone) */, src.n_upper);
+  fill_result(*h, launched, result);
   e->lm_trace_rows = e->lm_trace_on ? h->num_error_evals : 0;
   return FVH_OK;
 }
@@ -1249,7 +1294,7 @@ int do_align_multi(Engine* e, const CostSource& src_in, VoxelMapDev& vm, int K, 
   const size_t corr_stride = (size_t)std::max(src.n_upper, 1) * e->n_off;
   HIP_OR_FAIL(e, e->corr.ensure(2 * sizeof(int) * corr_stride));
   HIP_OR_FAIL(e, e->multi_corr.ensure(2 * sizeof(int) * corr_stride * K));
-  const long long budget = (long long)std::max(p.max_iterations, 0) * (1 + (long long)std::max(p.lm_max_iterations, 0)) + 1;
+  const long long budget = lm_budget(p);
   bool persistent = e->params.persistent != 0 && budget < 4000 && (long long)src.n_upper * e->n_off <= PERSIST_MAX_ITEMS;
   if (persistent && e->persist_skip > 0) { e->persist_skip--; persistent = false; }  // backing off after an abort, like align()
   SlotPool::Grant grant;
@@ -1268,7 +1313,8 @@ int do_align_multi(Engine* e, const CostSource& src_in, VoxelMapDev& vm, int K, 
   GridPlan plan;
   plan.nb = nb_h; plan.ng = default_groups(nb_h); plan.local = 0;
   // guesses and fresh states (the abort words included)
-  LmState* hs = static_cast<LmState*>(e->multi_pinned);
+  const LmBuffers buf = multi_buffers(e, K);
+  LmState* const hs = buf.host;
   PoseD* hg = reinterpret_cast<PoseD*>(static_cast<char*>(e->multi_pinned) + sizeof(LmState) * (size_t)e->multi_cap);
   for (int k = 0; k < K; k++) hg[k] = pose_from_colmajor16(guesses16 + 16 * k);
   HIP_OR_FAIL(e, hipMemcpyAsync(e->multi_guess.p, hg, sizeof(PoseD) * K, hipMemcpyHostToDevice, e->stream));
@@ -1276,8 +1322,7 @@ int do_align_multi(Engine* e, const CostSource& src_in, VoxelMapDev& vm, int K, 
   long long launched = 0;
   bool retried = false;
   for (;;) {
-    HIP_OR_FAIL(e, hipMemsetAsync(e->multi_state.p, 0, sizeof(LmState) * K, e->stream));
-    launched = 0;
+    HIP_OR_FAIL(e, hipMemsetAsync(buf.dev, 0, sizeof(LmState) * K, e->stream));
     if (persistent) {
       e->lm_crowds_chip = Engine::crowds(K * nb_h, cap);
       if (e->lm_crowds_chip && fence && hipEventQuery(fence) != hipSuccess) {  // a preparation still runs on the second stream (Engine::lm_crowds_chip)
@@ -1285,58 +1330,16 @@ int do_align_multi(Engine* e, const CostSource& src_in, VoxelMapDev& vm, int K, 
         HIP_OR_FAIL(e, hipStreamWaitEvent(e->stream, fence, 0));
       }
       int rc = launch_cost<MODE>(e, src, vm, -1, nullptr, nullptr, &p, true, 0, &plan, &ml);
+      if (!rc) rc = collect_persistent(e, buf);
       if (rc) return rc;
-      bool have = false;
-      if (e->multi_result_dev && e->zero_copy_armed) {  // the K sequence words (align_finish's spin / query logic)
-        volatile unsigned long long* words = reinterpret_cast<volatile unsigned long long*>(e->multi_result_host);
-        const size_t seq_at = sizeof(LmState) / 8;
-        if (e->params.host_wait_block != 0) (void)hipStreamSynchronize(e->stream);
-        const unsigned long long query_mask = [&] { unsigned long long m = 1; while (m < e->params.result_query_spins) m <<= 1; return m - 1; }();
-        auto all_in = [&] { for (int k = 0; k < K; k++) if (words[(size_t)k * GANG_RESULT_WORDS + seq_at] != e->persist_seq) return false; return true; };
-        for (unsigned long long spins = 0;; spins++) {
-          if (all_in()) { have = true; break; }
-          if ((spins & query_mask) == query_mask && hipStreamQuery(e->stream) != hipErrorNotReady) { have = all_in(); break; }
-        }
-        if (have) {
-          std::atomic_thread_fence(std::memory_order_acquire);
-          for (int k = 0; k < K; k++) {
-            std::memcpy(hs + k, static_cast<const char*>(e->multi_result_host) + sizeof(unsigned long long) * GANG_RESULT_WORDS * k, sizeof(LmState) - 8);
-            hs[k].gen = 0; hs[k].aborted = 0;
-          }
-        }
-      }
-      if (!have) {
-        HIP_OR_FAIL(e, hipMemcpyAsync(hs, e->multi_state.p, sizeof(LmState) * K, hipMemcpyDeviceToHost, e->stream));
-        HIP_OR_FAIL(e, hipStreamSynchronize(e->stream));
-      }
       slots.release();
       e->lm_crowds_chip = false;
-      bool failed = false;
-      for (int k = 0; k < K; k++) failed = failed || hs[k].aborted || hs[k].phase != PH_DONE;
-      if (failed) {  // the barrier watchdog fired in some gang: all K again on the multi-launch route, the same plan (the same sums)
-        e->persist_aborts++;
-        e->persist_backoff = std::min(std::max(2 * e->persist_backoff, 1), 64);
-        e->persist_skip = e->persist_backoff;
-        persistent = false;
-        continue;
-      }
+      persistent = false;  // (whatever comes: a redo after an abort or a table overflow takes the multi-launch route)
+      if (!persistent_ended_clean(e, buf)) continue;  // the barrier watchdog fired in some gang: all K again, the same plan (the same sums)
       launched = 1;
-      e->persist_backoff = 0;
-    } else {
-      int batch = e->last_steps > 0 ? std::max(e->last_steps, e->prev_steps) + 1 : 8;
-      for (;;) {
-        for (int s = 0; s < batch; s++) {  // (gangs that are done return at once)
-          const int rc = launch_cost<MODE>(e, src, vm, -1, nullptr, nullptr, (launched == 0 && s == 0) ? &p : nullptr, false, 0, &plan, &ml);
-          if (rc) return rc;
-        }
-        launched += batch;
-        HIP_OR_FAIL(e, hipMemcpyAsync(hs, e->multi_state.p, sizeof(LmState) * K, hipMemcpyDeviceToHost, e->stream));
-        HIP_OR_FAIL(e, hipStreamSynchronize(e->stream));
-        bool all_done = true;
-        for (int k = 0; k < K; k++) all_done = all_done && hs[k].phase == PH_DONE;
-        if (all_done || launched >= budget) break;
-        batch = 3;
-      }
+    } else {  // (gangs that are done return at once)
+      const int rc = run_transitions(e, buf, budget, &launched, [&](long long, bool first) { return launch_cost<MODE>(e, src, vm, -1, nullptr, nullptr, first ? &p : nullptr, false, 0, &plan, &ml); });
+      if (rc) return rc;
     }
     vm.nv_hint = hs[K - 1].vm_num_voxels;
     if (src.source_map) src.source_map->nv_hint = hs[K - 1].vm_num_voxels2;
@@ -1349,33 +1352,14 @@ int do_align_multi(Engine* e, const CostSource& src_in, VoxelMapDev& vm, int K, 
     const int rc = rebuild_safe();
     if (rc) return rc;
     src.refresh();
-    persistent = false;
     plan.nb = nb_h = std::min(cost_shape(e, src, MODE, true).blocks, cap); plan.ng = default_groups(nb_h);
   }
   if (grid_out) *grid_out = nb_h;
   e->gang_clear();
-  for (int k = 0; k < K; k++) {
-    const LmState& h = hs[k];
-    fvh_lm_result* r = results + k;
-    pose_to_colmajor16(h.x0, r->T);
-    for (int i = 0; i < 6; i++) for (int j = 0; j < 6; j++) r->H[j * 6 + i] = h.final_H[i * 6 + j];
-    r->final_error = h.y0;
-    r->converged = h.converged;
-    r->nr_iterations = h.nr_iterations;
-    r->num_linearize = h.num_linearize;
-    r->num_error_evals = h.num_error_evals;
-    r->lm_failed = h.lm_failed;
-    r->num_launches = (int)launched;
-    e->prev_steps = e->last_steps;
-    e->last_steps = p.optimizer ? std::max(1, (int)h.num_linearize) : 1 + h.num_error_evals;
-  }
-  // the handle as the last of K plain aligns leaves it: its linearisation pose, correspondences (compute_error) and device state
+  // the handle as K plain aligns, one after the other, leave it: their step counts, then the last one's linearisation pose, correspondences
+  // (compute_error) and device state
+  for (int k = 0; k < K; k++) { fill_result(hs[k], launched, results + k); leave_handle(e, hs[k], p, 0, src.n_upper); }
   const LmState& last = hs[K - 1];
-  e->lin = last.x_lin;
-  e->corr_sel = last.corr_cur;
-  e->has_corr = true;
-  e->corr_kind = 0;
-  e->corr_n_src = src.n_upper;
   HIP_OR_FAIL(e, hipMemcpyAsync(e->corr.p, e->multi_corr.as<int>() + (size_t)(K - 1) * 2 * corr_stride, 2 * sizeof(int) * corr_stride, hipMemcpyDeviceToDevice, e->stream));
   HIP_OR_FAIL(e, hipMemcpyAsync(e->state.p, e->multi_state.as<LmState>() + (K - 1), sizeof(LmState) - 8, hipMemcpyDeviceToDevice, e->stream));
   std::memcpy(e->pinned, &last, sizeof(LmState));
@@ -1392,7 +1376,7 @@ int do_fitness(Engine* e, CloudDev& src, CloudDev& tgt, const double* T16, doubl
   if (!T16 || !score) return e->fail(FVH_ERR_INVALID_ARGUMENT, "fitness_score: null argument");
   if (!src.has_pts || !tgt.has_pts || src.n == 0 || tgt.n == 0) return e->fail(FVH_ERR_BAD_STATE, "fitness_score: clouds not set");
   float T12[12];
-  for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) T12[i * 4 + j] = (float)T16[j * 4 + i]; T12[i * 4 + 3] = (float)T16[12 + i]; }
+  pose_to_rowmajor12f(T16, T12);
   char* base = (char*)e->fit.p;
   HIP_OR_FAIL(e, hipMemsetAsync(base, 0, 16, e->stream));
   HIP_OR_FAIL(e, hipMemcpyAsync(base + 16, T12, sizeof(T12), hipMemcpyHostToDevice, e->stream));

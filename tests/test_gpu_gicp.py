@@ -196,3 +196,36 @@ def test_row_per_query_nearest_neighbour_search_is_exact(O, ns, nt):
     fit = c.fitness_score(T)
     assert abs(fit - fit_expect) <= 1e-6 * max(fit_expect, 1e-30), (fit, fit_expect)
     c.close()
+
+
+FIELDS = ("T", "H", "final_error", "converged", "nr_iterations", "num_linearize", "num_error_evals")
+
+
+def _same(a, b, what=""):
+    for f in FIELDS:
+        assert np.array_equal(np.asarray(a[f]), np.asarray(b[f])), (what, f, a[f], b[f])
+
+
+def test_device_lm_align_without_iterations_returns_the_guess(pair):
+    tgt, src = pair
+    c, fresh = _prepared(tgt, src), _prepared(tgt, src)
+    guess = util.random_pose(np.random.default_rng(5), 2.0, 0.3)
+    r = c.gicp_align(guess, max_iterations=0)
+    assert np.array_equal(r["T"], guess), (r["T"], guess)
+    assert r["num_linearize"] == 0 and r["num_error_evals"] == 0 and r["nr_iterations"] == 0, r
+    _same(c.gicp_align(), fresh.gicp_align(), "after max_iterations=0")
+    c.close(); fresh.close()
+
+
+def test_device_lm_align_does_not_depend_on_its_batch_size(pair):
+    """the first batch of launches is 8, later ones follow the steps the last aligns took (of whatever kind): the result is the same"""
+    tgt, src = pair
+    c, d = _prepared(tgt, src), _prepared(tgt, src)
+    rs = [c.gicp_align() for _ in range(3)]
+    d.create_target_voxelmap()
+    d.align()
+    rs.append(d.gicp_align())
+    assert rs[0]["converged"]
+    for i, r in enumerate(rs[1:]):
+        _same(r, rs[0], i + 1)
+    c.close(); d.close()

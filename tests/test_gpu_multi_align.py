@@ -302,3 +302,77 @@ def test_pygicp_align_multi_and_align_best():
         te, re_ = util.pose_error(gt_turned, np.asarray(Tb, np.float64))
         assert te < 0.05 and re_ < np.radians(1.0), (make, idx, te, re_)
         assert np.array_equal(Tb, reg.get_final_transformation())
+
+
+# ---- the branches the shared host-side LM driver merges (table-overflow rerun, degenerate launch, back-off, result transport) ----
+def _small(res=None, hint=None, **params):
+    """the small synthetic pair of test_gpu_robustness.py, prepared as there: several workgroups, several groups, a ragged last tile"""
+    from fast_gicp_amd import capi
+    tgt, src, _ = util.synthetic_pair(4000, 3500, seed=3, extent=12.0)
+    c = capi.VGICPCore(0)
+    if params:
+        c.set_engine_params(**params)
+    if res is not None:
+        c.set_resolution(res)
+    c.set_neighbor_search_method(1)
+    c.set_target_cloud(tgt); c.find_target_neighbors(20); c.calculate_target_covariances(3)
+    if hint is not None:
+        c.debug_set_voxel_hint(hint)
+    c.create_target_voxelmap()
+    c.set_source_cloud(src); c.find_source_neighbors(20); c.calculate_source_covariances(3)
+    return c
+
+
+def test_multi_table_overflow_reruns_on_the_rebuilt_map():
+    c = _small(res=0.25, hint=1)  # 1,024 buckets for a few thousand voxels
+    assert c.debug_table_capacity() == 1024
+    G = guesses(3)
+    ms = c.align_multi(G)
+    assert c.debug_table_capacity() > 1024
+    assert all(m["num_launches"] > 1 for m in ms), [m["num_launches"] for m in ms]  # the rerun: one launch per transition
+    for i, s in enumerate(sequential(c, G, ms[0]["grid_blocks"])):  # (the same handle: the same rebuilt map)
+        same(ms[i], s, i)
+    c.close()
+
+
+def test_multi_without_iterations_returns_the_guesses():
+    a, b, fresh = _small(), _small(), _small()
+    G = guesses(3)
+    ms = a.align_multi(G, max_iterations=0)
+    for k, m in enumerate(ms):
+        assert np.array_equal(m["T"], G[k]), (k, m["T"], G[k])
+        assert m["num_linearize"] == 0 and m["num_error_evals"] == 0 and m["nr_iterations"] == 0, m
+        same(m, b.align(G[k], max_iterations=0), k)
+    after, ref = a.align_multi(G), fresh.align_multi(G)
+    for k in range(3):
+        same(after[k], ref[k], ("after", k))
+        assert after[k]["grid_blocks"] == ref[k]["grid_blocks"]
+    a.close(); b.close(); fresh.close()
+
+
+def test_multi_abort_backs_off_the_next_plain_align():
+    from fast_gicp_amd import capi
+    a, fresh = _small(persist_watchdog_ticks=0), _small()
+    a.align_multi(guesses(3))
+    assert a.debug_persist_aborts() == 1
+    a.set_engine_params(persist_watchdog_ticks=capi.default_engine_params().persist_watchdog_ticks)
+    r1, r2, r0 = a.align(), a.align(), fresh.align()
+    assert r1["num_launches"] > 1, r1["num_launches"]   # skipped the persistent route once ...
+    assert r2["num_launches"] == 1, r2["num_launches"]  # ... and took it again
+    assert a.debug_persist_aborts() == 1
+    assert np.array_equal(r1["T"], r0["T"]) and np.array_equal(r2["T"], r0["T"])
+    a.close(); fresh.close()
+
+
+def test_multi_result_transports_agree():
+    c = _small()
+    G = guesses(3)
+    ref = c.align_multi(G)
+    assert all(m["num_launches"] == 1 for m in ref)
+    for params in (dict(zerocopy_result=0), dict(zerocopy_result=1, host_wait_block=1)):
+        c.set_engine_params(**params)
+        ms = c.align_multi(G)
+        for k in range(3):
+            same(ms[k], ref[k], (params, k))
+            assert ms[k]["num_launches"] == 1, (params, ms[k]["num_launches"])
+    c.close()
