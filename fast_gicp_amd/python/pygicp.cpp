@@ -39,6 +39,12 @@ static RegularizationMethod regularization_method(const std::string& s) {
   if (s == "FROBENIUS") return RegularizationMethod::FROBENIUS;
   throw std::invalid_argument("unknown regularization method " + s);
 }
+static VoxelAccumulationMode voxel_accumulation_mode(const std::string& s) {  // FastVGICP::setVoxelAccumulationMode (fast_vgicp_impl.hpp:41-43)
+  if (s == "ADDITIVE") return VoxelAccumulationMode::ADDITIVE;
+  if (s == "ADDITIVE_WEIGHTED") return VoxelAccumulationMode::ADDITIVE_WEIGHTED;
+  if (s == "MULTIPLICATIVE") return VoxelAccumulationMode::MULTIPLICATIVE;
+  throw std::invalid_argument("unknown voxel accumulation mode: " + s);
+}
 static NearestNeighborMethod nn_method(const std::string& s) {
   if (s == "CPU_PARALLEL_KDTREE") return NearestNeighborMethod::CPU_PARALLEL_KDTREE;
   if (s == "GPU_BRUTEFORCE") return NearestNeighborMethod::GPU_BRUTEFORCE;
@@ -76,9 +82,10 @@ static std::vector<Matrix4f> numpy2mat4s(const Mat4& m) {  // (K, 4, 4) -> K pos
   for (py::ssize_t k = 0; k < m.shape(0); k++) for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) out[k](i, j) = (float)r(k, i, j);
   return out;
 }
-static py::array_t<float> mat4_to_numpy(const Matrix4f& M) {
-  py::array_t<float> out({4, 4});
-  auto w = out.mutable_unchecked<2>();
+template <typename T = float>  // (the class methods return float32 like the reference's Matrix4f, align_points float64)
+static py::array_t<T> mat4_to_numpy(const Matrix4f& M) {
+  py::array_t<T> out({4, 4});
+  auto w = out.template mutable_unchecked<2>();
   for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) w(i, j) = M(i, j);
   return out;
 }
@@ -164,11 +171,7 @@ static py::array_t<double> align_points(const Points& target, const Points& sour
   reg->setInputSource(source_cloud);
   Cloud aligned;
   reg->align(aligned, numpy2mat4(initial_guess));
-  py::array_t<double> out({4, 4});
-  auto w = out.mutable_unchecked<2>();
-  const Matrix4f& M = reg->getFinalTransformation();
-  for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) w(i, j) = M(i, j);
-  return out;
+  return mat4_to_numpy<double>(reg->getFinalTransformation());
 }
 
 static py::array_t<double> covs_to_numpy(const GICP::Covariances& covs) {
@@ -258,12 +261,7 @@ PYBIND11_MODULE(pygicp, m) {
   py::class_<VGICPCuda, Lsq, std::shared_ptr<VGICPCuda>>(m, "FastVGICPCuda")
       .def(py::init([](int device) { return std::make_shared<VGICPCuda>(device); }), py::arg("device") = 0)
       .def("set_resolution", &VGICPCuda::setResolution)
-      .def("set_voxel_accumulation_mode", [](VGICPCuda& v, const std::string& mode) {  // FastVGICP::setVoxelAccumulationMode (fast_vgicp_impl.hpp:41-43)
-        if (mode == "ADDITIVE") v.setVoxelAccumulationMode(fast_gicp::VoxelAccumulationMode::ADDITIVE);
-        else if (mode == "ADDITIVE_WEIGHTED") v.setVoxelAccumulationMode(fast_gicp::VoxelAccumulationMode::ADDITIVE_WEIGHTED);
-        else if (mode == "MULTIPLICATIVE") v.setVoxelAccumulationMode(fast_gicp::VoxelAccumulationMode::MULTIPLICATIVE);
-        else throw std::invalid_argument("unknown voxel accumulation mode: " + mode);
-      })
+      .def("set_voxel_accumulation_mode", [](VGICPCuda& v, const std::string& mode) { v.setVoxelAccumulationMode(voxel_accumulation_mode(mode)); })
       .def("set_neighbor_search_method", [](VGICPCuda& v, const std::string& method, double radius) { v.setNeighborSearchMethod(search_method(method), radius); },
            py::arg("method") = "DIRECT1", py::arg("radius") = 1.5)
       .def("set_correspondence_randomness", &VGICPCuda::setCorrespondenceRandomness)
@@ -348,12 +346,7 @@ PYBIND11_MODULE(pygicp, m) {
       .def(py::init([](int device) { return std::make_shared<VGICP>(device); }), py::arg("device") = 0)
       .def("set_max_correspondence_distance", &VGICP::setMaxCorrespondenceDistance)  // (FastVGICP never reads it: voxel correspondences)
       .def("set_resolution", &VGICP::setResolution)
-      .def("set_voxel_accumulation_mode", [](VGICP& v, const std::string& mode) {  // FastVGICP::setVoxelAccumulationMode (fast_vgicp_impl.hpp:41-43)
-        if (mode == "ADDITIVE") v.setVoxelAccumulationMode(fast_gicp::VoxelAccumulationMode::ADDITIVE);
-        else if (mode == "ADDITIVE_WEIGHTED") v.setVoxelAccumulationMode(fast_gicp::VoxelAccumulationMode::ADDITIVE_WEIGHTED);
-        else if (mode == "MULTIPLICATIVE") v.setVoxelAccumulationMode(fast_gicp::VoxelAccumulationMode::MULTIPLICATIVE);
-        else throw std::invalid_argument("unknown voxel accumulation mode: " + mode);
-      })
+      .def("set_voxel_accumulation_mode", [](VGICP& v, const std::string& mode) { v.setVoxelAccumulationMode(voxel_accumulation_mode(mode)); })
       .def("set_neighbor_search_method", [](VGICP& v, const std::string& method) { v.setNeighborSearchMethod(search_method(method)); }, py::arg("method") = "DIRECT1");
 
   py::class_<NDT, Lsq, std::shared_ptr<NDT>>(m, "NDTCuda")

@@ -3,6 +3,8 @@
 //   fast_gicp::LsqRegistration   <- include/fast_gicp/gicp/lsq_registration.hpp + impl/lsq_registration_impl.hpp
 //   fast_gicp::FastVGICPCuda     <- include/fast_gicp/gicp/fast_vgicp_cuda.hpp  + impl/fast_vgicp_cuda_impl.hpp
 //   fast_gicp::NDTCuda           <- include/fast_gicp/ndt/ndt_cuda.hpp          + impl/ndt_cuda_impl.hpp
+// (FastGICP and FastVGICP likewise.) What the four have in common -- the handle, the virtuals of LsqRegistration on top of it, the
+// exception text -- is written once, in DeviceRegistration, against a table of C calls per correspondence model (detail::DeviceCalls).
 //
 // Same class / method / enum names, argument meaning and defaults as the reference, so code written
 // against it (gicp_align, gicp_test, pygicp) reads the same. PCL and Eigen are not available in this
@@ -89,7 +91,8 @@ struct Isometry3d {  // row-major R | t, double
   double R[9];
   double t[3];
   static Isometry3d Identity() { Isometry3d T; std::memset(&T, 0, sizeof(T)); T.R[0] = T.R[4] = T.R[8] = 1.0; return T; }
-  static Isometry3d from(const Matrix4f& M) {
+  template <typename Matrix4>  // Matrix4f or Matrix4d
+  static Isometry3d from(const Matrix4& M) {
     Isometry3d T;
     for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) T.R[i * 3 + j] = M(i, j); T.t[i] = M(i, 3); }
     return T;
@@ -97,6 +100,13 @@ struct Isometry3d {  // row-major R | t, double
   Matrix4f cast_float() const {
     Matrix4f M = Matrix4f::Identity();
     for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) M(i, j) = (float)R[i * 3 + j]; M(i, 3) = (float)t[i]; }
+    return M;
+  }
+  Matrix4d matrix() const {
+    Matrix4d M;
+    std::memset(M.m, 0, sizeof(M.m));
+    for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) M(i, j) = R[i * 3 + j]; M(i, 3) = t[i]; }
+    M(3, 3) = 1.0;
     return M;
   }
   void to_colmajor16(double* T16) const {
@@ -174,6 +184,12 @@ inline void ldlt6_solve(const Matrix6d& A, const Vector6d& rhs, Vector6d& x) {
   for (int i = 0; i < 6; i++) { double s = rhs[i]; for (int k = 0; k < i; k++) s -= L[i * 6 + k] * y[k]; y[i] = s; }
   for (int i = 0; i < 6; i++) y[i] = std::fabs(D[i]) > tiny ? y[i] / D[i] : 0.0;
   for (int i = 5; i >= 0; i--) { double s = y[i]; for (int k = i + 1; k < 6; k++) s -= L[k * 6 + i] * x[k]; x[i] = s; }
+}
+/// the C ABI's 6x6 is column-major, the classes' Matrix6d row-major
+inline Matrix6d transposed6(const double* H36) {
+  Matrix6d H;
+  for (int i = 0; i < 6; i++) for (int j = 0; j < 6; j++) H[i * 6 + j] = H36[j * 6 + i];
+  return H;
 }
 /// the table LsqRegistration::step_lm prints with setDebugPrint(true) (lsq_registration_impl.hpp:143-149), from the rows the
 /// device LM recorded ({i, y0, yi, rho, lambda, |delta|} per trial step)
@@ -278,6 +294,23 @@ inline std::vector<float> pack_xyz(const PointCloud<PointT>& c) {
   for (size_t i = 0; i < c.size(); i++) { xyz[3 * i] = c.points[i].x; xyz[3 * i + 1] = c.points[i].y; xyz[3 * i + 2] = c.points[i].z; }
   return xyz;
 }
+/// k nearest neighbours of every point from the host kd-tree on `threads` OpenMP threads, n x k (find_neighbors_parallel_kdtree,
+/// fast_vgicp_cuda_impl.hpp:152-167). A cloud with fewer than k points: the reference's zero-initialised vector keeps index 0 in the
+/// unfilled entries (:155,162; fast_gicp_impl.hpp:253-265)
+template <typename PointT>
+inline std::vector<int> host_kdtree_neighbors(const PointCloud<PointT>& cloud, int k, int threads) {
+  const std::vector<float> xyz = pack_xyz(cloud);
+  const int n = (int)cloud.size();
+  host::KdTree tree(xyz.data(), n);
+  std::vector<int> neighbors((size_t)n * k);
+#pragma omp parallel for schedule(guided, 8) num_threads(threads) if (threads > 1)
+  for (int i = 0; i < n; i++) {
+    int* row = &neighbors[(size_t)i * k];
+    tree.knn(&xyz[3 * (size_t)i], k, row);
+    for (int j = 0; j < k; j++) if (row[j] < 0) row[j] = 0;
+  }
+  return neighbors;
+}
 /// where align() spends its host time (apps/gicp_align, GICP_ALIGN_BREAKDOWN): off unless a caller switches it on
 struct HostTiming { bool on = false; double optimize_us = 0, transform_us = 0; };
 inline HostTiming& host_timing() { static HostTiming t; return t; }
@@ -336,22 +369,11 @@ public:
     const int k = (int)guesses.size();
     std::vector<double> g16(16 * (size_t)k);
     for (int i = 0; i < k; i++) Isometry3d::from(guesses[i]).to_colmajor16(&g16[16 * (size_t)i]);
-    fvh_lm_params p{max_iterations_, rotation_epsilon_, transformation_epsilon_, lm_max_iterations_, lm_init_lambda_factor_,
-                    lsq_optimizer_type_ == LSQ_OPTIMIZER_TYPE::GaussNewton ? 1 : 0};
+    const fvh_lm_params p = lm_params();
     std::vector<fvh_lm_result> r((size_t)std::max(k, 1));
     device_align_multi(k, g16.data(), &p, r.data(), &multi_grid_blocks_);
     std::vector<MultiAlignResult> out((size_t)k);
-    for (int i = 0; i < k; i++) {
-      const Isometry3d x = Isometry3d::from_colmajor16(r[i].T);
-      MultiAlignResult& o = out[i];
-      std::memset(o.T.m, 0, sizeof(o.T.m));
-      for (int a = 0; a < 3; a++) { for (int b = 0; b < 3; b++) o.T(a, b) = x.R[a * 3 + b]; o.T(a, 3) = x.t[a]; }
-      o.T(3, 3) = 1.0;
-      for (int a = 0; a < 6; a++) for (int b = 0; b < 6; b++) o.H[a * 6 + b] = r[i].H[b * 6 + a];
-      o.final_error = r[i].final_error;
-      o.converged = r[i].converged != 0;
-      o.nr_iterations = r[i].nr_iterations;
-    }
+    for (int i = 0; i < k; i++) out[i] = unpack(r[i]);
     return out;
   }
   /// alignMulti, then the pose with the lowest device fitness score (getFitnessScore(max_range) at that pose; ties go to the lowest index)
@@ -363,18 +385,12 @@ public:
     double best_score = 0.0;
     for (int i = 0; i < (int)rs.size(); i++) {
       double T16[16];
-      for (int a = 0; a < 4; a++) for (int b = 0; b < 4; b++) T16[b * 4 + a] = rs[i].T(a, b);
+      Isometry3d::from(rs[i].T).to_colmajor16(T16);
       const double score = device_fitness(T16, max_range);
       if (best < 0 || score < best_score) { best = i; best_score = score; }
     }
     if (best < 0) throw std::invalid_argument("alignBest: no guesses");
-    const MultiAlignResult& b = rs[best];
-    Isometry3d x;
-    for (int a = 0; a < 3; a++) { for (int c = 0; c < 3; c++) x.R[a * 3 + c] = b.T(a, c); x.t[a] = b.T(a, 3); }
-    final_transformation_ = x.cast_float();
-    converged_ = b.converged;
-    nr_iterations_ = b.nr_iterations;
-    final_hessian_ = b.H;
+    final_transformation_ = take_result(rs[best]).cast_float();
     output.points.resize(input_->size());
     detail::transform_points(input_->points.data(), output.points.data(), input_->size(), final_transformation_.m);
     return best;
@@ -433,6 +449,29 @@ protected:
   }
   virtual double device_fitness(const double* T16, double max_range) { (void)T16; (void)max_range; throw std::runtime_error("alignBest: not offered by this class"); }
   int multi_grid_blocks_ = 0;
+
+  /// the parameters of the device-resident optimiser loop, from the setters
+  fvh_lm_params lm_params() const {
+    return fvh_lm_params{max_iterations_, rotation_epsilon_, transformation_epsilon_, lm_max_iterations_, lm_init_lambda_factor_,
+                         lsq_optimizer_type_ == LSQ_OPTIMIZER_TYPE::GaussNewton ? 1 : 0};
+  }
+  /// a result of the device LM as the classes hand it on: pose and Hessian row-major
+  static MultiAlignResult unpack(const fvh_lm_result& r) {
+    return MultiAlignResult{Isometry3d::from_colmajor16(r.T).matrix(), detail::transposed6(r.H), r.final_error, r.converged != 0, r.nr_iterations};
+  }
+  /// ... becomes what the getters report (hasConverged, getNumIterations, getFinalHessian); the pose is returned, where it goes is the caller's
+  Isometry3d take_result(const MultiAlignResult& m) {
+    converged_ = m.converged;
+    nr_iterations_ = m.nr_iterations;
+    final_hessian_ = m.H;
+    return Isometry3d::from(m.T);
+  }
+  /// ... straight from the device, with the reference's complaint about a failed LM step (lsq_registration_impl.hpp:69-72)
+  Isometry3d take_result(const fvh_lm_result& r) {
+    const Isometry3d x = take_result(unpack(r));
+    if (r.lm_failed) std::fprintf(stderr, "lm not converged!!\n");
+    return x;
+  }
 
   bool step_optimize(Isometry3d& x0, Isometry3d& delta) {  // :94-104
     return lsq_optimizer_type_ == LSQ_OPTIMIZER_TYPE::GaussNewton ? step_gn(x0, delta) : step_lm(x0, delta);
@@ -512,7 +551,164 @@ namespace detail {
 inline void check(int rc, const char* what, const char* err) {
   if (rc != 0) throw std::runtime_error(std::string(what) + " failed (status " + std::to_string(rc) + "): " + (err ? err : ""));
 }
+
+/// One C ABI call and the label detail::check puts into the exception text when it fails
+template <typename Fn>
+struct DeviceCall {
+  Fn fn;
+  const char* label;
+};
+/// What the registration classes ask of a handle whatever its correspondence model: the table DeviceRegistration works through
+/// (a null fn: the model has no such call)
+template <typename Handle>
+struct DeviceCalls {
+  const char* (*last_error)(const Handle*);
+  DeviceCall<int (*)(Handle*, const float*, int, int)> set_source_cloud_strided, set_target_cloud_strided;
+  DeviceCall<int (*)(Handle*, const double*)> update_correspondences;
+  DeviceCall<int (*)(Handle*, const double*, double*, double*, double*)> compute_error;
+  DeviceCall<int (*)(Handle*, const double*, const fvh_lm_params*, fvh_lm_result*)> align;
+  DeviceCall<int (*)(Handle*, int, const double*, const fvh_lm_params*, fvh_lm_result*, int*)> align_multi;
+  DeviceCall<int (*)(Handle*, const double*, double, double*)> fitness_score;
+  DeviceCall<int (*)(Handle*, int)> set_lm_trace;
+  DeviceCall<int (*)(Handle*, int*, double*)> get_lm_trace;
+  DeviceCall<int (*)(Handle*, const double*, const fvh_lm_params*)> align_async;
+  DeviceCall<int (*)(Handle*, fvh_lm_result*)> align_wait;
+};
+/// VGICP: voxels of the target (FastVGICPCuda, FastVGICP)
+inline constexpr DeviceCalls<fvh_vgicp> kVgicpVoxelCalls{
+    fvh_vgicp_last_error,
+    {fvh_vgicp_set_source_cloud_strided, "set_source_cloud"}, {fvh_vgicp_set_target_cloud_strided, "set_target_cloud"},
+    {fvh_vgicp_update_correspondences, "update_correspondences"}, {fvh_vgicp_compute_error, "compute_error"},
+    {fvh_vgicp_align, "align"}, {fvh_vgicp_align_multi, "align_multi"}, {fvh_vgicp_fitness_score, "fitness_score"},
+    {fvh_vgicp_set_lm_trace, "set_lm_trace"}, {fvh_vgicp_get_lm_trace, "get_lm_trace"},
+    {fvh_vgicp_align_async, "align_async"}, {fvh_vgicp_align_wait, "align_wait"}};
+/// GICP: the nearest target point, on the same handle (FastGICP); no multi-hypothesis and no asynchronous align
+inline constexpr DeviceCalls<fvh_vgicp> kVgicpNearestPointCalls{
+    fvh_vgicp_last_error,
+    {fvh_vgicp_set_source_cloud_strided, "set_source_cloud"}, {fvh_vgicp_set_target_cloud_strided, "set_target_cloud"},
+    {fvh_vgicp_gicp_update_correspondences, "gicp_update_correspondences"}, {fvh_vgicp_gicp_compute_error, "gicp_compute_error"},
+    {fvh_vgicp_gicp_align, "gicp_align"}, {nullptr, "align_multi"}, {fvh_vgicp_fitness_score, "fitness_score"},
+    {fvh_vgicp_set_lm_trace, "set_lm_trace"}, {fvh_vgicp_get_lm_trace, "get_lm_trace"},
+    {nullptr, "align_async"}, {nullptr, "align_wait"}};
+/// NDT (NDTCuda)
+inline constexpr DeviceCalls<fvh_ndt> kNdtCalls{
+    fvh_ndt_last_error,
+    {fvh_ndt_set_source_cloud_strided, "set_source_cloud"}, {fvh_ndt_set_target_cloud_strided, "set_target_cloud"},
+    {fvh_ndt_update_correspondences, "update_correspondences"}, {fvh_ndt_compute_error, "compute_error"},
+    {fvh_ndt_align, "align"}, {fvh_ndt_align_multi, "align_multi"}, {fvh_ndt_fitness_score, "fitness_score"},
+    {fvh_ndt_set_lm_trace, "set_lm_trace"}, {fvh_ndt_get_lm_trace, "get_lm_trace"},
+    {fvh_ndt_align_async, "align_async"}, {fvh_ndt_align_wait, "align_wait"}};
 }  // namespace detail
+
+/// What FastVGICPCuda, FastGICP, FastVGICP and NDTCuda share (no reference counterpart): the device handle and LsqRegistration's
+/// virtuals on top of it, written once against a detail::DeviceCalls table. The classes create and destroy the handle and add what
+/// is theirs: parameters, covariances, voxel maps.
+template <typename Handle, typename PointSource, typename PointTarget>
+class DeviceRegistration : public LsqRegistration<PointSource, PointTarget> {
+  using Base = LsqRegistration<PointSource, PointTarget>;
+
+public:
+  using PointCloudSourceConstPtr = typename Base::PointCloudSourceConstPtr;
+  using PointCloudTargetConstPtr = typename Base::PointCloudTargetConstPtr;
+
+  DeviceRegistration(const DeviceRegistration&) = delete;
+  DeviceRegistration& operator=(const DeviceRegistration&) = delete;
+
+  void clearSource() override { this->input_.reset(); }
+  void clearTarget() override { this->target_.reset(); }
+  double getFitnessScore(double max_range = std::numeric_limits<double>::max()) override {
+    double T16[16];
+    Isometry3d::from(this->final_transformation_).to_colmajor16(T16);
+    return device_fitness(T16, max_range);
+  }
+  Handle* core() { return core_; }
+
+protected:
+  explicit DeviceRegistration(const detail::DeviceCalls<Handle>* calls) : calls_(calls) {}
+
+  /// the first half of setInputSource / setInputTarget: false when `cloud` is the one already set, else it is kept and uploaded
+  bool take_source(const PointCloudSourceConstPtr& cloud) {
+    if (cloud == this->input_) return false;
+    this->input_ = cloud;
+    const detail::XyzView<PointSource> view(*cloud, scratch_xyz_);
+    call(calls_->set_source_cloud_strided, view.data, (int)cloud->size(), view.stride);
+    return true;
+  }
+  bool take_target(const PointCloudTargetConstPtr& cloud) {
+    if (cloud == this->target_) return false;
+    this->target_ = cloud;
+    const detail::XyzView<PointTarget> view(*cloud, scratch_xyz_);
+    call(calls_->set_target_cloud_strided, view.data, (int)cloud->size(), view.stride);
+    return true;
+  }
+  /// the registration as a two-stage pipeline: the classes whose handle offers it make these two public. alignWait() returns the pose
+  /// without transforming a host cloud.
+  void alignAsync(const Matrix4f& guess = Matrix4f::Identity()) {
+    double g16[16];
+    Isometry3d::from(guess).to_colmajor16(g16);
+    const fvh_lm_params p = this->lm_params();
+    call(calls_->align_async, g16, &p);
+  }
+  const Matrix4f& alignWait() {
+    fvh_lm_result r;
+    call(calls_->align_wait, &r);
+    return this->final_transformation_ = this->take_result(r).cast_float();
+  }
+
+  double linearize(const Isometry3d& trans, Matrix6d* H, Vector6d* b) override {
+    double T16[16], err = 0, Hc[36];
+    trans.to_colmajor16(T16);
+    call(calls_->update_correspondences, T16);
+    call(calls_->compute_error, T16, (H && b) ? Hc : nullptr, (H && b) ? b->data() : nullptr, &err);
+    if (H && b) *H = detail::transposed6(Hc);
+    return err;
+  }
+  double compute_error(const Isometry3d& trans) override {
+    double T16[16], err = 0;
+    trans.to_colmajor16(T16);
+    call(calls_->compute_error, T16, nullptr, nullptr, &err);
+    return err;
+  }
+  /// the whole LM loop on the device; with setDebugPrint(true) the rows it recorded are printed afterwards
+  bool device_align(Isometry3d& x0) override {
+    double g16[16];
+    x0.to_colmajor16(g16);
+    const fvh_lm_params p = this->lm_params();
+    fvh_lm_result r;
+    call(calls_->set_lm_trace, this->lm_debug_print_ ? 1 : 0);
+    call(calls_->align, g16, &p, &r);
+    if (this->lm_debug_print_) {
+      int n = 0;
+      call(calls_->get_lm_trace, &n, nullptr);
+      std::vector<double> rows(6 * (size_t)n);
+      if (n) call(calls_->get_lm_trace, &n, rows.data());
+      detail::print_lm_trace(rows);
+    }
+    x0 = this->take_result(r);
+    return true;
+  }
+  void device_align_multi(int k, const double* guesses16, const fvh_lm_params* p, fvh_lm_result* results, int* grid_blocks) override {
+    if (!calls_->align_multi.fn) return Base::device_align_multi(k, guesses16, p, results, grid_blocks);  // (throws: not offered)
+    call(calls_->align_multi, k, guesses16, p, results, grid_blocks);
+  }
+  double device_fitness(const double* T16, double max_range) override {
+    double score = 0;
+    call(calls_->fitness_score, T16, max_range, &score);
+    return score;
+  }
+
+  /// throws "<what> failed (status N): <the handle's last error>" unless rc is FVH_OK
+  void call(int rc, const char* what) const { detail::check(rc, what, calls_->last_error(core_)); }
+  template <typename Fn, typename... Args>
+  void call(const detail::DeviceCall<Fn>& c, Args... args) const {
+    if (!c.fn) throw std::runtime_error(std::string(c.label) + ": not offered by this class");
+    call(c.fn(core_, args...), c.label);
+  }
+
+  const detail::DeviceCalls<Handle>* calls_;
+  Handle* core_ = nullptr;
+  std::vector<float> scratch_xyz_;  // only used for point types that are not 12 / 16 bytes of packed xyz
+};
 
 /// A snapshot of FastVGICPCuda's incremental target map (exportTargetMap / importTargetMap; C ABI: fvh_vgicp_voxelmap_export / _import):
 /// per voxel coords[3], the device's ten fp64 sums and an age, rows in ascending packed-key order (z-major, then y, then x).
@@ -589,9 +785,12 @@ inline TargetMapSnapshot read_map_file(const std::string& path) {
 
 /// FastVGICPCuda (fast_vgicp_cuda.hpp:24-85, impl/fast_vgicp_cuda_impl.hpp)
 template <typename PointSource, typename PointTarget>
-class FastVGICPCuda : public LsqRegistration<PointSource, PointTarget> {
-  using Base = LsqRegistration<PointSource, PointTarget>;
+class FastVGICPCuda : public DeviceRegistration<fvh_vgicp, PointSource, PointTarget> {
+  using Base = DeviceRegistration<fvh_vgicp, PointSource, PointTarget>;
+  using Base::call;
+  using Base::core_;
   using Base::input_;
+  using Base::scratch_xyz_;
   using Base::target_;
 
 public:
@@ -599,14 +798,12 @@ public:
   using PointCloudSourceConstPtr = typename Base::PointCloudSourceConstPtr;
   using PointCloudTargetConstPtr = typename Base::PointCloudTargetConstPtr;
 
-  explicit FastVGICPCuda(int device = 0) {  // fast_vgicp_cuda_impl.hpp:21-32
+  explicit FastVGICPCuda(int device = 0) : Base(&detail::kVgicpVoxelCalls) {  // fast_vgicp_cuda_impl.hpp:21-32
     detail::check(fvh_vgicp_create(device, &core_), "fvh_vgicp_create", "cannot create the HIP engine (no GPU? there is no CPU fallback)");
     call(fvh_vgicp_set_resolution(core_, voxel_resolution_), "set_resolution");
     call(fvh_vgicp_set_kernel_params(core_, 0.5, 3.0), "set_kernel_params");
   }
   ~FastVGICPCuda() override { if (core_) fvh_vgicp_destroy(core_); }
-  FastVGICPCuda(const FastVGICPCuda&) = delete;
-  FastVGICPCuda& operator=(const FastVGICPCuda&) = delete;
 
   void setCorrespondenceRandomness(int) {}  // empty in the reference too (:38): k stays 20
   void setResolution(double resolution) { call(fvh_vgicp_set_resolution(core_, resolution), "set_resolution"); }
@@ -636,18 +833,12 @@ public:
     call(fvh_vgicp_swap_source_and_target(core_), "swap_source_and_target");
     input_.swap(target_);
   }
-  void clearSource() override { input_.reset(); }
-  void clearTarget() override { target_.reset(); }
 
   void setInputSource(const PointCloudSourceConstPtr& cloud) override {  // :85-111
-    if (cloud == input_) return;
-    input_ = cloud;
-    const detail::XyzView<PointSource> view(*cloud, scratch_xyz_);
-    call(fvh_vgicp_set_source_cloud_strided(core_, view.data, (int)cloud->size(), view.stride), "set_source_cloud");
+    if (!this->take_source(cloud)) return;
     switch (effective_neighbor_method(cloud->size())) {
       case NearestNeighborMethod::CPU_PARALLEL_KDTREE: {
-        const std::vector<float> xyz = detail::pack_xyz(*cloud);
-        const std::vector<int> nb = find_neighbors_parallel_kdtree(k_correspondences_, xyz);
+        const std::vector<int> nb = find_neighbors_parallel_kdtree(*cloud);
         call(fvh_vgicp_set_source_neighbors(core_, k_correspondences_, nb.data()), "set_source_neighbors");
         call(fvh_vgicp_calculate_source_covariances(core_, (int)regularization_method_), "calculate_source_covariances");
       } break;
@@ -662,14 +853,11 @@ public:
   }
   void setInputTarget(const PointCloudTargetConstPtr& cloud) override {  // :114-141
     if (cloud == target_) return;
-    target_ = cloud;
     incremental_target_ = false;  // (create_target_voxelmap below replaces an incremental map by the batch map of this cloud)
-    const detail::XyzView<PointTarget> view(*cloud, scratch_xyz_);
-    call(fvh_vgicp_set_target_cloud_strided(core_, view.data, (int)cloud->size(), view.stride), "set_target_cloud");
+    this->take_target(cloud);
     switch (effective_neighbor_method(cloud->size())) {
       case NearestNeighborMethod::CPU_PARALLEL_KDTREE: {
-        const std::vector<float> xyz = detail::pack_xyz(*cloud);
-        const std::vector<int> nb = find_neighbors_parallel_kdtree(k_correspondences_, xyz);
+        const std::vector<int> nb = find_neighbors_parallel_kdtree(*cloud);
         call(fvh_vgicp_set_target_neighbors(core_, k_correspondences_, nb.data()), "set_target_neighbors");
         call(fvh_vgicp_calculate_target_covariances(core_, (int)regularization_method_), "calculate_target_covariances");
       } break;
@@ -683,14 +871,6 @@ public:
     }
     call(fvh_vgicp_create_target_voxelmap(core_), "create_target_voxelmap");
   }
-
-  double getFitnessScore(double max_range = std::numeric_limits<double>::max()) override {
-    double T16[16], score = 0;
-    Isometry3d::from(this->final_transformation_).to_colmajor16(T16);
-    call(fvh_vgicp_fitness_score(core_, T16, max_range, &score), "fitness_score");
-    return score;
-  }
-  fvh_vgicp* core() { return core_; }
 
   // ---- incremental target map (no reference counterpart; C ABI: fvh_vgicp_map_begin / _insert_source / _prune). Scan-to-map loops:
   //     beginIncrementalTarget(); setInputSource(scan 0); insertSourceIntoTarget(Identity);
@@ -780,69 +960,10 @@ public:
       else call(fvh_vgicp_calculate_source_covariances(core_, (int)regularization_method_), "calculate_source_covariances");
     }
   }
-  void alignAsync(const Matrix4f& guess = Matrix4f::Identity()) {
-    double g16[16];
-    Isometry3d::from(guess).to_colmajor16(g16);
-    fvh_lm_params p{this->max_iterations_, this->rotation_epsilon_, this->transformation_epsilon_, this->lm_max_iterations_, this->lm_init_lambda_factor_,
-                    this->lsq_optimizer_type_ == LSQ_OPTIMIZER_TYPE::GaussNewton ? 1 : 0};
-    call(fvh_vgicp_align_async(core_, g16, &p), "align_async");
-  }
-  const Matrix4f& alignWait() {
-    fvh_lm_result r;
-    call(fvh_vgicp_align_wait(core_, &r), "align_wait");
-    this->final_transformation_ = Isometry3d::from_colmajor16(r.T).cast_float();
-    this->converged_ = r.converged != 0;
-    this->nr_iterations_ = r.nr_iterations;
-    for (int i = 0; i < 6; i++) for (int j = 0; j < 6; j++) this->final_hessian_[i * 6 + j] = r.H[j * 6 + i];
-    if (r.lm_failed) std::fprintf(stderr, "lm not converged!!\n");
-    return this->final_transformation_;
-  }
+  using Base::alignAsync;
+  using Base::alignWait;
 
 protected:
-  double linearize(const Isometry3d& trans, Matrix6d* H, Vector6d* b) override {  // :170-173
-    double T16[16], err = 0, Hc[36];
-    trans.to_colmajor16(T16);
-    call(fvh_vgicp_update_correspondences(core_, T16), "update_correspondences");
-    call(fvh_vgicp_compute_error(core_, T16, (H && b) ? Hc : nullptr, (H && b) ? b->data() : nullptr, &err), "compute_error");
-    if (H && b) for (int i = 0; i < 6; i++) for (int j = 0; j < 6; j++) (*H)[i * 6 + j] = Hc[j * 6 + i];
-    return err;
-  }
-  double compute_error(const Isometry3d& trans) override {  // :176-178
-    double T16[16], err = 0;
-    trans.to_colmajor16(T16);
-    call(fvh_vgicp_compute_error(core_, T16, nullptr, nullptr, &err), "compute_error");
-    return err;
-  }
-  void device_align_multi(int k, const double* guesses16, const fvh_lm_params* p, fvh_lm_result* results, int* grid_blocks) override {
-    call(fvh_vgicp_align_multi(core_, k, guesses16, p, results, grid_blocks), "align_multi");
-  }
-  double device_fitness(const double* T16, double max_range) override {
-    double score = 0;
-    call(fvh_vgicp_fitness_score(core_, T16, max_range, &score), "fitness_score");
-    return score;
-  }
-  bool device_align(Isometry3d& x0) override {
-    double g16[16];
-    x0.to_colmajor16(g16);
-    fvh_lm_params p{this->max_iterations_, this->rotation_epsilon_, this->transformation_epsilon_, this->lm_max_iterations_, this->lm_init_lambda_factor_,
-                    this->lsq_optimizer_type_ == LSQ_OPTIMIZER_TYPE::GaussNewton ? 1 : 0};
-    fvh_lm_result r;
-    call(fvh_vgicp_set_lm_trace(core_, this->lm_debug_print_ ? 1 : 0), "set_lm_trace");
-    call(fvh_vgicp_align(core_, g16, &p, &r), "align");
-    if (this->lm_debug_print_) {
-      int n = 0;
-      call(fvh_vgicp_get_lm_trace(core_, &n, nullptr), "get_lm_trace");
-      std::vector<double> rows(6 * (size_t)n);
-      if (n) call(fvh_vgicp_get_lm_trace(core_, &n, rows.data()), "get_lm_trace");
-      detail::print_lm_trace(rows);
-    }
-    x0 = Isometry3d::from_colmajor16(r.T);
-    this->converged_ = r.converged != 0;
-    this->nr_iterations_ = r.nr_iterations;
-    for (int i = 0; i < 6; i++) for (int j = 0; j < 6; j++) this->final_hessian_[i * 6 + j] = r.H[j * 6 + i];
-    if (r.lm_failed) std::fprintf(stderr, "lm not converged!!\n");
-    return true;
-  }
   /// the enum value the switch statements act on: the default one is served by the device search unless the host tree was asked for
   /// (a cloud with fewer points than k keeps the host path: the reference pads those lists with index 0, :155,162)
   NearestNeighborMethod effective_neighbor_method(size_t n_points) const {
@@ -853,23 +974,12 @@ protected:
     static const bool on = [] { const char* v = std::getenv("FVH_HOST_KDTREE"); return v && std::atoi(v) != 0; }();
     return on;
   }
-  /// find_neighbors_parallel_kdtree (:152-167): host kd-tree + OpenMP
-  std::vector<int> find_neighbors_parallel_kdtree(int k, const std::vector<float>& xyz) const {
-    const int n = (int)(xyz.size() / 3);
-    host::KdTree tree(xyz.data(), n);
-    std::vector<int> neighbors((size_t)n * k);
-    const int threads = host::omp_threads_for(n);  // hundreds of threads on a 17k-point loop only add contention
-#pragma omp parallel for schedule(guided, 8) num_threads(threads)
-    for (int i = 0; i < n; i++) {
-      int* row = &neighbors[(size_t)i * k];
-      tree.knn(&xyz[3 * (size_t)i], k, row);
-      // a cloud with fewer than k points: the reference's zero-initialised vector keeps index 0 in the unfilled entries (:155,162)
-      for (int j = 0; j < k; j++) if (row[j] < 0) row[j] = 0;
-    }
-    return neighbors;
+  /// find_neighbors_parallel_kdtree (:152-167): host kd-tree + OpenMP (hundreds of threads on a 17k-point loop only add contention)
+  template <typename CloudT>
+  std::vector<int> find_neighbors_parallel_kdtree(const CloudT& cloud) const {
+    return detail::host_kdtree_neighbors(cloud, k_correspondences_, host::omp_threads_for((int)cloud.size()));
   }
   bool has_device_target() const override { return incremental_target_; }
-  void call(int rc, const char* what) const { detail::check(rc, what, fvh_vgicp_last_error(core_)); }
 
 private:
   bool incremental_target_ = false;                                                              // beginIncrementalTarget .. setInputTarget
@@ -880,18 +990,18 @@ private:
   bool host_kdtree_ = host_kdtree_default();                                                     // setHostKdTree
   int prepared_stages_ = 2;                                                                         // prepareNextSourceDevice
   PointCloudSourceConstPtr prepared_cloud_;                                                         // prepareNextSource (host cloud): becomes input_ on adoption
-  fvh_vgicp* core_ = nullptr;
-  std::vector<float> scratch_xyz_;  // only used for point types that are not 12 / 16 bytes of packed xyz
 };
 
 /// FastGICP (gicp/fast_gicp.hpp:24-98, impl/fast_gicp_impl.hpp) on the HIP engine: the reference class is CPU/OpenMP only;
 /// here the covariances (exact k-NN + regularisation), the nearest-target-point correspondences and the cost sums run on
 /// the device; the LM recursion runs on the device too (setUseDeviceLM(false): the reference's host loop, LsqRegistration::step_lm).
 template <typename PointSource, typename PointTarget>
-class FastGICP : public LsqRegistration<PointSource, PointTarget> {
-  using Base = LsqRegistration<PointSource, PointTarget>;
+class FastGICP : public DeviceRegistration<fvh_vgicp, PointSource, PointTarget> {
+  using Base = DeviceRegistration<fvh_vgicp, PointSource, PointTarget>;
 
 protected:
+  using Base::call;
+  using Base::core_;
   using Base::input_;
   using Base::target_;
 
@@ -900,12 +1010,10 @@ public:
   using PointCloudSourceConstPtr = typename Base::PointCloudSourceConstPtr;
   using PointCloudTargetConstPtr = typename Base::PointCloudTargetConstPtr;
 
-  explicit FastGICP(int device = 0) {  // fast_gicp_impl.hpp:9-23
+  explicit FastGICP(int device = 0) : Base(&detail::kVgicpNearestPointCalls) {  // fast_gicp_impl.hpp:9-23
     detail::check(fvh_vgicp_create(device, &core_), "fvh_vgicp_create", "cannot create the HIP engine (no GPU? there is no CPU fallback)");
   }
   ~FastGICP() override { if (core_) fvh_vgicp_destroy(core_); }
-  FastGICP(const FastGICP&) = delete;
-  FastGICP& operator=(const FastGICP&) = delete;
 
   void setNumThreads(int) {}  // :29-38: OpenMP threads of the CPU class; the device needs none
   void setCorrespondenceRandomness(int k) { k_correspondences_ = k; }  // :41-43
@@ -916,22 +1024,12 @@ public:
     call(fvh_vgicp_gicp_swap_source_and_target(core_), "gicp_swap_source_and_target");
     input_.swap(target_);
   }
-  void clearSource() override { input_.reset(); }  // :65-68
-  void clearTarget() override { target_.reset(); }  // :71-74
 
   void setInputSource(const PointCloudSourceConstPtr& cloud) override {  // :77-85 (covariances: :103-112, computed eagerly here)
-    if (cloud == input_) return;
-    input_ = cloud;
-    const detail::XyzView<PointSource> view(*cloud, scratch_xyz_);
-    call(fvh_vgicp_set_source_cloud_strided(core_, view.data, (int)cloud->size(), view.stride), "set_source_cloud");
-    estimate_covariances(*cloud, true);
+    if (this->take_source(cloud)) estimate_covariances(*cloud, true);
   }
   void setInputTarget(const PointCloudTargetConstPtr& cloud) override {  // :88-95
-    if (cloud == target_) return;
-    target_ = cloud;
-    const detail::XyzView<PointTarget> view(*cloud, scratch_xyz_);
-    call(fvh_vgicp_set_target_cloud_strided(core_, view.data, (int)cloud->size(), view.stride), "set_target_cloud");
-    estimate_covariances(*cloud, false);
+    if (this->take_target(cloud)) estimate_covariances(*cloud, false);
   }
   /// gicp/fast_gicp.hpp:60-70: covariances computed elsewhere / read back. The reference carries them as 4x4 doubles with a
   /// zero last row and column; here a covariance is its 3x3 block, 9 doubles per point (symmetric, so any major).
@@ -947,14 +1045,6 @@ public:
   Covariances getSourceCovariances() const { return get_covariances(input_ ? input_->size() : 0, true); }
   Covariances getTargetCovariances() const { return get_covariances(target_ ? target_->size() : 0, false); }
 
-  double getFitnessScore(double max_range = std::numeric_limits<double>::max()) override {
-    double T16[16], score = 0;
-    Isometry3d::from(this->final_transformation_).to_colmajor16(T16);
-    call(fvh_vgicp_fitness_score(core_, T16, max_range, &score), "fitness_score");
-    return score;
-  }
-  fvh_vgicp* core() { return core_; }
-
 protected:
   Covariances get_covariances(size_t n, bool source) const {
     std::vector<float> f(9 * n);
@@ -963,45 +1053,6 @@ protected:
     for (size_t i = 0; i < n; i++) for (int j = 0; j < 9; j++) out[i][j] = f[9 * i + j];
     return out;
   }
-  /// the whole LM loop on the device (fvh_vgicp_gicp_align): one nearest-point search + one cost launch per LM transition, no host round trip
-  bool device_align(Isometry3d& x0) override {
-    double g16[16];
-    x0.to_colmajor16(g16);
-    fvh_lm_params p{this->max_iterations_, this->rotation_epsilon_, this->transformation_epsilon_, this->lm_max_iterations_, this->lm_init_lambda_factor_,
-                    this->lsq_optimizer_type_ == LSQ_OPTIMIZER_TYPE::GaussNewton ? 1 : 0};
-    fvh_lm_result r;
-    call(fvh_vgicp_set_lm_trace(core_, this->lm_debug_print_ ? 1 : 0), "set_lm_trace");
-    call(fvh_vgicp_gicp_align(core_, g16, &p, &r), "gicp_align");
-    if (this->lm_debug_print_) {
-      int n = 0;
-      call(fvh_vgicp_get_lm_trace(core_, &n, nullptr), "get_lm_trace");
-      std::vector<double> rows(6 * (size_t)n);
-      if (n) call(fvh_vgicp_get_lm_trace(core_, &n, rows.data()), "get_lm_trace");
-      detail::print_lm_trace(rows);
-    }
-    x0 = Isometry3d::from_colmajor16(r.T);
-    this->converged_ = r.converged != 0;
-    this->nr_iterations_ = r.nr_iterations;
-    for (int i = 0; i < 6; i++) for (int j = 0; j < 6; j++) this->final_hessian_[i * 6 + j] = r.H[j * 6 + i];
-    if (r.lm_failed) std::fprintf(stderr, "lm not converged!!\n");
-    return true;
-  }
-  double linearize(const Isometry3d& trans, Matrix6d* H, Vector6d* b) override {  // :159-213
-    double T16[16], err = 0, Hc[36];
-    trans.to_colmajor16(T16);
-    call(fvh_vgicp_gicp_update_correspondences(core_, T16), "gicp_update_correspondences");
-    call(fvh_vgicp_gicp_compute_error(core_, T16, (H && b) ? Hc : nullptr, (H && b) ? b->data() : nullptr, &err), "gicp_compute_error");
-    if (H && b) for (int i = 0; i < 6; i++) for (int j = 0; j < 6; j++) (*H)[i * 6 + j] = Hc[j * 6 + i];
-    return err;
-  }
-  double compute_error(const Isometry3d& trans) override {  // :216-240
-    double T16[16], err = 0;
-    trans.to_colmajor16(T16);
-    call(fvh_vgicp_gicp_compute_error(core_, T16, nullptr, nullptr, &err), "gicp_compute_error");
-    return err;
-  }
-  void call(int rc, const char* what) const { detail::check(rc, what, fvh_vgicp_last_error(core_)); }
-
   /// calculate_covariances (fast_gicp_impl.hpp:244-301): k nearest neighbours of every point + regularisation. The device's exact
   /// search serves k <= 64 on clouds of at least k points; what the reference's kd-tree also accepts -- larger k, or fewer points than
   /// k (nearestKSearch then returns them all; the unfilled entries of its index vector stay 0) -- goes through the host kd-tree.
@@ -1014,14 +1065,7 @@ protected:
       call(source ? fvh_vgicp_find_source_neighbors(core_, k) : fvh_vgicp_find_target_neighbors(core_, k), "find_neighbors");
     } else {
       if (k > 64) throw std::invalid_argument("setCorrespondenceRandomness: more than 64 neighbours per point are not supported by the covariance kernel");
-      const std::vector<float> xyz = detail::pack_xyz(cloud);
-      host::KdTree tree(xyz.data(), n);
-      std::vector<int> nb((size_t)n * k);
-      for (int i = 0; i < n; i++) {
-        int* row = &nb[(size_t)i * k];
-        tree.knn(&xyz[3 * (size_t)i], k, row);
-        for (int j = 0; j < k; j++) if (row[j] < 0) row[j] = 0;
-      }
+      const std::vector<int> nb = detail::host_kdtree_neighbors(cloud, k, 1);
       call(source ? fvh_vgicp_set_source_neighbors(core_, k, nb.data()) : fvh_vgicp_set_target_neighbors(core_, k, nb.data()), "set_neighbors");
     }
     call(source ? fvh_vgicp_calculate_source_covariances(core_, (int)regularization_method_) : fvh_vgicp_calculate_target_covariances(core_, (int)regularization_method_), "calculate_covariances");
@@ -1030,8 +1074,6 @@ protected:
 protected:
   int k_correspondences_ = 20;                                                // :17
   RegularizationMethod regularization_method_ = RegularizationMethod::PLANE;  // :21
-  fvh_vgicp* core_ = nullptr;
-  std::vector<float> scratch_xyz_;  // only used for point types that are not 12 / 16 bytes of packed xyz
 };
 
 /// FastVGICP -- the reference's CPU / OpenMP class (gicp/fast_vgicp.hpp:28-78, impl/fast_vgicp_impl.hpp) -- served by the same HIP
@@ -1052,6 +1094,7 @@ public:
   using PointCloudTargetConstPtr = typename Base::PointCloudTargetConstPtr;
 
   explicit FastVGICP(int device = 0) : Base(device) {  // fast_vgicp_impl.hpp:19-25
+    this->calls_ = &detail::kVgicpVoxelCalls;  // what it replaces in FastGICP: voxel correspondences, and the calls only they have
     this->call(fvh_vgicp_set_resolution(core_, 1.0), "set_resolution");
     this->call(fvh_vgicp_set_neighbor_search_method(core_, (int)NeighborSearchMethod::DIRECT1, -1.0), "set_neighbor_search_method");
   }
@@ -1085,96 +1128,32 @@ public:
     Base::setInputTarget(cloud);
     this->call(fvh_vgicp_create_target_voxelmap(core_), "create_target_voxelmap");
   }
-
-protected:
-  double linearize(const Isometry3d& trans, Matrix6d* H, Vector6d* b) override {  // :119-178
-    double T16[16], err = 0, Hc[36];
-    trans.to_colmajor16(T16);
-    this->call(fvh_vgicp_update_correspondences(core_, T16), "update_correspondences");
-    this->call(fvh_vgicp_compute_error(core_, T16, (H && b) ? Hc : nullptr, (H && b) ? b->data() : nullptr, &err), "compute_error");
-    if (H && b) for (int i = 0; i < 6; i++) for (int j = 0; j < 6; j++) (*H)[i * 6 + j] = Hc[j * 6 + i];
-    return err;
-  }
-  double compute_error(const Isometry3d& trans) override {  // :181-204
-    double T16[16], err = 0;
-    trans.to_colmajor16(T16);
-    this->call(fvh_vgicp_compute_error(core_, T16, nullptr, nullptr, &err), "compute_error");
-    return err;
-  }
-  void device_align_multi(int k, const double* guesses16, const fvh_lm_params* p, fvh_lm_result* results, int* grid_blocks) override {
-    this->call(fvh_vgicp_align_multi(core_, k, guesses16, p, results, grid_blocks), "align_multi");
-  }
-  double device_fitness(const double* T16, double max_range) override {
-    double score = 0;
-    this->call(fvh_vgicp_fitness_score(core_, T16, max_range, &score), "fitness_score");
-    return score;
-  }
-  bool device_align(Isometry3d& x0) override {
-    double g16[16];
-    x0.to_colmajor16(g16);
-    fvh_lm_params p{this->max_iterations_, this->rotation_epsilon_, this->transformation_epsilon_, this->lm_max_iterations_, this->lm_init_lambda_factor_,
-                    this->lsq_optimizer_type_ == LSQ_OPTIMIZER_TYPE::GaussNewton ? 1 : 0};
-    fvh_lm_result r;
-    this->call(fvh_vgicp_set_lm_trace(core_, this->lm_debug_print_ ? 1 : 0), "set_lm_trace");
-    this->call(fvh_vgicp_align(core_, g16, &p, &r), "align");
-    if (this->lm_debug_print_) {
-      int n = 0;
-      this->call(fvh_vgicp_get_lm_trace(core_, &n, nullptr), "get_lm_trace");
-      std::vector<double> rows(6 * (size_t)n);
-      if (n) this->call(fvh_vgicp_get_lm_trace(core_, &n, rows.data()), "get_lm_trace");
-      detail::print_lm_trace(rows);
-    }
-    x0 = Isometry3d::from_colmajor16(r.T);
-    this->converged_ = r.converged != 0;
-    this->nr_iterations_ = r.nr_iterations;
-    for (int i = 0; i < 6; i++) for (int j = 0; j < 6; j++) this->final_hessian_[i * 6 + j] = r.H[j * 6 + i];
-    if (r.lm_failed) std::fprintf(stderr, "lm not converged!!\n");
-    return true;
-  }
 };
 
 /// NDTCuda (ndt_cuda.hpp:23-69, impl/ndt_cuda_impl.hpp)
 template <typename PointSource, typename PointTarget>
-class NDTCuda : public LsqRegistration<PointSource, PointTarget> {
-  using Base = LsqRegistration<PointSource, PointTarget>;
+class NDTCuda : public DeviceRegistration<fvh_ndt, PointSource, PointTarget> {
+  using Base = DeviceRegistration<fvh_ndt, PointSource, PointTarget>;
+  using Base::call;
+  using Base::core_;
   using Base::input_;
+  using Base::scratch_xyz_;
   using Base::target_;
 
 public:
   using PointCloudSourceConstPtr = typename Base::PointCloudSourceConstPtr;
   using PointCloudTargetConstPtr = typename Base::PointCloudTargetConstPtr;
 
-  explicit NDTCuda(int device = 0) { detail::check(fvh_ndt_create(device, &core_), "fvh_ndt_create", "cannot create the HIP engine (no GPU? there is no CPU fallback)"); }
+  explicit NDTCuda(int device = 0) : Base(&detail::kNdtCalls) { detail::check(fvh_ndt_create(device, &core_), "fvh_ndt_create", "cannot create the HIP engine (no GPU? there is no CPU fallback)"); }
   ~NDTCuda() override { if (core_) fvh_ndt_destroy(core_); }
-  NDTCuda(const NDTCuda&) = delete;
-  NDTCuda& operator=(const NDTCuda&) = delete;
 
   void setDistanceMode(NDTDistanceMode mode) { call(fvh_ndt_set_distance_mode(core_, (int)mode), "set_distance_mode"); }
   void setResolution(double resolution) { call(fvh_ndt_set_resolution(core_, resolution), "set_resolution"); }
   void setNeighborSearchMethod(NeighborSearchMethod method, double radius = -1.0) { call(fvh_ndt_set_neighbor_search_method(core_, (int)method, radius), "set_neighbor_search_method"); }
 
   void swapSourceAndTarget() override { call(fvh_ndt_swap_source_and_target(core_), "swap_source_and_target"); input_.swap(target_); }
-  void clearSource() override { input_.reset(); }
-  void clearTarget() override { target_.reset(); }
-  void setInputSource(const PointCloudSourceConstPtr& cloud) override {  // ndt_cuda_impl.hpp:52-60
-    if (cloud == input_) return;
-    input_ = cloud;
-    const detail::XyzView<PointSource> view(*cloud, scratch_xyz_);
-    call(fvh_ndt_set_source_cloud_strided(core_, view.data, (int)cloud->size(), view.stride), "set_source_cloud");
-  }
-  void setInputTarget(const PointCloudTargetConstPtr& cloud) override {  // :63-73
-    if (cloud == target_) return;
-    target_ = cloud;
-    const detail::XyzView<PointTarget> view(*cloud, scratch_xyz_);
-    call(fvh_ndt_set_target_cloud_strided(core_, view.data, (int)cloud->size(), view.stride), "set_target_cloud");
-  }
-  double getFitnessScore(double max_range = std::numeric_limits<double>::max()) override {
-    double T16[16], score = 0;
-    Isometry3d::from(this->final_transformation_).to_colmajor16(T16);
-    call(fvh_ndt_fitness_score(core_, T16, max_range, &score), "fitness_score");
-    return score;
-  }
-  fvh_ndt* core() { return core_; }
+  void setInputSource(const PointCloudSourceConstPtr& cloud) override { this->take_source(cloud); }  // ndt_cuda_impl.hpp:52-60
+  void setInputTarget(const PointCloudTargetConstPtr& cloud) override { this->take_target(cloud); }  // :63-73
 
   // ---- frame streams as a two-stage pipeline (no reference counterpart; C ABI: fvh_ndt_align_async / _wait, fvh_ndt_prepare_source_device /
   // _adopt_prepared_source). kitti.cpp:95-128 with the preparation of frame k+1 hidden under the registration of frame k:
@@ -1191,23 +1170,8 @@ public:
     prepared_cloud_ = cloud;
   }
   void adoptPreparedSource() { call(fvh_ndt_adopt_prepared_source(core_), "adopt_prepared_source"); input_ = prepared_cloud_; prepared_cloud_.reset(); }
-  void alignAsync(const Matrix4f& guess = Matrix4f::Identity()) {
-    double g16[16];
-    Isometry3d::from(guess).to_colmajor16(g16);
-    fvh_lm_params p{this->max_iterations_, this->rotation_epsilon_, this->transformation_epsilon_, this->lm_max_iterations_, this->lm_init_lambda_factor_,
-                    this->lsq_optimizer_type_ == LSQ_OPTIMIZER_TYPE::GaussNewton ? 1 : 0};
-    call(fvh_ndt_align_async(core_, g16, &p), "align_async");
-  }
-  const Matrix4f& alignWait() {
-    fvh_lm_result r;
-    call(fvh_ndt_align_wait(core_, &r), "align_wait");
-    this->final_transformation_ = Isometry3d::from_colmajor16(r.T).cast_float();
-    this->converged_ = r.converged != 0;
-    this->nr_iterations_ = r.nr_iterations;
-    for (int i = 0; i < 6; i++) for (int j = 0; j < 6; j++) this->final_hessian_[i * 6 + j] = r.H[j * 6 + i];
-    if (r.lm_failed) std::fprintf(stderr, "lm not converged!!\n");
-    return this->final_transformation_;
-  }
+  using Base::alignAsync;  // (not preceded by create_voxelmaps, unlike align and alignMulti below)
+  using Base::alignWait;
 
 protected:
   void computeTransformation(typename Base::PointCloudSource& output, const Matrix4f& guess) override {  // :76-79
@@ -1216,54 +1180,10 @@ protected:
   }
   void device_align_multi(int k, const double* guesses16, const fvh_lm_params* p, fvh_lm_result* results, int* grid_blocks) override {
     call(fvh_ndt_create_voxelmaps(core_), "create_voxelmaps");
-    call(fvh_ndt_align_multi(core_, k, guesses16, p, results, grid_blocks), "align_multi");
+    Base::device_align_multi(k, guesses16, p, results, grid_blocks);
   }
-  double device_fitness(const double* T16, double max_range) override {
-    double score = 0;
-    call(fvh_ndt_fitness_score(core_, T16, max_range, &score), "fitness_score");
-    return score;
-  }
-  double linearize(const Isometry3d& trans, Matrix6d* H, Vector6d* b) override {
-    double T16[16], err = 0, Hc[36];
-    trans.to_colmajor16(T16);
-    call(fvh_ndt_update_correspondences(core_, T16), "update_correspondences");
-    call(fvh_ndt_compute_error(core_, T16, (H && b) ? Hc : nullptr, (H && b) ? b->data() : nullptr, &err), "compute_error");
-    if (H && b) for (int i = 0; i < 6; i++) for (int j = 0; j < 6; j++) (*H)[i * 6 + j] = Hc[j * 6 + i];
-    return err;
-  }
-  double compute_error(const Isometry3d& trans) override {
-    double T16[16], err = 0;
-    trans.to_colmajor16(T16);
-    call(fvh_ndt_compute_error(core_, T16, nullptr, nullptr, &err), "compute_error");
-    return err;
-  }
-  bool device_align(Isometry3d& x0) override {
-    double g16[16];
-    x0.to_colmajor16(g16);
-    fvh_lm_params p{this->max_iterations_, this->rotation_epsilon_, this->transformation_epsilon_, this->lm_max_iterations_, this->lm_init_lambda_factor_,
-                    this->lsq_optimizer_type_ == LSQ_OPTIMIZER_TYPE::GaussNewton ? 1 : 0};
-    fvh_lm_result r;
-    call(fvh_ndt_set_lm_trace(core_, this->lm_debug_print_ ? 1 : 0), "set_lm_trace");
-    call(fvh_ndt_align(core_, g16, &p, &r), "align");
-    if (this->lm_debug_print_) {
-      int n = 0;
-      call(fvh_ndt_get_lm_trace(core_, &n, nullptr), "get_lm_trace");
-      std::vector<double> rows(6 * (size_t)n);
-      if (n) call(fvh_ndt_get_lm_trace(core_, &n, rows.data()), "get_lm_trace");
-      detail::print_lm_trace(rows);
-    }
-    x0 = Isometry3d::from_colmajor16(r.T);
-    this->converged_ = r.converged != 0;
-    this->nr_iterations_ = r.nr_iterations;
-    for (int i = 0; i < 6; i++) for (int j = 0; j < 6; j++) this->final_hessian_[i * 6 + j] = r.H[j * 6 + i];
-    if (r.lm_failed) std::fprintf(stderr, "lm not converged!!\n");
-    return true;
-  }
-  void call(int rc, const char* what) const { detail::check(rc, what, fvh_ndt_last_error(core_)); }
 
 private:
-  fvh_ndt* core_ = nullptr;
-  std::vector<float> scratch_xyz_;
   PointCloudSourceConstPtr prepared_cloud_;  // prepareNextSource (host cloud): becomes input_ on adoption
 };
 

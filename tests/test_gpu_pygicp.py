@@ -343,3 +343,46 @@ def test_pipelined_calls_of_ndt_equal_the_sequential_loop():
         assert reg.has_converged()
         assert np.abs(T - seq[i - 1]).max() < 1e-6, i
         reg.swap_source_and_target()
+
+
+def test_class_errors_name_the_call_and_carry_the_handles_text(pygicp):
+    """What the classes throw when the library refuses a call: "<label> failed (status N): <the handle's last_error text>", the label being the
+    C call without its fvh_<handle>_ prefix (cloud setters: without _strided). Checked through the real library on the refusals a caller can
+    reach without breaking anything; the text is compared with what the same misuse of a bare handle reports."""
+    import re
+    from fast_gicp_amd import capi
+    rng = np.random.default_rng(11)
+    cloud = rng.uniform(-2.0, 2.0, size=(64, 3))
+
+    def library_text(handle, misuse):
+        with pytest.raises(capi.FvhError) as e:
+            misuse(handle)
+        handle.close()
+        return re.match(r"fvh_\w+: status \d+: (.*)$", str(e.value), re.S).group(1)
+
+    def raised(label, call, text):
+        with pytest.raises(RuntimeError) as e:
+            call()
+        msg = str(e.value)
+        assert re.match(re.escape(label) + r" failed \(status \d+\): ", msg), msg
+        assert text and msg.endswith("): " + text), (msg, text)
+
+    raised("align_wait", pygicp.NDTCuda().align_wait, library_text(capi.NDTCore(0), lambda c: c.align_wait()))
+    raised("align_wait", pygicp.FastVGICPCuda().align_wait, library_text(capi.VGICPCore(0), lambda c: c.align_wait()))
+
+    def swap_an_incremental_target(c):
+        c.map_begin()
+        c.swap_source_and_target()
+    reg = pygicp.FastVGICPCuda()
+    reg.begin_incremental_target()
+    reg.set_input_source(cloud)
+    reg.insert_source_into_target(np.eye(4))
+    raised("swap_source_and_target", reg.swap_source_and_target, library_text(capi.VGICPCore(0), swap_an_incremental_target))
+    T = reg.align()  # the handle is as usable as before (the scan against the map made of it; accuracy is other tests' business)
+    assert reg.has_converged() and np.isfinite(T).all()
+
+    gicp = pygicp.FastGICP()
+    gicp.set_input_target(cloud); gicp.set_input_source(cloud)
+    with pytest.raises(ValueError, match="setSourceCovariances: one covariance per source point"):  # refused by the class, before the library
+        gicp.set_source_covariances(np.tile(np.eye(3), (63, 1, 1)))
+    gicp.set_source_covariances(np.tile(np.eye(3), (64, 1, 1)))
