@@ -123,10 +123,10 @@ int ensure_sorted(Engine* e, CloudDev& c) {
       HIP_OR_FAIL(e, e->sort_coop.ensure(COOP_STATE_BYTES));
       SortCoopState* cs = e->sort_coop.as<SortCoopState>();
       char* base = reinterpret_cast<char*>(cs);
-      unsigned* chist = reinterpret_cast<unsigned*>(cs + 1);
+      unsigned long long* chist = reinterpret_cast<unsigned long long*>(cs + 1);  // [pass][workgroup][bin / 4] granules (sort_granule.hpp)
       // once: tags of no launch everywhere (afterwards every launch rewrites the tagged words, and the state words are compared with the launch's number)
       if (fresh) HIP_OR_FAIL(e, hipMemsetAsync(cs, 0, COOP_STATE_BYTES, e->stream));
-      if ((++e->sort_seq & (COOP_HTAG_MASK >> 1)) == 0) ++e->sort_seq;  // (a histogram tag of 0 is what fresh memory holds)
+      e->sort_seq = coop_next_seq(e->sort_seq);  // (never one whose histogram tag is 0: that is what fresh memory holds)
       const unsigned long long wd = fvh_env_ull("FVH_SORT_COOP_WATCHDOG_TICKS", e->params.sort_coop_watchdog_ticks);  // (the environment overrides the handle's value per call: test hook, 0 forces the fallback)
       unsigned long long* celem = reinterpret_cast<unsigned long long*>(base + COOP_ELEM_OFFSET);
       sort_coop_kernel<<<COOP_WGS, COOP_THREADS, 0, e->stream>>>(c.pts.as<float4>(), n, c.order.as<int>(), c.sorted.as<float4>(), c.box.as<unsigned>(), chist, celem, cs, e->sort_seq, wd);

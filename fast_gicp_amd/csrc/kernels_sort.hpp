@@ -11,6 +11,7 @@
 #pragma once
 #include <cstddef>
 #include "dev_math.hpp"
+#include "sort_granule.hpp"
 
 namespace fvh {
 
@@ -624,16 +625,17 @@ __global__ __launch_bounds__(1024) void sort_small_kernel(const float4* __restri
 // consumer polls (see sort_coop_kernel) -- no grid barrier. (Round 5 also built the widening of the caller's array + the bounding cube
 // INTO this kernel, for one more hand-off: 22.4 us against pack 4.8 + sort 19.4, and the registration rate did not move. Not kept.)
 // Each wave owns a contiguous chunk of <= 128 keys (2 steps of 64), so stable order = (workgroup, wave, step, lane).
-// The per-pass scan is done redundantly by every workgroup from the 512 x COOP_WGS matrix of workgroup totals.
+// The per-pass scan is done redundantly by every workgroup -- and, behind ONE barrier, by every wave of it for its own cursors -- from the
+// COOP_WGS x 512 matrix of workgroup totals, which travels as 8-byte granules of four 11-bit counts under one tag (sort_granule.hpp).
 // A poll that never succeeds (workgroups not co-resident) trips a watchdog: not every workgroup reports "done" and
 // sort_coop_finish_kernel, launched right behind, does the whole job on one workgroup instead.
 // ------------------------------------------------------------------------------------------------
 constexpr int COOP_WGS = 32, COOP_THREADS = 512, COOP_WAVES = COOP_THREADS / 64, COOP_STEPS = 2;
 static_assert(COOP_WGS * COOP_WAVES * COOP_STEPS * 64 >= SORT_SMALL_MAX, "every key needs a slot");
 static_assert(COOP_THREADS == SMALL_BINS, "one thread per bin in the scans");
-static_assert(COOP_THREADS == COOP_WGS * 16 && SMALL_BINS == 16 * 32, "a thread polls 32 consecutive words of one row of the matrix");
+constexpr int COOP_ROW_GRANULES = SMALL_BINS / COOP_GRANULE_COUNTS;  // 128 granules = 1 KB: what a workgroup publishes per pass
+static_assert(COOP_WGS == 4 * COOP_WAVES && COOP_ROW_GRANULES == 2 * 64, "a wave polls four rows of the matrix, a lane two granules of each");
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 struct SortCoopState {     // zeroed once, when allocated. Every word is compared with the launch's sequence number (>= 1): nothing is ever reset
   unsigned abort_seq;              // == seq: a workgroup of launch `seq` gave up (watchdog, or the test hook)
   unsigned pad[15];
@@ -643,18 +645,22 @@ struct SortCoopState {     // zeroed once, when allocated. Every word is compare
 template <typename T> __device__ __forceinline__ void st_agent(T* p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }  // write-through (sc1)
 template <typename T> __device__ __forceinline__ T ld_agent(const T* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }     // bypasses the non-coherent L2
 
-// Hand-offs between workgroups carry their own arrival signal (round 3, as in the LM kernel): a histogram entry is
-// {count:11, tag:21}, a scattered element {tag:31, key:18, index:15} in ONE 64-bit word, an entry of the final order {tag:32,
-// index:32} -- tag = this launch's sequence number (+ the pass). A consumer polls the words it needs with L2-bypassing loads
+// Hand-offs between workgroups carry their own arrival signal (round 3, as in the LM kernel): four histogram entries share ONE 64-bit
+// granule {count:11 x 4, tag:20} (sort_granule.hpp; a lane stores and loads it whole, so one tag vouches for four counts), a scattered
+// element is {tag:31, key:18, index:15} in ONE 64-bit word, an entry of the final order {tag:32, index:32} -- tag = this launch's
+// sequence number (+ the pass). A consumer polls the words it needs with L2-bypassing loads
 // until their tags are current; nobody waits for anybody else: no arrival counter, no "wait for my stores, add 1, poll the
 // counter" (four grid barriers of ~3 us each in the first version of this kernel). Buffers are zeroed
 // when allocated, sequence numbers start at 1 and every complete launch rewrites every word it will poll next time.
 // What a hand-off costs (round 5, tools/sort_timing.py + rocprofv3 A/B, tools/ab_sort.sh): an sc1 load past the caches is ~1 us for one
-// word per lane and ~2 us for the 64 KB of a pass's histogram matrix per workgroup; a store is visible ~1 us after it was issued. Two things
-// were slower than that and are gone: (a) the matrix as [bin][workgroup] -- a workgroup published 512 scattered 4-byte words -- read by 32
-// separate agent-scope loads per thread, ten of which the compiler serialised behind their own s_waitcnt (now [workgroup][bin]: 2 KB of whole
-// lines per workgroup, read as eight 16-byte loads behind ONE wait and transposed through LDS); (b) a failed poll that consulted the watchdog
-// -- a clock read and another load past the caches -- before every retry (now every 16th). 27.5 -> 22.2 us at 17k points. With cheap
+// word per lane and grows with the bytes a workgroup pulls (~2 us for 64 KB); a store is visible ~1 us after it was issued. What was slower
+// than that and is gone: (a) the matrix as [bin][workgroup] -- a workgroup published 512 scattered 4-byte words -- read by 32
+// separate agent-scope loads per thread, ten of which the compiler serialised behind their own s_waitcnt (now [workgroup][bin]: whole
+// lines per workgroup, read as eight loads behind ONE wait); (b) a failed poll that consulted the watchdog
+// -- a clock read and another load past the caches -- before every retry (now every 16th): 27.5 -> 22.2 us at 17k points; (c) one tagged
+// 4-byte word per bin -- 64 KB per workgroup and pass, transposed through LDS to "thread = bin", summed, scanned through the LDS crossbar
+// and handed to the waves behind two more barriers (now 32 KB of granules; a wave sums its four rows in registers while it unpacks them,
+// the waves meet ONCE in LDS, and every wave scans the 512 totals for itself with DPP row scans: profiles/sort_exchange_timeline.txt). With cheap
 // retries the delay before the first look no longer matters (0.1 ... 0.9 us measure the same; polling with no delay at all costs 3 us).
 #ifndef FVH_COOP_POLL_SLEEP
 #define FVH_COOP_POLL_SLEEP 8
@@ -662,31 +668,52 @@ template <typename T> __device__ __forceinline__ T ld_agent(const T* p) { return
 #ifndef FVH_COOP_FIRST_SLEEP
 #define FVH_COOP_FIRST_SLEEP 8
 #endif
-constexpr int COOP_MATRIX_WORDS = 2 * SMALL_BINS * COOP_WGS;                                    // u32 {count, tag}
-constexpr int COOP_HTAG_BITS = 21;
-constexpr unsigned COOP_HTAG_MASK = (1u << COOP_HTAG_BITS) - 1u;
-static_assert(COOP_THREADS * COOP_STEPS < (1 << (32 - COOP_HTAG_BITS)), "a workgroup's count of one bin must fit the bits above the tag");
-constexpr size_t COOP_ELEM_OFFSET = sizeof(SortCoopState) + sizeof(unsigned) * COOP_MATRIX_WORDS;  // u64 x SORT_SMALL_MAX: pass-0 output
+constexpr int COOP_MATRIX_WORDS = SMALL_PASSES * COOP_WGS * COOP_ROW_GRANULES;                    // u64 granules, [pass][workgroup][bin / 4]
+static_assert(COOP_THREADS * COOP_STEPS <= (int)COOP_COUNT_MASK, "a workgroup's count of one bin must fit a granule's slot");
+static_assert(2 * COOP_WGS * COOP_THREADS * COOP_STEPS <= 0x10000, "{total, part before this workgroup} of a bin are summed as two 16-bit halves of one word");
+constexpr size_t COOP_ELEM_OFFSET = sizeof(SortCoopState) + sizeof(unsigned long long) * COOP_MATRIX_WORDS;  // u64 x SORT_SMALL_MAX: pass-0 output
 constexpr size_t COOP_STATE_BYTES = COOP_ELEM_OFFSET + sizeof(unsigned long long) * SORT_SMALL_MAX;
-static_assert(sizeof(SortCoopState) % 16 == 0, "the matrix behind it is read in 16-byte words");
+static_assert(sizeof(SortCoopState) % 8 == 0 && COOP_ELEM_OFFSET % 8 == 0, "granules and elements behind it are 8-byte words");
 static_assert(SORT_SMALL_MAX <= (1 << 15) && SMALL_BITS * SMALL_PASSES <= 18, "element packing: 15 index bits, 18 key bits");
 
-// eight 16-byte agent-scope loads of 128 consecutive bytes in flight together, one wait (loads and wait in one asm block: nothing touches a
-// destination register before its data has landed)
-__device__ __forceinline__ void load8x16_agent(u32x4 (&v)[8], const u32x4* p) {
+// A wave's share of a pass's matrix -- granules `lane` and `lane + 64` of four consecutive rows, every load 512 consecutive bytes across the
+// wave -- as eight 8-byte agent-scope loads in flight together, one wait (loads and wait in one asm block: nothing touches a destination
+// register before its data has landed)
+__device__ __forceinline__ void load8x8_agent(unsigned long long (&v)[8], const unsigned long long* p) {
+  static_assert(COOP_ROW_GRANULES * 8 == 1024, "the offsets below: a row is 1,024 bytes");
   asm volatile(
-      "global_load_dwordx4 %0, %8, off sc1\n\t"
-      "global_load_dwordx4 %1, %8, off offset:16 sc1\n\t"
-      "global_load_dwordx4 %2, %8, off offset:32 sc1\n\t"
-      "global_load_dwordx4 %3, %8, off offset:48 sc1\n\t"
-      "global_load_dwordx4 %4, %8, off offset:64 sc1\n\t"
-      "global_load_dwordx4 %5, %8, off offset:80 sc1\n\t"
-      "global_load_dwordx4 %6, %8, off offset:96 sc1\n\t"
-      "global_load_dwordx4 %7, %8, off offset:112 sc1\n\t"
+      "global_load_dwordx2 %0, %8, off sc1\n\t"
+      "global_load_dwordx2 %1, %8, off offset:512 sc1\n\t"
+      "global_load_dwordx2 %2, %8, off offset:1024 sc1\n\t"
+      "global_load_dwordx2 %3, %8, off offset:1536 sc1\n\t"
+      "global_load_dwordx2 %4, %8, off offset:2048 sc1\n\t"
+      "global_load_dwordx2 %5, %8, off offset:2560 sc1\n\t"
+      "global_load_dwordx2 %6, %8, off offset:3072 sc1\n\t"
+      "global_load_dwordx2 %7, %8, off offset:3584 sc1\n\t"
       "s_waitcnt vmcnt(0)"
       : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(v[6]), "=&v"(v[7])
       : "v"(p)
       : "memory");
+}
+
+// Inclusive sum scan of a u32 over the wave: inside the rows of 16 lanes with DPP row shifts (lanes without a source add 0), the row totals
+// passed on with the two row broadcasts -- six dependent VALU ops, no trip through the LDS crossbar (kernels_cov.hpp, wave_min_u32, is the pattern).
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ unsigned dpp_add_step(unsigned x) {
+  return x + (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, ROW_MASK, 0xF, false);
+}
+__device__ __forceinline__ unsigned wave_scan_add_u32(unsigned v) {
+  v = dpp_add_step<0x111, 0xF>(v);  // row_shr:1
+  v = dpp_add_step<0x112, 0xF>(v);  // row_shr:2
+  v = dpp_add_step<0x114, 0xF>(v);  // row_shr:4
+  v = dpp_add_step<0x118, 0xF>(v);  // row_shr:8 -> inclusive inside each row
+  v = dpp_add_step<0x142, 0xA>(v);  // row_bcast:15 into rows 1, 3
+  v = dpp_add_step<0x143, 0xC>(v);  // row_bcast:31 into rows 2, 3
+  return v;
+}
+template <int SEL>  // the value of lane SEL of this lane's quad
+__device__ __forceinline__ unsigned quad_lane_u32(unsigned x) {
+  return (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, SEL * 0x55, 0xF, 0xF, false);
 }
 
 __device__ __forceinline__ bool coop_timed_out(SortCoopState* st, unsigned seq, unsigned long long t0, unsigned long long watchdog_ticks) {
@@ -704,13 +731,19 @@ __device__ unsigned long long g_sort_time[COOP_WGS][16];
 #endif
 
 __global__ __launch_bounds__(COOP_THREADS) void sort_coop_kernel(const float4* __restrict__ pts, int n, int* order, float4* sorted,
-                                                                const unsigned* __restrict__ box /* {~ordered(min) x3, ordered(max) x3} */, unsigned* hist /* [2][COOP_WGS][SMALL_BINS] */,
+                                                                const unsigned* __restrict__ box /* {~ordered(min) x3, ordered(max) x3} */, unsigned long long* hist /* [2][COOP_WGS][COOP_ROW_GRANULES] */,
                                                                 unsigned long long* elem, SortCoopState* st, unsigned seq, unsigned long long watchdog_ticks) {
-  __shared__ unsigned wh[COOP_WAVES][SMALL_BINS];  // per-wave digit counts -> exclusive prefix over the waves of this workgroup -> scatter cursors
-  __shared__ unsigned wsum[COOP_WAVES];
-  __shared__ unsigned short s_cnt[COOP_WGS][SMALL_BINS];  // the pass's matrix of workgroup totals (counts <= 1,024), on its way from "thread = 32 words of a row" to "thread = bin"
+  __shared__ __attribute__((aligned(16))) unsigned wh[COOP_WAVES][SMALL_BINS];  // per-wave digit counts -> exclusive prefix over the waves of this workgroup -> scatter cursors
+  __shared__ __attribute__((aligned(16))) unsigned s_part[COOP_WAVES][SMALL_BINS];  // per bin {total:16, part before this workgroup:16} over the four rows of the pass's matrix a wave polled
   const int wg = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  // A thread whose poll gave up (watchdog) says so here before the next barrier, and everybody leaves behind that barrier: one s_barrier and
+  // one LDS read where __syncthreads_or spends three barriers and a reduction. Never cleared: the whole launch is void once it is set (abort_seq
+  // is, too, and the finish kernel redoes the sort). A wave that has already read 0 behind barrier k while another one, ahead of it, sets 1
+  // on its way to barrier k + 1 leaves one barrier later -- waves that have ended do not hold a barrier up.
+  __shared__ int s_failed;
+  if (tid == 0) s_failed = 0;  // (nobody polls before the first barrier)
+  auto sync_or = [&](int f) { if (f) s_failed = 1; __syncthreads(); return s_failed; };
   const int gw = wg * COOP_WAVES + wv;  // global wave index
   const int chunk = ((((n + COOP_WGS * COOP_WAVES - 1) / (COOP_WGS * COOP_WAVES)) + 63) & ~63);
   const int begin = gw * chunk, end = min(n, begin + chunk);
@@ -755,10 +788,10 @@ __global__ __launch_bounds__(COOP_THREADS) void sort_coop_kernel(const float4* _
   FVH_ST(1);  // keys computed
   for (int pass = 0; pass < SMALL_PASSES; pass++) {
     const int shift = pass * SMALL_BITS;
-    unsigned* gh = hist + (size_t)pass * SMALL_BINS * COOP_WGS;
-    // {count:11, tag:21}: a workgroup holds at most 1,024 keys, so 11 bits carry its count and the tag wraps every 2^20 sorts of an engine
-    // (16 tag bits wrapped every 32,768: a word a watchdog-aborted launch never rewrote could have matched a later launch)
-    const unsigned htag = ((seq << 1) | (unsigned)pass) & COOP_HTAG_MASK;
+    unsigned long long* gh = hist + (size_t)pass * COOP_WGS * COOP_ROW_GRANULES;
+    // {count:11 x 4, tag:20}: a workgroup holds at most 1,024 keys, so 11 bits carry its count of a bin and the tag repeats every 2^19 sorts of an
+    // engine (16 tag bits repeated every 32,768: a word a watchdog-aborted launch never rewrote could have matched a later launch)
+    const unsigned htag = coop_htag(seq, pass);
     int failed = 0;
     if (pass > 0) {  // this wave's chunk in the order pass 0 produced: poll until every element of the chunk has landed
       if (FVH_COOP_FIRST_SLEEP) __builtin_amdgcn_s_sleep(FVH_COOP_FIRST_SLEEP);
@@ -784,59 +817,79 @@ __global__ __launch_bounds__(COOP_THREADS) void sort_coop_kernel(const float4* _
 #pragma unroll
     for (int u = 0; u < COOP_STEPS; u++)
       if (begin + u * 64 + lane < end) atomicAdd(&wh[wv][(key[u] >> shift) & (SMALL_BINS - 1)], 1u);
-    if (__syncthreads_or(failed)) return;
-    {  // thread = bin: exclusive prefix over this workgroup's waves; workgroup total -> global, tagged
+    if (sync_or(failed)) return;
+    {  // thread = bin: exclusive prefix over this workgroup's waves; workgroup total -> global, four bins of a quad of lanes under one tag
       unsigned run = 0;
 #pragma unroll
       for (int w = 0; w < COOP_WAVES; w++) { const unsigned c = wh[w][tid]; wh[w][tid] = run; run += c; }
-      st_agent(&gh[(size_t)wg * SMALL_BINS + tid], (run << COOP_HTAG_BITS) | htag);  // [workgroup][bin]: a workgroup publishes 2 KB of whole lines
+      const unsigned long long g = coop_granule_pack(quad_lane_u32<0>(run), quad_lane_u32<1>(run), quad_lane_u32<2>(run), quad_lane_u32<3>(run), htag);
+      if ((tid & 3) == 0) st_agent(&gh[(size_t)wg * COOP_ROW_GRANULES + (tid >> 2)], g);  // [workgroup][bin / 4]: a workgroup publishes 1 KB of whole lines
     }
     FVH_ST(3 + 5 * pass);  // workgroup totals published
-    {  // thread = bin: total over all workgroups and the part before this workgroup (polled until all 32 entries are current); then the bins are scanned
-      // The matrix is [workgroup][bin]: thread t takes 32 consecutive words of row t / 16 -- eight 16-byte loads in flight together, ONE wait
-      // (32 separate agent-scope loads were compiled into 22 batched + 10 serialised round trips: 3.5 of this kernel's 26 us per pass) --
-      // checks their tags, and the counts cross to "thread = bin" through LDS.
-      const u32x4* src = reinterpret_cast<const u32x4*>(gh + (size_t)(tid >> 4) * SMALL_BINS + (size_t)(tid & 15) * 32);
-      u32x4 q[8];
+    {  // total over all workgroups and the part before this workgroup, per bin (polled until all 32 rows are current); then the bins are scanned
+      // The matrix is [workgroup][bin / 4]: wave w takes rows 4 w ... 4 w + 3, a lane granules `lane` and `lane + 64` of each (bins 4 lane ... + 3 and
+      // 256 + 4 lane ... + 3) -- eight loads in flight together, ONE wait -- checks their tags and sums the four rows while it unpacks them.
+      const unsigned long long* src = gh + (size_t)(4 * wv) * COOP_ROW_GRANULES + lane;
+      unsigned long long q[8];
       if (FVH_COOP_FIRST_SLEEP) __builtin_amdgcn_s_sleep(FVH_COOP_FIRST_SLEEP);
       while (true) {
-        load8x16_agent(q, src);
+        load8x8_agent(q, src);
         unsigned bad = 0;
 #pragma unroll
-        for (int j = 0; j < 8; j++) bad |= ((q[j].x & COOP_HTAG_MASK) ^ htag) | ((q[j].y & COOP_HTAG_MASK) ^ htag) | ((q[j].z & COOP_HTAG_MASK) ^ htag) | ((q[j].w & COOP_HTAG_MASK) ^ htag);
+        for (int j = 0; j < 8; j++) bad |= coop_granule_tag(q[j]) ^ htag;
         if (!bad) break;
         if ((++spins & 15u) == 0u && coop_timed_out(st, seq, t_start, watchdog_ticks)) { failed = 1; break; }
         __builtin_amdgcn_s_sleep(FVH_COOP_POLL_SLEEP);
       }
-      FVH_ST(4 + 5 * pass);  // this thread's part of the matrix is current
+      FVH_ST(4 + 5 * pass);  // this wave's part of the matrix is current
       {
-        uint2* dst = reinterpret_cast<uint2*>(&s_cnt[tid >> 4][(tid & 15) * 32]);
+        unsigned acc[2][COOP_GRANULE_COUNTS] = {};
 #pragma unroll
-        for (int j = 0; j < 8; j++)
-          dst[j] = make_uint2((q[j].x >> COOP_HTAG_BITS) | ((q[j].y >> COOP_HTAG_BITS) << 16), (q[j].z >> COOP_HTAG_BITS) | ((q[j].w >> COOP_HTAG_BITS) << 16));
+        for (int j = 0; j < 4; j++) {
+          const unsigned both = (4 * wv + j < wg) ? 0x10001u : 1u;  // (wave-uniform) a row before this workgroup counts in both halves
+#pragma unroll
+          for (int h = 0; h < 2; h++)
+#pragma unroll
+            for (int c = 0; c < COOP_GRANULE_COUNTS; c++) acc[h][c] += coop_granule_count(q[2 * j + h], c) * both;
+        }
+#pragma unroll
+        for (int h = 0; h < 2; h++) *reinterpret_cast<uint4*>(&s_part[wv][256 * h + 4 * lane]) = make_uint4(acc[h][0], acc[h][1], acc[h][2], acc[h][3]);
       }
-      if (__syncthreads_or(failed)) return;
+      if (sync_or(failed)) return;  // the ONE barrier between "rows seen" and the cursors
 #ifdef FVH_SORT_TIMING
       if (pass == 0) { FVH_ST(14); if (threadIdx.x == 0) g_sort_time[wg][15] = spins; }
 #endif
-      unsigned total = 0, before = 0;
+      // Every wave for itself, a lane for the same eight bins: the eight partial sums per bin, the exclusive scan of the 512 totals (both halves
+      // of the bins in ONE DPP scan: a lane's two sums are <= 32,768 each and ride in the two halves of a word), + the part before this
+      // workgroup, onto the wave's OWN row of prefixes -> its scatter cursors. Own row only: LDS operations of one wave complete in order.
+      unsigned sum[2][COOP_GRANULE_COUNTS] = {};
 #pragma unroll
-      for (int j = 0; j < COOP_WGS; j++) {
-        const unsigned a = s_cnt[j][tid];
-        total += a;
-        before += (j < wg) ? a : 0u;
+      for (int w = 0; w < COOP_WAVES; w++)
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+          const uint4 a = *reinterpret_cast<const uint4*>(&s_part[w][256 * h + 4 * lane]);
+          sum[h][0] += a.x; sum[h][1] += a.y; sum[h][2] += a.z; sum[h][3] += a.w;
+        }
+      unsigned mine = 0;
+#pragma unroll
+      for (int c = 0; c < COOP_GRANULE_COUNTS; c++) mine += (sum[0][c] & 0xFFFFu) | (sum[1][c] << 16);
+      const unsigned incl = wave_scan_add_u32(mine);
+      const unsigned low_half = (unsigned)__builtin_amdgcn_readlane((int)incl, 63) & 0xFFFFu;  // bins 0 ... 255 of all workgroups
+      unsigned run[2] = {(incl - mine) & 0xFFFFu, ((incl - mine) >> 16) + low_half};
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+        uint4* cur = reinterpret_cast<uint4*>(&wh[wv][256 * h + 4 * lane]);
+        const uint4 v = *cur;
+        unsigned cv[COOP_GRANULE_COUNTS] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int c = 0; c < COOP_GRANULE_COUNTS; c++) {
+          cv[c] += run[h] + (sum[h][c] >> 16);
+          run[h] += sum[h][c] & 0xFFFFu;
+        }
+        *cur = make_uint4(cv[0], cv[1], cv[2], cv[3]);
       }
-      unsigned x = total;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) { const unsigned y = __shfl_up(x, off); if (lane >= off) x += y; }
-      if (lane == 63) wsum[wv] = x;
-      if (__syncthreads_or(failed)) return;
-      unsigned base = x - total + before;
-      for (int w = 0; w < wv; w++) base += wsum[w];
-#pragma unroll
-      for (int w = 0; w < COOP_WAVES; w++) wh[w][tid] += base;  // scatter cursor of wave w for this bin
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     }
-    __syncthreads();
     FVH_ST(5 + 5 * pass);  // scatter cursors ready
     const bool last = (pass == SMALL_PASSES - 1);
 #pragma unroll
@@ -861,6 +914,7 @@ __global__ __launch_bounds__(COOP_THREADS) void sort_coop_kernel(const float4* _
       dst_base = __shfl(dst_base, leader);
       if (valid) {
         const unsigned dst = dst_base + rank;
+        if (dst >= (unsigned)n) continue;  // (cursors are sums of what other workgroups published: never a store outside the cloud, whatever they hold)
         if (!last) {
           st_agent(&elem[dst], (etag << 33) | ((unsigned long long)key[u] << 15) | (unsigned long long)(unsigned)id[u]);
         } else {
