@@ -1532,6 +1532,7 @@ int fvh_ndt_adopt_prepared_source(fvh_ndt* h) {
   return h->pipe.adopt(&h->e, h->source, h->source_vm, "fvh_ndt_prepare_source_device");
 }
 int fvh_ndt_debug_set_voxel_hint(fvh_ndt* h, int which, int num_voxels) { CHECK_HANDLE(h); (which ? h->target_vm : h->source_vm).nv_hint = num_voxels; return FVH_OK; }
+int fvh_ndt_debug_get_table_capacity(fvh_ndt* h, int which, int* capacity) { CHECK_HANDLE(h); if (!capacity) return FVH_ERR_INVALID_ARGUMENT; *capacity = (int)(which ? h->target_vm : h->source_vm).capacity; return FVH_OK; }
 int fvh_ndt_set_lm_trace(fvh_ndt* h, int on) { CHECK_HANDLE(h); h->e.lm_trace_on = on != 0; return FVH_OK; }
 int fvh_ndt_get_lm_trace(fvh_ndt* h, int* n, double* rows6) { CHECK_HANDLE(h); return get_lm_trace(&h->e, n, rows6); }
 int fvh_ndt_fitness_score(fvh_ndt* h, const double* T, double max_range, double* score) { CHECK_HANDLE(h); return do_fitness(&h->e, h->source, h->target, T, max_range, score); }

@@ -470,6 +470,8 @@ int fvh_ndt_prepare_source_from_voxelgrid(fvh_ndt* h, struct fvh_voxelgrid* filt
 int fvh_ndt_fitness_score(fvh_ndt* h, const double* T16, double max_range, double* score);
 /* testing hook (as fvh_vgicp_debug_set_voxel_hint): table size hint of the NEXT build of the source (which = 0) / target (1) voxel map */
 int fvh_ndt_debug_set_voxel_hint(fvh_ndt* h, int which, int num_voxels);
+/* testing hook (as fvh_vgicp_debug_get_table_capacity): buckets of the current source (which = 0) / target (1) voxel table */
+int fvh_ndt_debug_get_table_capacity(fvh_ndt* h, int which, int* capacity);
 int fvh_ndt_set_lm_trace(fvh_ndt* h, int on);
 int fvh_ndt_get_lm_trace(fvh_ndt* h, int* num_rows, double* rows6);
 int fvh_ndt_get_num_voxels(fvh_ndt* h, int which /* 0 source, 1 target */, int* num_voxels);

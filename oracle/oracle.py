@@ -248,9 +248,11 @@ class FastVGICP(_Reg):
     """fp64 restatement of the reference CPU FastVGICP (fast_vgicp_impl.hpp)."""
     _prefix = "orc_vgicp_"
 
-    def __init__(self, threads=0, k=20, reg=PLANE, resolution=1.0, search=DIRECT1, cov_mode=0, kernel_width=0.5, kernel_max_dist=3.0, round_fp32=False):
+    def __init__(self, threads=0, k=20, reg=PLANE, resolution=1.0, search=DIRECT1, cov_mode=0, kernel_width=0.5, kernel_max_dist=3.0, round_fp32=False, radius=0.0):
         self.h = lib().orc_vgicp_create()
         self._call("set_params", threads, k, reg, C.c_double(resolution), search, cov_mode, C.c_double(kernel_width), C.c_double(kernel_max_dist), int(round_fp32))
+        if radius:
+            self._call("set_search_radius", C.c_double(radius))
 
     def set_gicp_mode(self, on=True, max_correspondence_distance=3.4028234663852886e38):
         """FastGICP (fast_gicp_impl.hpp:118-240): nearest-target-point correspondences instead of voxels."""

@@ -144,6 +144,7 @@ void orc_vgicp_set_params(void* h, int threads, int k, int reg, double res, int 
   g->search_method = (NeighborSearchMethod)search; g->cov_mode = cov_mode; g->kernel_width = kw; g->kernel_max_dist = kmax;
   g->round_storage_fp32 = round_fp32 != 0;
 }
+void orc_vgicp_set_search_radius(void* h, double radius) { ((FastVGICP*)h)->search_radius = radius; }
 void orc_vgicp_set_lm(void* h, int max_iter, double rot_eps, double trans_eps, int lm_max_iter, double init_lambda_factor, int debug) {
   auto* g = (FastVGICP*)h;
   g->max_iterations = max_iter; g->rotation_epsilon = rot_eps; g->transformation_epsilon = trans_eps;

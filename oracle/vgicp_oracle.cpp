@@ -632,7 +632,7 @@ void FastVGICP::update_correspondences(const Iso3& T) {
     }
     return;
   }
-  auto offsets = neighbor_offsets(search_method);
+  auto offsets = neighbor_offsets(search_method, search_radius);
   std::vector<std::vector<std::pair<int, int>>> corrs(num_threads);
   for (auto& c : corrs) c.reserve((input->size() * offsets.size()) / num_threads);
 #pragma omp parallel for num_threads(num_threads) schedule(guided, 8)

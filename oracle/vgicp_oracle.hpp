@@ -120,6 +120,7 @@ struct FastVGICP : LsqBase {
   RegularizationMethod regularization = PLANE;        // :21
   double voxel_resolution = 1.0;                      // fast_vgicp_impl.hpp:22
   NeighborSearchMethod search_method = DIRECT1;       // :23
+  double search_radius = 0.0;                         // DIRECT_RADIUS (the CUDA classes' fourth method, fast_vgicp_cuda.cu:77-91) on the fp64 formulas
   // covariance source: 0 = kd-tree k-NN (CPU reference), 1 = RBF kernel (CUDA formula)
   int cov_mode = 0;
   int voxel_mode = 0;                                 // VoxelAccumulationMode ordinal (fast_vgicp_impl.hpp:24 ADDITIVE; 2 = MULTIPLICATIVE)

@@ -499,6 +499,7 @@ def _in_flight_calls(kind, c, a):
             "create_target_voxelmap": (G, lambda: c.create_target_voxelmap()),
             "create_source_voxelmap": (G, lambda: c.create_source_voxelmap()),
             "debug_set_voxel_hint": (G, lambda: c.debug_set_voxel_hint("source", 1000)),
+            "debug_table_capacity": (G, lambda: c.debug_table_capacity("target")),
             "set_source_tile": (G, lambda: c.set_source_tile(0, 1)),
             "get_num_voxels": (G, lambda: c.get_num_voxels("target")),
             "get_voxelmap": (G, lambda: c.get_voxelmap("target")),

@@ -171,6 +171,28 @@ def test_voxelmap_and_linearize_vs_numpy(O):
         assert util.rel_err(H, H2) < 1e-10 and util.rel_err(b, b2) < 1e-10
 
 
+@pytest.mark.parametrize("mode", ["P2D", "D2D"])
+def test_ndt_linearize_vs_numpy(O, mode):
+    """The NDT sums of the oracle against their numpy twin (np_twin.ndt_linearize: Cauchy weight, voxels of at most 6 points skipped, D2D on
+    the source voxels' means and covariances) over the oracle's own voxel records, to the tolerance of the VGICP leg above."""
+    from tests import np_twin
+    t, s = util.bundled_pair()
+    t, s = t[:5000], s[:5000]
+    d2d = mode == "D2D"
+    for search in (O.DIRECT1, O.DIRECT7):
+        g = O.NDT(mode=O.D2D if d2d else O.P2D, search=search)
+        g.set_target(t); g.set_source(s); g.prepare()
+        vm = util.voxel_dict(*g.get_voxelmap("target"))
+        assert sum(1 for v in vm.values() if v[0] > 6) > 20 and sum(1 for v in vm.values() if v[0] <= 6) > 20  # both kinds of voxel take part
+        recs = list(zip(*g.get_voxelmap("source")[1:])) if d2d else None
+        T = util.random_pose(np.random.default_rng(3), 1.0, 0.3)
+        e, H, b = g.linearize(T)
+        e2, H2, b2, nc = np_twin.ndt_linearize(s, recs, vm, 1.0, O.neighbor_offsets(search), T, d2d)
+        assert nc == g.num_correspondences() and nc > 100
+        assert abs(e - e2) < 1e-10 * abs(e2)
+        assert util.rel_err(H, H2) < 1e-10 and util.rel_err(b, b2) < 1e-10
+
+
 def test_se3_exp_vs_scipy(O):
     from scipy.linalg import expm
     rng = np.random.default_rng(0)
