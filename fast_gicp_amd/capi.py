@@ -16,6 +16,7 @@ DIRECT27, DIRECT7, DIRECT1, DIRECT_RADIUS = range(4)
 NDT_P2D, NDT_D2D = 0, 1
 COMPUTE_FP64, COMPUTE_FP32, COMPUTE_CUDA_COMPAT = 0, 1, 2
 VOXEL_ADDITIVE, VOXEL_ADDITIVE_WEIGHTED, VOXEL_MULTIPLICATIVE = range(3)
+VOXEL_NDT_SUMS = 3  # `mode` of a snapshot of an NDT map (FVH_VOXEL_NDT_SUMS): never a VGICP accumulation mode
 
 EXPORTED_SYMBOLS = None  # filled by _declared_symbols()
 
@@ -120,7 +121,7 @@ def _result_dict(r):
                 lm_failed=bool(r.lm_failed), num_launches=r.num_launches)
 
 
-# ---- map snapshot files (VGICPCore.map_save / map_load; FastVGICPCuda::saveTargetMap / loadTargetMap write the same bytes) ----
+# ---- map snapshot files (VGICPCore / NDTMapCore .map_save / map_load; FastVGICPCuda::saveTargetMap / loadTargetMap write the same bytes) ----
 # little-endian: magic "FVHVMAP\0" (8 bytes) | version u32 = 1 | mode i32 | num_inserts i32 | num_voxels i32 | num_points i64 | resolution f64
 # (40 bytes) | coords i32[n][3] | sums f64[n][10] | ages u32[n]          ("Map snapshot files")
 MAP_FILE_MAGIC = b"FVHVMAP\0"
@@ -173,6 +174,60 @@ def read_map_file(path):
     ages = np.frombuffer(raw, "<u4", n, o).astype(np.uint32)
     return dict(resolution=float(hdr["resolution"]), mode=int(hdr["mode"]), num_inserts=int(hdr["num_inserts"]), num_points=int(hdr["num_points"]), num_voxels=n,
                 coords=coords, sums=sums, ages=ages)
+
+
+class _IncrementalMap:
+    """The incremental target map of a handle class whose C prefix has map_* / voxelmap_* calls (mixed into VGICPCore and NDTMapCore)."""
+
+    # ---- incremental target map (include/fast_vgicp_hip.h: fvh_vgicp_map_* / fvh_ndt_map_*; the calls VGICPCore and NDTMapCore share) ----
+    def map_begin(self, expected_voxels=0):
+        """Start (or restart) an empty incremental target map at the handle's resolution (and, VGICP, voxel accumulation mode)."""
+        self._call("map_begin", int(expected_voxels))
+
+    def map_insert_source(self, T=None):
+        """Add the current source (VGICP: points + covariances; NDT: points) to the map at pose T (4x4, default identity)."""
+        t = _IDENTITY16 if T is None else _colmajor16(T)
+        self._call("map_insert_source", _p(t))
+
+    def map_prune(self, center=None, radius=0.0, max_age=0):
+        """Drop voxels further than `radius` from `center` (None: no distance rule) and those untouched by the last max_age inserts (0: no age rule). -> voxels removed"""
+        removed = C.c_int(0)
+        c = None if center is None else np.ascontiguousarray(center, np.float64).reshape(3)
+        self._call("map_prune", None if c is None else _p(c), C.c_double(radius), int(max_age), C.byref(removed))
+        return removed.value
+
+    def map_info(self):
+        inc, nv, cap, ni, dr = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        npts = C.c_longlong(0)
+        self._call("map_get_info", C.byref(inc), C.byref(nv), C.byref(cap), C.byref(ni), C.byref(npts), C.byref(dr))
+        return dict(incremental=bool(inc.value), num_voxels=nv.value, capacity=cap.value, num_inserts=ni.value, num_points=npts.value, dropped=dr.value)
+
+    # ---- snapshots of the incremental map (fvh_{vgicp,ndt}_voxelmap_export / _import / _merge_from) ----
+    def map_export(self):
+        """The live incremental map as a snapshot: header fields + coords (n, 3) int32, sums (n, 10) float64 (the device's own per-voxel sums)
+        and ages (n,) uint32, rows in ascending packed-key order (z-major, then y, then x)."""
+        nv, mode, ni = C.c_int(0), C.c_int(0), C.c_int(0)
+        res, npts = C.c_double(0.0), C.c_longlong(0)
+        self._call("voxelmap_export", C.byref(nv), C.byref(res), C.byref(mode), C.byref(ni), C.byref(npts), None, None, None)
+        n = nv.value
+        coords, sums, ages = np.empty((n, 3), np.int32), np.empty((n, 10), np.float64), np.empty(n, np.uint32)
+        if n:
+            self._call("voxelmap_export", C.byref(nv), C.byref(res), C.byref(mode), C.byref(ni), C.byref(npts), _p(coords), _p(sums), _p(ages))
+        return dict(resolution=res.value, mode=mode.value, num_inserts=ni.value, num_points=npts.value, num_voxels=n, coords=coords, sums=sums, ages=ages)
+
+    def map_import(self, snapshot):
+        """ADD a snapshot's voxels into the live map (restore: map_begin() first): sums and counts add, ages and the insert count carry over."""
+        coords, sums, ages = _snapshot_arrays(snapshot)
+        n = len(coords)
+        self._call("voxelmap_import", n, _p(coords) if n else None, _p(sums) if n else None, _p(ages) if n else None, C.c_double(snapshot["resolution"]), int(snapshot["mode"]),
+                   int(snapshot["num_inserts"]), C.c_longlong(int(snapshot["num_points"])))
+
+    def map_merge_from(self, other):
+        """ADD the live map of `other` (a handle of the same class on the same device, same resolution and mode) into this one, device to device; `other` is unchanged."""
+        self._call("voxelmap_merge_from", other.h)
+
+    def map_save(self, path):
+        write_map_file(path, self.map_export())
 
 
 class _Core:
@@ -423,7 +478,7 @@ def device_count():
     return n.value if rc == 0 else 0
 
 
-class VGICPCore(_Core):
+class VGICPCore(_Core, _IncrementalMap):
     """fast_gicp::cuda::FastVGICPCudaCore on the HIP engine (same method names, snake_case as in the .cuh)."""
     _prefix = "fvh_vgicp_"
 
@@ -560,16 +615,7 @@ class VGICPCore(_Core):
     def create_target_voxelmap(self):
         self._call("create_target_voxelmap")
 
-    # ---- incremental target map (include/fast_vgicp_hip.h: fvh_vgicp_map_begin ...) ----
-    def map_begin(self, expected_voxels=0):
-        """Start (or restart) an empty incremental target map at the handle's resolution and voxel accumulation mode."""
-        self._call("map_begin", int(expected_voxels))
-
-    def map_insert_source(self, T=None):
-        """Add the current source (points + covariances) to the map at pose T (4x4, default identity)."""
-        t = _IDENTITY16 if T is None else _colmajor16(T)
-        self._call("map_insert_source", _p(t))
-
+    # ---- incremental target map: what takes covariances / picks a voxel type (the rest: _IncrementalMap) ----
     def map_insert_cloud(self, xyz, covs, T=None, device_ptr=None, n=None, stride=3):
         """Add a cloud that is not the source: host points (N x 3 float32) or a device pointer (device_ptr, n, stride), covariances N x 3 x 3 on the host."""
         t = _IDENTITY16 if T is None else _colmajor16(T)
@@ -579,46 +625,6 @@ class VGICPCore(_Core):
         else:
             a = _f32(xyz)
             self._call("map_insert_cloud", _p(a), len(a), 3, _p(c), _p(t), 0)
-
-    def map_prune(self, center=None, radius=0.0, max_age=0):
-        """Drop voxels further than `radius` from `center` (None: no distance rule) and those untouched by the last max_age inserts (0: no age rule). -> voxels removed"""
-        removed = C.c_int(0)
-        c = None if center is None else np.ascontiguousarray(center, np.float64).reshape(3)
-        self._call("map_prune", None if c is None else _p(c), C.c_double(radius), int(max_age), C.byref(removed))
-        return removed.value
-
-    def map_info(self):
-        inc, nv, cap, ni, dr = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
-        npts = C.c_longlong(0)
-        self._call("map_get_info", C.byref(inc), C.byref(nv), C.byref(cap), C.byref(ni), C.byref(npts), C.byref(dr))
-        return dict(incremental=bool(inc.value), num_voxels=nv.value, capacity=cap.value, num_inserts=ni.value, num_points=npts.value, dropped=dr.value)
-
-    # ---- snapshots of the incremental map (fvh_vgicp_voxelmap_export / _import / _merge_from) ----
-    def map_export(self):
-        """The live incremental map as a snapshot: header fields + coords (n, 3) int32, sums (n, 10) float64 (the device's own per-voxel sums)
-        and ages (n,) uint32, rows in ascending packed-key order (z-major, then y, then x)."""
-        nv, mode, ni = C.c_int(0), C.c_int(0), C.c_int(0)
-        res, npts = C.c_double(0.0), C.c_longlong(0)
-        self._call("voxelmap_export", C.byref(nv), C.byref(res), C.byref(mode), C.byref(ni), C.byref(npts), None, None, None)
-        n = nv.value
-        coords, sums, ages = np.empty((n, 3), np.int32), np.empty((n, 10), np.float64), np.empty(n, np.uint32)
-        if n:
-            self._call("voxelmap_export", C.byref(nv), C.byref(res), C.byref(mode), C.byref(ni), C.byref(npts), _p(coords), _p(sums), _p(ages))
-        return dict(resolution=res.value, mode=mode.value, num_inserts=ni.value, num_points=npts.value, num_voxels=n, coords=coords, sums=sums, ages=ages)
-
-    def map_import(self, snapshot):
-        """ADD a snapshot's voxels into the live map (restore: map_begin() first): sums and counts add, ages and the insert count carry over."""
-        coords, sums, ages = _snapshot_arrays(snapshot)
-        n = len(coords)
-        self._call("voxelmap_import", n, _p(coords) if n else None, _p(sums) if n else None, _p(ages) if n else None, C.c_double(snapshot["resolution"]), int(snapshot["mode"]),
-                   int(snapshot["num_inserts"]), C.c_longlong(int(snapshot["num_points"])))
-
-    def map_merge_from(self, other):
-        """ADD the live map of `other` (a VGICPCore on the same device, same resolution and mode) into this one, device to device; `other` is unchanged."""
-        self._call("voxelmap_merge_from", other.h)
-
-    def map_save(self, path):
-        write_map_file(path, self.map_export())
 
     def map_load(self, path):
         """Add the file's map into the live map; a handle with no live map takes the file's resolution and mode and starts one sized for it."""
@@ -898,3 +904,27 @@ class NDTCore(_Core):
         covs = np.empty((nv, 3, 3), np.float32)
         self._call("get_voxels", w, _p(coords), _p(num), _p(means), _p(covs))
         return coords, num, means, covs
+
+
+class NDTMapCore(NDTCore, _IncrementalMap):
+    """An NDT handle with the calls of its incremental target map (include/fast_vgicp_hip.h: fvh_ndt_map_* / fvh_ndt_voxelmap_*): map_begin,
+    map_insert_source, map_prune, map_info, map_export, map_import, map_merge_from, map_save come from _IncrementalMap as on VGICPCore; NDT
+    voxels take points only. Everything else is NDTCore's, on the same C handle type."""
+
+    def map_insert_cloud(self, xyz, T=None, device_ptr=None, n=None, stride=3):
+        """Add a cloud that is not the source: host points (N x 3 float32) or a device pointer (device_ptr, n, stride)."""
+        t = _IDENTITY16 if T is None else _colmajor16(T)
+        if device_ptr is not None:
+            self._call("map_insert_cloud", C.c_void_p(device_ptr), int(n), int(stride), _p(t), 1)
+        else:
+            a = _f32(xyz)
+            self._call("map_insert_cloud", _p(a), len(a), 3, _p(t), 0)
+
+    def map_load(self, path):
+        """Add the file's map (mode VOXEL_NDT_SUMS) into the live map; a handle with no live map takes the file's resolution and starts one sized for it."""
+        snap = read_map_file(path)
+        if not self.map_info()["incremental"]:
+            self.set_resolution(snap["resolution"])
+            self.map_begin(max(snap["num_voxels"], 1))
+        self.map_import(snap)
+        return snap

@@ -554,9 +554,25 @@ struct fvh_ndt {
     source_vm.has_canon = true;
     return FVH_OK;
   }
+  // Incremental target map (fvh_ndt_map_*, host_incmap.inc.hpp): `target_vm` keeps its sums (sum p, sum p p^T, count) and grows in place; there
+  // is no cloud behind it. `target_newer`: a target cloud was set while it was live -- the next create_target_voxelmap (an align makes that
+  // call itself) builds the batch map of that cloud and the mode ends.
+  bool incremental() const { return target_vm.inc.live && target_vm.valid; }
+  bool target_newer = false;
+  CloudDev insert_cloud;     // staging of fvh_ndt_map_insert_cloud
+  hipEvent_t merge_ev[2] = {nullptr, nullptr};  // fvh_ndt_voxelmap_merge_from: the other handle's stream -> ours before the kernel, ours -> its stream after it
+  int build_target_map() {
+    const int rc = build_voxelmap<1>(&e, target, target_vm, resolution, true);
+    if (rc == FVH_OK || !target_vm.valid) { target_vm.inc.live = false; target_newer = false; }  // (a call refused for want of a target cloud leaves an incremental map as it was)
+    return rc;
+  }
   Rebuild rebuild_safe() {
     return [this] {
-      int rc = build_voxelmap<1>(&e, target, target_vm, target_vm.res, true, true);
+      // (an insert secures its capacity before it launches: an incremental map never reports an overflow, and has no cloud to rebuild from.
+      // The D2D source map is a hint-sized batch map like any other)
+      const bool inc = incremental();
+      if (inc && distance_mode != FVH_NDT_D2D) return e.fail(FVH_ERR_BAD_STATE, "the incremental target map reported a table overflow; start again with fvh_ndt_map_begin");
+      int rc = inc ? (int)FVH_OK : build_voxelmap<1>(&e, target, target_vm, target_vm.res, true, true);
       if (!rc && distance_mode == FVH_NDT_D2D) {
         rc = build_voxelmap<1>(&e, source, source_vm, source_vm.res, true, true);
         // A tiled handle walks the source voxels in canonical order, and the rebuild has just reordered the compact list that order indexes:
@@ -671,7 +687,7 @@ int fvh_vgicp_map_begin(fvh_vgicp* h, int expected_voxels) {
   CHECK_HANDLE(h);
   { const int rc = map_refusal(h, "map_begin"); if (rc) return rc; }
   h->live_map_stale = false;
-  return incmap_begin(&h->e, h->voxelmap, h->resolution, h->voxel_mode, expected_voxels);
+  return incmap_begin(&h->e, h->voxelmap, h->resolution, h->voxel_mode == 2 ? 2 : 0, expected_voxels);  // (ADDITIVE_WEIGHTED: the additive voxel type)
 }
 int fvh_vgicp_map_insert_source(fvh_vgicp* h, const double* T16) {
   CHECK_HANDLE(h);
@@ -1358,18 +1374,26 @@ int fvh_ndt_destroy(fvh_ndt* h) {
   if (h->e.stream) (void)hipStreamSynchronize(h->e.stream);
   if (h->e.side) (void)hipStreamSynchronize(h->e.side);
   h->pipe.release();
-  h->source.release(); h->target.release(); h->source_vm.release(); h->target_vm.release();
+  h->source.release(); h->target.release(); h->source_vm.release(); h->target_vm.release(); h->insert_cloud.release();
+  for (hipEvent_t ev : h->merge_ev) if (ev) (void)hipEventDestroy(ev);
   h->e.shutdown();
   delete h;
   return FVH_OK;
 }
 const char* fvh_ndt_last_error(const fvh_ndt* h) { return h ? h->e.err.c_str() : "null handle"; }
 int fvh_ndt_set_distance_mode(fvh_ndt* h, int m) { CHECK_HANDLE(h); if (m != FVH_NDT_P2D && m != FVH_NDT_D2D) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "bad distance mode"); h->distance_mode = m; h->e.has_corr = false; return FVH_OK; }
-int fvh_ndt_set_resolution(fvh_ndt* h, double r) { CHECK_HANDLE(h); if (!(r > 0)) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "resolution must be > 0"); h->resolution = r; return FVH_OK; }
+int fvh_ndt_set_resolution(fvh_ndt* h, double r) {
+  CHECK_HANDLE(h);
+  if (!(r > 0)) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "resolution must be > 0");
+  if (h->incremental() && r != h->target_vm.res) return h->e.fail(FVH_ERR_BAD_STATE, "set_resolution: an incremental target map is live at another resolution; call fvh_ndt_map_begin again");
+  h->resolution = r;
+  return FVH_OK;
+}
 int fvh_ndt_set_neighbor_search_method(fvh_ndt* h, int m, double radius) { CHECK_HANDLE(h); return h->e.set_offsets(m, radius); }
 int fvh_ndt_set_precision(fvh_ndt* h, int p) {
   CHECK_HANDLE(h);
   if (p != FVH_COMPUTE_FP64 && p != FVH_COMPUTE_FP32 && p != FVH_COMPUTE_CUDA_COMPAT) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "bad precision");
+  if (p == FVH_COMPUTE_CUDA_COMPAT && h->incremental()) return h->e.fail(FVH_ERR_UNSUPPORTED, "set_precision: FVH_COMPUTE_CUDA_COMPAT has no incremental target map (its voxel sums are float sums in point order)");
   if ((p == FVH_COMPUTE_CUDA_COMPAT) != (h->e.precision == FVH_COMPUTE_CUDA_COMPAT)) { h->source_vm.invalidate(); h->target_vm.invalidate(); h->e.has_corr = false; }  // the voxel records of the two arithmetics differ
   h->e.precision = p;
   return FVH_OK;
@@ -1378,6 +1402,7 @@ int fvh_ndt_get_engine_params(fvh_ndt* h, fvh_engine_params* out) { CHECK_HANDLE
 int fvh_ndt_set_engine_params(fvh_ndt* h, const fvh_engine_params* p) { CHECK_HANDLE(h); return set_engine_params(&h->e, p); }
 int fvh_ndt_swap_source_and_target(fvh_ndt* h) {
   CHECK_HANDLE(h);
+  if (h->incremental()) return h->e.fail(FVH_ERR_BAD_STATE, "swap_source_and_target: the live target map is incremental -- there is no cloud behind it to become a source");
   h->source.swap(h->target);
   std::swap(h->source_vm, h->target_vm);
   h->e.has_corr = false;
@@ -1385,7 +1410,9 @@ int fvh_ndt_swap_source_and_target(fvh_ndt* h) {
 }
 static int ndt_set_cloud(fvh_ndt* h, bool is_target, const float* xyz, int n, int stride, bool on_device) {
   h->e.has_corr = false;
-  (is_target ? h->target_vm : h->source_vm).invalidate();
+  // the target cloud was replaced: the batch map built from the old one is dead; an incremental map never depended on it
+  if (is_target && h->incremental()) h->target_newer = true;
+  else (is_target ? h->target_vm : h->source_vm).invalidate();
   return upload_cloud(&h->e, is_target ? h->target : h->source, xyz, n, stride, on_device, false);
 }
 int fvh_ndt_set_source_cloud(fvh_ndt* h, const float* xyz, int n) { CHECK_HANDLE(h); return ndt_set_cloud(h, false, xyz, n, 3, false); }
@@ -1403,10 +1430,88 @@ int fvh_ndt_create_source_voxelmap(fvh_ndt* h) {
 }
 int fvh_ndt_create_target_voxelmap(fvh_ndt* h) {
   CHECK_HANDLE(h);
-  if (h->target_vm.valid) return FVH_OK;  // ndt_cuda.cu:133-135
-  return build_voxelmap<1>(&h->e, h->target, h->target_vm, h->resolution, true);
+  if (h->target_vm.valid && !(h->incremental() && h->target_newer)) return FVH_OK;  // ndt_cuda.cu:133-135; a live incremental map IS the target map
+  return h->build_target_map();
 }
 int fvh_ndt_create_voxelmaps(fvh_ndt* h) { int rc = fvh_ndt_create_source_voxelmap(h); if (rc) return rc; return fvh_ndt_create_target_voxelmap(h); }
+// ---- incremental target map (host_incmap.inc.hpp; the VGICP calls above, for NDT voxels: points only) ----
+static int ndt_map_refusal(fvh_ndt* h, const char* who) {
+  if (h->e.sharded()) return h->e.fail(FVH_ERR_UNSUPPORTED, std::string(who) + ": not on a multi-GPU handle (communicator / tile attached)");
+  if (h->e.precision == FVH_COMPUTE_CUDA_COMPAT) return h->e.fail(FVH_ERR_UNSUPPORTED, std::string(who) + ": FVH_COMPUTE_CUDA_COMPAT has no incremental target map (its voxel sums are float sums in point order)");
+  return FVH_OK;
+}
+static int ndt_map_live(fvh_ndt* h, const char* who) {
+  if (!h->incremental()) return h->e.fail(FVH_ERR_BAD_STATE, std::string(who) + ": no incremental map is live (fvh_ndt_map_begin)");
+  return FVH_OK;
+}
+int fvh_ndt_map_begin(fvh_ndt* h, int expected_voxels) {
+  CHECK_HANDLE(h);
+  { const int rc = ndt_map_refusal(h, "map_begin"); if (rc) return rc; }
+  const int rc = incmap_begin(&h->e, h->target_vm, h->resolution, 1, expected_voxels);
+  if (rc == FVH_OK) h->target_newer = false;
+  return rc;
+}
+int fvh_ndt_map_insert_source(fvh_ndt* h, const double* T16) {
+  CHECK_HANDLE(h);
+  { const int rc = ndt_map_refusal(h, "map_insert_source"); if (rc) return rc; }
+  { const int rc = ndt_map_live(h, "map_insert_source"); if (rc) return rc; }
+  return incmap_insert(&h->e, h->target_vm, h->source, T16, "map_insert_source");
+}
+int fvh_ndt_map_insert_cloud(fvh_ndt* h, const float* xyz, int n, int stride_floats, const double* T16, int on_device) {
+  CHECK_HANDLE(h);
+  { const int rc = ndt_map_refusal(h, "map_insert_cloud"); if (rc) return rc; }
+  { const int rc = ndt_map_live(h, "map_insert_cloud"); if (rc) return rc; }
+  const int rc = upload_cloud(&h->e, h->insert_cloud, xyz, n, stride_floats, on_device != 0, false);
+  if (rc) return rc;
+  return incmap_insert(&h->e, h->target_vm, h->insert_cloud, T16, "map_insert_cloud");
+}
+int fvh_ndt_map_prune(fvh_ndt* h, const double* center3, double radius, int max_age, int* num_removed) {
+  CHECK_HANDLE(h);
+  { const int rc = ndt_map_refusal(h, "map_prune"); if (rc) return rc; }
+  { const int rc = ndt_map_live(h, "map_prune"); if (rc) return rc; }
+  return incmap_prune(&h->e, h->target_vm, center3, radius, max_age, num_removed);
+}
+int fvh_ndt_map_get_info(fvh_ndt* h, int* incremental, int* num_voxels, int* capacity, int* num_inserts, long long* num_points, int* num_dropped) {
+  CHECK_HANDLE(h);
+  const bool live = h->incremental();
+  if (incremental) *incremental = live ? 1 : 0;
+  if (capacity) *capacity = live ? (int)h->target_vm.capacity : 0;
+  if (num_inserts) *num_inserts = live ? (int)h->target_vm.inc.epoch : 0;
+  if (num_points) *num_points = live ? h->target_vm.inc.num_points : 0;
+  int cnt[3] = {0, 0, 0};
+  if (live && (num_voxels || num_dropped)) { const int rc = incmap_read_counts(&h->e, h->target_vm, cnt, nullptr); if (rc) return rc; h->target_vm.inc.voxel_bound = cnt[0]; }
+  if (num_voxels) *num_voxels = cnt[0];
+  if (num_dropped) *num_dropped = cnt[1];
+  return FVH_OK;
+}
+int fvh_ndt_voxelmap_export(fvh_ndt* h, int* num_voxels, double* resolution, int* mode, int* num_inserts, long long* num_points, int* coords3, double* sums10, unsigned* ages) {
+  CHECK_HANDLE(h);
+  { const int rc = ndt_map_refusal(h, "voxelmap_export"); if (rc) return rc; }
+  { const int rc = ndt_map_live(h, "voxelmap_export"); if (rc) return rc; }
+  return incmap_export(&h->e, h->target_vm, num_voxels, resolution, mode, num_inserts, num_points, coords3, sums10, ages);
+}
+int fvh_ndt_voxelmap_import(fvh_ndt* h, int n, const int* coords3, const double* sums10, const unsigned* ages, double resolution, int mode, int num_inserts, long long num_points) {
+  CHECK_HANDLE(h);
+  { const int rc = ndt_map_refusal(h, "voxelmap_import"); if (rc) return rc; }
+  { const int rc = ndt_map_live(h, "voxelmap_import"); if (rc) return rc; }
+  if (mode != FVH_VOXEL_NDT_SUMS) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_import: the snapshot's accumulation mode is not the live map's (an NDT map takes FVH_VOXEL_NDT_SUMS snapshots only: VGICP sums are of another kind)");
+  return incmap_import(&h->e, h->target_vm, n, coords3, sums10, ages, resolution, mode, num_inserts, num_points);
+}
+int fvh_ndt_voxelmap_merge_from(fvh_ndt* h, fvh_ndt* other) {
+  CHECK_HANDLE(h);
+  { const int rc = ndt_map_refusal(h, "voxelmap_merge_from"); if (rc) return rc; }
+  if (!other) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_merge_from: null other handle");
+  if (other == h) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_merge_from: a map cannot be merged into itself");
+  if (other->e.device != h->e.device) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_merge_from: the two handles are on different devices");
+  if (other->e.sharded() || other->e.precision == FVH_COMPUTE_CUDA_COMPAT) return h->e.fail(FVH_ERR_UNSUPPORTED, "voxelmap_merge_from: the other handle is a multi-GPU / FVH_COMPUTE_CUDA_COMPAT handle");
+  if (other->in_flight()) return h->e.fail(FVH_ERR_BAD_STATE, "voxelmap_merge_from: an align_async is in flight on the other handle: call fvh_ndt_align_wait first");
+  { const int rc = ndt_map_live(h, "voxelmap_merge_from"); if (rc) return rc; }
+  if (!other->incremental()) return h->e.fail(FVH_ERR_BAD_STATE, "voxelmap_merge_from: the other handle has no live incremental map (fvh_ndt_map_begin)");
+  { const int rc = other->e.settle(); if (rc) return h->e.fail(rc, "voxelmap_merge_from: the other handle: " + other->e.err); }
+  for (hipEvent_t& ev : h->merge_ev) if (!ev) HIP_OR_FAIL(&h->e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  other->e.quiet = false;  // (its stream now holds a wait)
+  return incmap_merge_from(&h->e, h->target_vm, other->target_vm, other->e.stream, h->merge_ev[0], h->merge_ev[1]);
+}
 static int ndt_ready(fvh_ndt* h) {
   if (!h->source.has_pts) return h->e.fail(FVH_ERR_BAD_STATE, "source cloud not set");
   if (!h->target_vm.valid) return h->e.fail(FVH_ERR_BAD_STATE, "target voxel map not built (create_voxelmaps)");
@@ -1432,6 +1537,7 @@ int fvh_ndt_set_source_tile(fvh_ndt* h, int rank, int nranks) {
   CHECK_HANDLE(h);
   if (nranks < 1 || rank < 0 || rank >= nranks) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "set_source_tile: need 0 <= rank < nranks");
   if (h->e.comm && nranks > 1 && (nranks != h->e.nranks || rank != h->e.rank)) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "set_source_tile: rank / nranks differ from the attached communicator's");
+  if (nranks > 1 && h->incremental()) return h->e.fail(FVH_ERR_BAD_STATE, "set_source_tile: an incremental target map is live (every rank would grow a private map); end it first (create_target_voxelmap / a new handle)");
   h->e.tile_rank = nranks > 1 ? rank : 0;
   h->e.tile_n = nranks;
   h->e.has_corr = false;
@@ -1525,7 +1631,7 @@ int fvh_ndt_prepare_source_from_voxelgrid(fvh_ndt* h, fvh_voxelgrid* vg) {
   return ndt_prepare(h, nullptr, 0, 3, true, vg);
 }
 int fvh_ndt_set_source_cloud_from_voxelgrid(fvh_ndt* h, fvh_voxelgrid* vg) { CHECK_HANDLE(h); h->e.has_corr = false; h->source_vm.invalidate(); return take_filter_output(&h->e, vg, h->source, h->e.stream); }
-int fvh_ndt_set_target_cloud_from_voxelgrid(fvh_ndt* h, fvh_voxelgrid* vg) { CHECK_HANDLE(h); h->e.has_corr = false; h->target_vm.invalidate(); return take_filter_output(&h->e, vg, h->target, h->e.stream); }
+int fvh_ndt_set_target_cloud_from_voxelgrid(fvh_ndt* h, fvh_voxelgrid* vg) { CHECK_HANDLE(h); h->e.has_corr = false; if (h->incremental()) h->target_newer = true; else h->target_vm.invalidate(); return take_filter_output(&h->e, vg, h->target, h->e.stream); }
 int fvh_ndt_adopt_prepared_source(fvh_ndt* h) {
   if (h && h->in_flight()) return h->e.fail(FVH_ERR_BAD_STATE, "adopt_prepared_source: an align_async is in flight");
   CHECK_HANDLE(h);
@@ -1606,6 +1712,7 @@ int fvh_ndt_synchronize(fvh_ndt* h) { CHECK_HANDLE(h); HIP_OR_FAIL(&h->e, hipStr
 int fvh_ndt_comm_init(fvh_ndt* h, const void* id, int nranks, int rank) {
   CHECK_HANDLE(h);
   if (h->e.tile_n > 1 && (h->e.tile_n != nranks || h->e.tile_rank != rank)) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "comm_init: rank / nranks differ from fvh_ndt_set_source_tile's");
+  if (nranks > 1 && h->incremental()) return h->e.fail(FVH_ERR_BAD_STATE, "comm_init: an incremental target map is live (every rank would grow a private map); end it first (create_target_voxelmap / a new handle)");
   return comm_init(&h->e, id, nranks, rank);
 }
 int fvh_ndt_comm_destroy(fvh_ndt* h) { CHECK_HANDLE(h); if (h->e.comm) { g_rccl.CommDestroy(h->e.comm); h->e.comm = nullptr; } h->e.nranks = 1; h->e.rank = 0; return FVH_OK; }

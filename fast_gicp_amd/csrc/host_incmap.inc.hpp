@@ -1,5 +1,6 @@
-// Incremental target voxel map of a VGICP handle (fvh_vgicp_map_*): a map that keeps its per-voxel sums, takes posed scans in place and
-// can be pruned. Kernels and buffer layout: kernels_voxelmap.hpp ("incremental target map").
+// Incremental target voxel map of a VGICP or NDT handle (fvh_vgicp_map_* / fvh_ndt_map_*): a map that keeps its per-voxel sums, takes posed
+// scans in place and can be pruned. Kernels and buffer layout: kernels_voxelmap.hpp ("incremental target map"). VoxelMapDev::inc.mode picks
+// the voxel type: 0 / 2 VGICP additive / multiplicative (points + covariances), 1 NDT (points only: sum p, sum p p^T).
 // (a section of the host translation unit: included by fvh_capi.hip inside its anonymous namespace, after host_stages.inc.hpp)
 //
 // The map lives in the handle's VoxelMapDev like a batch map -- keys[cur], table, occupied, counter set `cur`, bitmap / grid -- so
@@ -15,6 +16,14 @@ inline unsigned incmap_capacity_for(long long voxels) {  // load factor <= 0.25 
   unsigned cap = INCMAP_MIN_CAPACITY;
   while ((long long)cap < 4 * voxels) cap <<= 1;
   return cap;
+}
+
+// the kernel instantiation of the live map's voxel type: f(std::integral_constant<int, 0 additive | 1 NDT sums | 2 multiplicative>{})
+template <class F>
+inline void incmap_by_mode(const VoxelMapDev& vm, F&& f) {
+  if (vm.inc.mode == 2) f(std::integral_constant<int, 2>{});
+  else if (vm.inc.mode == 1) f(std::integral_constant<int, 1>{});
+  else f(std::integral_constant<int, 0>{});
 }
 
 // buffers of side `which` at `cap` buckets, empty: keys EMPTY, sums / stamps 0
@@ -45,7 +54,7 @@ int incmap_begin(Engine* e, VoxelMapDev& vm, double res, int mode, int expected_
   { int rc = incmap_prepare_side(e, vm, vm.cur, cap); if (rc) return rc; }
   HIP_OR_FAIL(e, hipMemsetAsync(vm.counters.p, 0, 2 * 16 * sizeof(int), e->stream));
   HIP_OR_FAIL(e, hipMemsetAsync(vm.inc.ctl.p, 0, 4 * sizeof(int), e->stream));
-  vm.inc.mode = mode == 2 ? 2 : 0;
+  vm.inc.mode = mode == 2 ? 2 : (mode == 1 ? 1 : 0);  // (VGICP's ADDITIVE_WEIGHTED never reaches here as 1: fvh_vgicp_map_begin folds it into 0)
   vm.inc.epoch = 0;
   vm.inc.num_points = 0;
   vm.inc.voxel_bound = 0;
@@ -88,14 +97,11 @@ int incmap_rehash(Engine* e, VoxelMapDev& vm, unsigned new_cap, const VmPrune& p
   int* next_counters = vm.counters.as<int>() + 16 * to;
   vm_rehash_begin_kernel<<<1, 64, 0, e->stream>>>(vm.counters_cur(), next_counters, vm.inc.ctl.as<int>());
   const unsigned blocks = (old_cap + VM_FIN_THREADS - 1) / VM_FIN_THREADS;
-  if (vm.inc.mode == 2)
-    vm_rehash_kernel<2><<<blocks, VM_FIN_THREADS, 0, e->stream>>>(vm.keys[from].as<unsigned long long>(), vm.inc.sums[from].as<double>(), vm.inc.stamps[from].as<unsigned>(), old_cap,
-                                                                   vm.keys[to].as<unsigned long long>(), new_cap - 1, vm.inc.sums[to].as<double>(), vm.inc.stamps[to].as<unsigned>(),
-                                                                   vm.table.as<uint4>(), next_counters, vm.occupied.as<int>(), prune, vm.inc.ctl.as<int>());
-  else
-    vm_rehash_kernel<0><<<blocks, VM_FIN_THREADS, 0, e->stream>>>(vm.keys[from].as<unsigned long long>(), vm.inc.sums[from].as<double>(), vm.inc.stamps[from].as<unsigned>(), old_cap,
-                                                                   vm.keys[to].as<unsigned long long>(), new_cap - 1, vm.inc.sums[to].as<double>(), vm.inc.stamps[to].as<unsigned>(),
-                                                                   vm.table.as<uint4>(), next_counters, vm.occupied.as<int>(), prune, vm.inc.ctl.as<int>());
+  incmap_by_mode(vm, [&](auto m) {
+    vm_rehash_kernel<decltype(m)::value><<<blocks, VM_FIN_THREADS, 0, e->stream>>>(vm.keys[from].as<unsigned long long>(), vm.inc.sums[from].as<double>(), vm.inc.stamps[from].as<unsigned>(), old_cap,
+                                                                                   vm.keys[to].as<unsigned long long>(), new_cap - 1, vm.inc.sums[to].as<double>(), vm.inc.stamps[to].as<unsigned>(),
+                                                                                   vm.table.as<uint4>(), next_counters, vm.occupied.as<int>(), prune, vm.inc.ctl.as<int>());
+  });
   HIP_OR_FAIL(e, hipGetLastError());
   vm.cur = to;
   vm.capacity = new_cap;
@@ -124,7 +130,7 @@ int incmap_read_counts(Engine* e, VoxelMapDev& vm, int* counters3, int* ctl4) {
 // count (every point could open a voxel): an insert can neither drop a point nor need to be redone.
 int incmap_insert(Engine* e, VoxelMapDev& vm, const CloudDev& c, const double* T16, const char* who) {
   if (!vm.inc.live || !vm.valid) return e->fail(FVH_ERR_BAD_STATE, std::string(who) + ": no incremental map is live (fvh_vgicp_map_begin)");
-  if (!c.has_pts || !c.has_cov) return e->fail(FVH_ERR_BAD_STATE, std::string(who) + ": the cloud needs points and covariances");
+  if (vm.inc.mode == 1 ? !c.has_pts : (!c.has_pts || !c.has_cov)) return e->fail(FVH_ERR_BAD_STATE, std::string(who) + (vm.inc.mode == 1 ? ": the cloud is not set" : ": the cloud needs points and covariances"));
   if (!T16) return e->fail(FVH_ERR_INVALID_ARGUMENT, std::string(who) + ": null pose");
   for (int i = 0; i < 16; i++)
     if (!std::isfinite(T16[i])) return e->fail(FVH_ERR_INVALID_ARGUMENT, std::string(who) + ": the pose is not finite");
@@ -166,13 +172,11 @@ int incmap_insert(Engine* e, VoxelMapDev& vm, const CloudDev& c, const double* T
   const int blocks = (n + 255) / 256;
   {
     ProfScope ps(e, "map_insert");
-    if (vm.inc.mode == 2) {
-      vm_insert_kernel<2><<<blocks, 256, 0, e->stream>>>(c.pts.as<float4>(), c.cov.as<float4>(), n, T, vm.res, keys, vm.capacity - 1, sums, stamps, vm.inc.epoch, dirty, ctl, counters + 1, order);
-      vm_refresh_kernel<2><<<blocks, 256, 0, e->stream>>>(dirty, ctl, keys, sums, vm.table.as<uint4>(), counters, vm.occupied.as<int>(), grid, bitmap);
-    } else {
-      vm_insert_kernel<0><<<blocks, 256, 0, e->stream>>>(c.pts.as<float4>(), c.cov.as<float4>(), n, T, vm.res, keys, vm.capacity - 1, sums, stamps, vm.inc.epoch, dirty, ctl, counters + 1, order);
-      vm_refresh_kernel<0><<<blocks, 256, 0, e->stream>>>(dirty, ctl, keys, sums, vm.table.as<uint4>(), counters, vm.occupied.as<int>(), grid, bitmap);
-    }
+    incmap_by_mode(vm, [&](auto m) {
+      constexpr int M = decltype(m)::value;
+      vm_insert_kernel<M><<<blocks, 256, 0, e->stream>>>(c.pts.as<float4>(), M == 1 ? nullptr : c.cov.as<float4>(), n, T, vm.res, keys, vm.capacity - 1, sums, stamps, vm.inc.epoch, dirty, ctl, counters + 1, order);
+      vm_refresh_kernel<M><<<blocks, 256, 0, e->stream>>>(dirty, ctl, keys, sums, vm.table.as<uint4>(), counters, vm.occupied.as<int>(), grid, bitmap);
+    });
   }
   HIP_OR_FAIL(e, hipGetLastError());
   vm.inc.voxel_bound += n;
@@ -207,6 +211,10 @@ int incmap_prune(Engine* e, VoxelMapDev& vm, const double* center3, double radiu
 // in ascending packed-key order. Rows ADD into a live map of the same grid: import (host rows) and merge_from (another handle's map, read
 // in place) are one kernel + the insert's refresh.
 
+// `mode` of a snapshot header: the VGICP accumulation mode (0 additive, 2 multiplicative), or FVH_VOXEL_NDT_SUMS for an NDT map -- whose
+// sums (sum p, sum p p^T) must never add into VGICP voxels (sum p, sum C) or the other way round: import compares this value
+inline int incmap_snapshot_mode(const VoxelMapDev& vm) { return vm.inc.mode == 1 ? (int)FVH_VOXEL_NDT_SUMS : vm.inc.mode; }
+
 inline unsigned long long host_pack_key(int x, int y, int z) {
   return (unsigned long long)(unsigned)(x + FVH_COORD_BIAS) | ((unsigned long long)(unsigned)(y + FVH_COORD_BIAS) << 21) | ((unsigned long long)(unsigned)(z + FVH_COORD_BIAS) << 42);
 }
@@ -237,7 +245,7 @@ int incmap_export(Engine* e, VoxelMapDev& vm, int* num_voxels, double* resolutio
   const int n = cnt[0];
   if (num_voxels) *num_voxels = n;
   if (resolution) *resolution = vm.res;
-  if (mode) *mode = vm.inc.mode;
+  if (mode) *mode = incmap_snapshot_mode(vm);
   if (num_inserts) *num_inserts = (int)vm.inc.epoch;
   if (num_points) *num_points = vm.inc.num_points;
   if (!rows || n == 0) return FVH_OK;
@@ -301,8 +309,9 @@ int incmap_add_rows(Engine* e, VoxelMapDev& vm, int n_rows, const int* d_coords,
     vm_import_kernel<FROM_MAP><<<blocks, VM_SNAP_THREADS, 0, e->stream>>>(d_coords, d_sums, d_ages, n_rows, from ? from->keys_cur() : nullptr, from ? from->occupied.as<int>() : nullptr,
                                                                            from ? from->counters_cur() : nullptr, from ? from->inc.stamps[from->cur].as<unsigned>() : nullptr, in_epoch,
                                                                            keys, vm.capacity - 1, sums, stamps, vm.inc.epoch, dirty, ctl, counters + 1);
-    if (vm.inc.mode == 2) vm_refresh_kernel<2><<<(n_rows + 255) / 256, 256, 0, e->stream>>>(dirty, ctl, keys, sums, vm.table.as<uint4>(), counters, vm.occupied.as<int>(), grid, bitmap);
-    else vm_refresh_kernel<0><<<(n_rows + 255) / 256, 256, 0, e->stream>>>(dirty, ctl, keys, sums, vm.table.as<uint4>(), counters, vm.occupied.as<int>(), grid, bitmap);
+    incmap_by_mode(vm, [&](auto m) {
+      vm_refresh_kernel<decltype(m)::value><<<(n_rows + 255) / 256, 256, 0, e->stream>>>(dirty, ctl, keys, sums, vm.table.as<uint4>(), counters, vm.occupied.as<int>(), grid, bitmap);
+    });
   }
   HIP_OR_FAIL(e, hipGetLastError());
   vm.inc.voxel_bound += n_rows;
@@ -317,7 +326,7 @@ int incmap_import(Engine* e, VoxelMapDev& vm, int n, const int* coords3, const d
   if ((long long)n > INCMAP_MAX_VOXELS) return e->fail(FVH_ERR_UNSUPPORTED, "voxelmap_import: more than 2^28 voxels");
   if (n > 0 && (!coords3 || !sums10)) return e->fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_import: null coords3 / sums10 with n > 0");
   if (!(resolution == vm.res)) return e->fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_import: the snapshot's resolution is not the live map's");
-  if (mode != vm.inc.mode) return e->fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_import: the snapshot's accumulation mode is not the live map's");
+  if (mode != incmap_snapshot_mode(vm)) return e->fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_import: the snapshot's accumulation mode is not the live map's");
   if (num_inserts < 0 || num_points < 0) return e->fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_import: negative num_inserts / num_points");
   const int lim = FVH_COORD_BIAS - 4096;  // the range voxel_index_ok gives an inserted point
   for (int i = 0; i < n; i++) {

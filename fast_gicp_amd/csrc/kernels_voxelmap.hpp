@@ -466,9 +466,38 @@ __device__ __forceinline__ unsigned inc_claim(unsigned long long* keys, unsigned
   return 0xFFFFFFFFu;
 }
 
-// record {key, n, mean, cov, sqrt(n)} of bucket b from its sums: the arithmetic of vm_finalize_kernel<0 | 2>
+// NDT (MODE 1) record in two halves, the arithmetic of vm_finalize_kernel<1> restated expression by expression (equal sums give the batch
+// record to the bit). Head: {key, n, mean} written, the raw covariance (sum pp^T - mean sum p^T) / n and the weight sqrt(n) handed back.
+// Tail: the MIN_EIG regularisation (an eigen-decomposition, ~1,000 dependent fp64 instructions) and the covariance half of the record --
+// apart, so that a pass over half-empty buckets (vm_rehash_kernel<1>) can run it on dense waves.
+__device__ __forceinline__ void inc_ndt_record_head(unsigned long long key, const double* a, uint4* __restrict__ table, unsigned b, Sym3<double>& C, double& wn) {
+  const double cnt = a[9];
+  const double inv = 1.0 / cnt;
+  const double mx = a[0] * inv, my = a[1] * inv, mz = a[2] * inv;
+  C.xx = (a[3] - mx * a[0]) * inv; C.xy = (a[4] - mx * a[1]) * inv; C.xz = (a[5] - mx * a[2]) * inv;
+  C.yy = (a[6] - my * a[1]) * inv; C.yz = (a[7] - my * a[2]) * inv; C.zz = (a[8] - mz * a[2]) * inv;
+  const int n = (int)cnt;
+  wn = sqrt((double)n);
+  table[(size_t)b * 4] = make_uint4((unsigned)key, (unsigned)(key >> 32), (unsigned)n, 0u);
+  reinterpret_cast<float4*>(table)[(size_t)b * 4 + 1] = make_float4((float)mx, (float)my, (float)mz, (float)n);
+}
+__device__ __forceinline__ void inc_ndt_record_tail(const Sym3<double>& C, double wn, uint4* __restrict__ table, unsigned b) {
+  const Sym3<double> R = regularize_cov(C, 1 /* MIN_EIG */);
+  float4* tf = reinterpret_cast<float4*>(table);
+  tf[(size_t)b * 4 + 2] = make_float4((float)R.xx, (float)R.xy, (float)R.xz, (float)R.yy);
+  tf[(size_t)b * 4 + 3] = make_float4((float)R.yz, (float)R.zz, __int_as_float(__double2loint(wn)), __int_as_float(__double2hiint(wn)));
+}
+
+// record {key, n, mean, cov, sqrt(n)} of bucket b from its sums: the arithmetic of vm_finalize_kernel<MODE>
 template <int MODE>
 __device__ __forceinline__ void inc_write_record(unsigned long long key, const double* a, uint4* __restrict__ table, unsigned b) {
+  if (MODE == 1) {
+    Sym3<double> Craw;
+    double w;
+    inc_ndt_record_head(key, a, table, b, Craw, w);
+    inc_ndt_record_tail(Craw, w, table, b);
+    return;
+  }
   const double cnt = a[9];
   const double inv = 1.0 / cnt;
   double mx = a[0] * inv, my = a[1] * inv, mz = a[2] * inv;
@@ -489,8 +518,9 @@ __device__ __forceinline__ void inc_write_record(unsigned long long key, const d
   tf[(size_t)b * 4 + 3] = make_float4((float)C.yz, (float)C.zz, __int_as_float(__double2loint(wn)), __int_as_float(__double2hiint(wn)));
 }
 
-// MODE 0 additive, 2 multiplicative. An inserted point is p' = (float)(R p + t) and its covariance C' = (float)(R C R^T), both formed in
-// fp64 and rounded once: the values a batch build of the transformed cloud would be handed.
+// MODE 0 additive, 2 multiplicative, 1 NDT (sum p', sum p' p'^T: no covariances, `cov` is never read). An inserted point is
+// p' = (float)(R p + t) and its covariance C' = (float)(R C R^T), both formed in fp64 and rounded once: the values a batch build of the
+// transformed cloud would be handed.
 template <int MODE>
 __global__ __launch_bounds__(256) void vm_insert_kernel(const float4* __restrict__ pts, const float4* __restrict__ cov, int n, PoseD T, double res,
                                                         unsigned long long* __restrict__ table_keys, unsigned mask, double* __restrict__ sums, unsigned* __restrict__ stamps,
@@ -519,24 +549,30 @@ __global__ __launch_bounds__(256) void vm_insert_kernel(const float4* __restrict
       atomicAdd(dropped + 1, 1);  // non-finite / absurdly far: belongs to no voxel (counted as vm_accumulate_kernel does)
     } else {
       const unsigned long long key = pack_key((int)fx, (int)fy, (int)fz);
-      const float4 c0 = cov[2 * i], c1 = cov[2 * i + 1];
-      const double C[3][3] = {{(double)c0.x, (double)c0.y, (double)c0.z}, {(double)c0.y, (double)c0.w, (double)c1.x}, {(double)c0.z, (double)c1.x, (double)c1.y}};
-      double M[3][3];  // R C
-#pragma unroll
-      for (int r = 0; r < 3; r++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) M[r][c] = T.r[3 * r] * C[0][c] + T.r[3 * r + 1] * C[1][c] + T.r[3 * r + 2] * C[2][c];
-      auto rcr = [&](int r, int c) { return (double)(float)(M[r][0] * T.r[3 * c] + M[r][1] * T.r[3 * c + 1] + M[r][2] * T.r[3 * c + 2]); };
-      const Sym3<double> Cp = {rcr(0, 0), rcr(0, 1), rcr(0, 2), rcr(1, 1), rcr(1, 2), rcr(2, 2)};
       double v[VM_ACC_STRIDE];
-      if (MODE == 0) {
+      if constexpr (MODE == 1) {  // points only: `cov` may be null. The terms vm_accumulate_kernel<1> adds for a cloud that holds p'
+        const double qx = px, qy = py, qz = pz;
         v[0] = px; v[1] = py; v[2] = pz;
-        v[3] = Cp.xx; v[4] = Cp.xy; v[5] = Cp.xz; v[6] = Cp.yy; v[7] = Cp.yz; v[8] = Cp.zz;
+        v[3] = qx * qx; v[4] = qx * qy; v[5] = qx * qz; v[6] = qy * qy; v[7] = qy * qz; v[8] = qz * qz;
       } else {
-        const Sym3<double> Ci = inverse(Cp);
-        const Vec3<double> cp = mul(Ci, Vec3<double>{(double)px, (double)py, (double)pz});
-        v[0] = cp.x; v[1] = cp.y; v[2] = cp.z;
-        v[3] = Ci.xx; v[4] = Ci.xy; v[5] = Ci.xz; v[6] = Ci.yy; v[7] = Ci.yz; v[8] = Ci.zz;
+        const float4 c0 = cov[2 * i], c1 = cov[2 * i + 1];
+        const double C[3][3] = {{(double)c0.x, (double)c0.y, (double)c0.z}, {(double)c0.y, (double)c0.w, (double)c1.x}, {(double)c0.z, (double)c1.x, (double)c1.y}};
+        double M[3][3];  // R C
+#pragma unroll
+        for (int r = 0; r < 3; r++)
+#pragma unroll
+          for (int c = 0; c < 3; c++) M[r][c] = T.r[3 * r] * C[0][c] + T.r[3 * r + 1] * C[1][c] + T.r[3 * r + 2] * C[2][c];
+        auto rcr = [&](int r, int c) { return (double)(float)(M[r][0] * T.r[3 * c] + M[r][1] * T.r[3 * c + 1] + M[r][2] * T.r[3 * c + 2]); };
+        const Sym3<double> Cp = {rcr(0, 0), rcr(0, 1), rcr(0, 2), rcr(1, 1), rcr(1, 2), rcr(2, 2)};
+        if (MODE == 0) {
+          v[0] = px; v[1] = py; v[2] = pz;
+          v[3] = Cp.xx; v[4] = Cp.xy; v[5] = Cp.xz; v[6] = Cp.yy; v[7] = Cp.yz; v[8] = Cp.zz;
+        } else {
+          const Sym3<double> Ci = inverse(Cp);
+          const Vec3<double> cp = mul(Ci, Vec3<double>{(double)px, (double)py, (double)pz});
+          v[0] = cp.x; v[1] = cp.y; v[2] = cp.z;
+          v[3] = Ci.xx; v[4] = Ci.xy; v[5] = Ci.xz; v[6] = Ci.yy; v[7] = Ci.yz; v[8] = Ci.zz;
+        }
       }
       v[9] = 1.0;
       unsigned slot = hash_slot(key, VM_LDS_SLOTS - 1);
@@ -652,7 +688,14 @@ __global__ __launch_bounds__(VM_FIN_THREADS) void vm_rehash_kernel(const unsigne
                                                                    unsigned old_capacity, unsigned long long* __restrict__ new_keys, unsigned new_mask, double* __restrict__ new_sums,
                                                                    unsigned* __restrict__ new_stamps, uint4* __restrict__ table, int* __restrict__ counters, int* __restrict__ occupied,
                                                                    VmPrune prune, int* __restrict__ ctl) {
+  // NDT (MODE 1): at the load factor <= 0.5 the host keeps, a wave of old buckets is at most half survivors, and each survivor's record
+  // needs the MIN_EIG eigen-decomposition. As vm_finalize_kernel<1>: the workgroup's survivors are compacted through LDS (raw covariance,
+  // weight, new bucket at the position the keep counter hands out) and regularised by the first ceil(count / 64) waves, one voxel per lane.
+  // Rows of 7 doubles: lane t reads 8 bytes at 56 t -- the 32 lanes of a half wave fall on 32 distinct bank pairs.
+  constexpr bool DENSE = (MODE == 1);
   __shared__ int s_keep, s_drop, s_base;
+  __shared__ double s_cov[DENSE ? VM_FIN_THREADS : 1][7];
+  __shared__ unsigned s_bucket[DENSE ? VM_FIN_THREADS : 1];
   if (threadIdx.x == 0) { s_keep = 0; s_drop = 0; }
   __syncthreads();
   const unsigned b = blockIdx.x * VM_FIN_THREADS + threadIdx.x;
@@ -682,14 +725,27 @@ __global__ __launch_bounds__(VM_FIN_THREADS) void vm_rehash_kernel(const unsigne
 #pragma unroll
       for (int j = 0; j < VM_ACC_STRIDE; j++) { a[j] = old_sums[(size_t)b * VM_ACC_STRIDE + j]; new_sums[(size_t)nb * VM_ACC_STRIDE + j] = a[j]; }
       new_stamps[nb] = stamp;
-      inc_write_record<MODE>(key, a, table, nb);
-      local = atomicAdd(&s_keep, 1);
+      if constexpr (DENSE) {
+        Sym3<double> C;
+        double wn;
+        inc_ndt_record_head(key, a, table, nb, C, wn);
+        local = atomicAdd(&s_keep, 1);  // (< VM_FIN_THREADS: one survivor per thread at most)
+        s_cov[local][0] = C.xx; s_cov[local][1] = C.xy; s_cov[local][2] = C.xz; s_cov[local][3] = C.yy; s_cov[local][4] = C.yz; s_cov[local][5] = C.zz; s_cov[local][6] = wn;
+        s_bucket[local] = nb;
+      } else {
+        inc_write_record<MODE>(key, a, table, nb);
+        local = atomicAdd(&s_keep, 1);
+      }
     }
   }
   __syncthreads();
   if (threadIdx.x == 0) {
     s_base = s_keep ? atomicAdd(counters, s_keep) : 0;
     if (s_drop) atomicAdd(ctl + 2, s_drop);
+  }
+  if constexpr (DENSE) {
+    const int t = threadIdx.x;
+    if (t < s_keep) inc_ndt_record_tail(Sym3<double>{s_cov[t][0], s_cov[t][1], s_cov[t][2], s_cov[t][3], s_cov[t][4], s_cov[t][5]}, s_cov[t][6], table, s_bucket[t]);
   }
   __syncthreads();
   if (nb != 0xFFFFFFFFu) occupied[s_base + local] = (int)nb;

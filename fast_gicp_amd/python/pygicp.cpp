@@ -20,6 +20,7 @@ using VGICPCuda = FastVGICPCuda<PointXYZ, PointXYZ>;
 using VGICP = FastVGICP<PointXYZ, PointXYZ>;
 using GICP = FastGICP<PointXYZ, PointXYZ>;
 using NDT = NDTCuda<PointXYZ, PointXYZ>;
+struct NDTMap : NDT { using NDT::NDT; };  // the C++ class again, bound as its own Python class (NDTCudaMap)
 using Points = py::array_t<double, py::array::c_style | py::array::forcecast>;
 using Mat4 = py::array_t<double, py::array::c_style | py::array::forcecast>;
 
@@ -187,6 +188,61 @@ static GICP::Covariances numpy_to_covs(const py::array_t<double, py::array::c_st
   return covs;
 }
 
+// not in the reference: an incremental target map for scan-to-map loops, the same methods on FastVGICPCuda and NDTCudaMap
+// (include/fast_vgicp_hip.h: fvh_vgicp_map_begin ... / fvh_ndt_map_begin ...).
+//   reg.begin_incremental_target(); reg.set_input_source(scan0); reg.insert_source_into_target(np.eye(4))
+//   per scan: reg.set_input_source(scan); T = reg.align(guess); reg.insert_source_into_target(); reg.prune_target(T[:3, 3], radius)
+template <typename Reg, typename PyClass>
+static void def_incremental_target(PyClass& c) {
+  c.def("begin_incremental_target", [](Reg& v, int expected_voxels) { v.beginIncrementalTarget(expected_voxels); }, py::arg("expected_voxels") = 0)
+      .def("insert_source_into_target", [](Reg& v, const py::object& T) {  // T = None: the final transformation of the last align
+        if (T.is_none()) v.insertSourceIntoTarget();
+        else v.insertSourceIntoTarget(numpy2mat4(T.cast<Mat4>()));
+      }, py::arg("T") = py::none())
+      .def("prune_target", [](Reg& v, const py::object& center, double radius, int max_age) {
+        if (center.is_none()) return v.pruneTarget(nullptr, radius, max_age);
+        const auto c = center.cast<py::array_t<double, py::array::c_style | py::array::forcecast>>();
+        if (c.size() != 3) throw std::invalid_argument("prune_target: center must have 3 elements");
+        return v.pruneTarget(c.data(), radius, max_age);
+      }, py::arg("center") = py::none(), py::arg("radius") = 0.0, py::arg("max_age") = 0)
+      // snapshots of the incremental target: save / restore / merge (fvh_*_voxelmap_export / _import / _merge_from). The dict is
+      // {resolution, mode, num_inserts, num_points, num_voxels, coords (n, 3) int32, sums (n, 10) float64, ages (n,) uint32}
+      .def("export_target_map", [](Reg& v) {
+        const fast_gicp::TargetMapSnapshot m = v.exportTargetMap();
+        const py::ssize_t n = (py::ssize_t)m.ages.size();
+        py::array_t<int> coords({n, (py::ssize_t)3});
+        py::array_t<double> sums({n, (py::ssize_t)10});
+        py::array_t<unsigned> ages(n);
+        if (n) {
+          std::memcpy(coords.mutable_data(), m.coords.data(), sizeof(int) * m.coords.size());
+          std::memcpy(sums.mutable_data(), m.sums.data(), sizeof(double) * m.sums.size());
+          std::memcpy(ages.mutable_data(), m.ages.data(), sizeof(unsigned) * m.ages.size());
+        }
+        py::dict d;
+        d["resolution"] = m.resolution; d["mode"] = m.mode; d["num_inserts"] = m.num_inserts; d["num_points"] = m.num_points; d["num_voxels"] = (int)n;
+        d["coords"] = coords; d["sums"] = sums; d["ages"] = ages;
+        return d;
+      })
+      .def("import_target_map", [](Reg& v, const py::dict& d) {
+        fast_gicp::TargetMapSnapshot m;
+        m.resolution = d["resolution"].cast<double>(); m.mode = d["mode"].cast<int>(); m.num_inserts = d["num_inserts"].cast<int>(); m.num_points = d["num_points"].cast<long long>();
+        const auto coords = d["coords"].cast<py::array_t<int, py::array::c_style | py::array::forcecast>>();
+        const auto sums = d["sums"].cast<py::array_t<double, py::array::c_style | py::array::forcecast>>();
+        m.coords.assign(coords.data(), coords.data() + coords.size());
+        m.sums.assign(sums.data(), sums.data() + sums.size());
+        if (d.contains("ages") && !d["ages"].is_none()) {
+          const auto ages = d["ages"].cast<py::array_t<unsigned, py::array::c_style | py::array::forcecast>>();
+          m.ages.assign(ages.data(), ages.data() + ages.size());
+        } else {
+          m.ages.assign(m.coords.size() / 3, 0u);
+        }
+        v.importTargetMap(m);
+      }, py::arg("snapshot"))
+      .def("merge_target_from", [](Reg& v, Reg& other) { v.mergeTargetFrom(other); }, py::arg("other"))
+      .def("save_target_map", [](Reg& v, const std::string& path) { v.saveTargetMap(path); }, py::arg("path"))
+      .def("load_target_map", [](Reg& v, const std::string& path) { v.loadTargetMap(path); }, py::arg("path"));
+}
+
 PYBIND11_MODULE(pygicp, m) {
   m.doc() = "pygicp on the MI355X HIP engine (surface of koide3/fast_gicp src/python/main.cpp)";
   m.def("downsample", &downsample, "downsample points", py::arg("points"), py::arg("downsample_resolution"));
@@ -258,7 +314,8 @@ PYBIND11_MODULE(pygicp, m) {
         return py::make_tuple(mat4_to_numpy(reg.getFinalTransformation()), best);
       }, py::arg("guesses"), py::arg("max_range") = std::numeric_limits<double>::max());
 
-  py::class_<VGICPCuda, Lsq, std::shared_ptr<VGICPCuda>>(m, "FastVGICPCuda")
+  py::class_<VGICPCuda, Lsq, std::shared_ptr<VGICPCuda>> vgicp_cuda(m, "FastVGICPCuda");
+  vgicp_cuda
       .def(py::init([](int device) { return std::make_shared<VGICPCuda>(device); }), py::arg("device") = 0)
       .def("set_resolution", &VGICPCuda::setResolution)
       .def("set_voxel_accumulation_mode", [](VGICPCuda& v, const std::string& mode) { v.setVoxelAccumulationMode(voxel_accumulation_mode(mode)); })
@@ -276,57 +333,8 @@ PYBIND11_MODULE(pygicp, m) {
       .def("prepare_next_source", [](VGICPCuda& v, const Points& p, int stages) { v.prepareNextSource(numpy2cloud(p), stages); }, py::arg("points"), py::arg("stages") = 2)
       .def("adopt_prepared_source", &VGICPCuda::adoptPreparedSource)
       .def("align_async", [](VGICPCuda& v, const Mat4& initial_guess) { v.alignAsync(numpy2mat4(initial_guess)); }, py::arg("initial_guess") = identity4())
-      .def("align_wait", [](VGICPCuda& v) { return mat4_to_numpy(v.alignWait()); })
-      // not in the reference: an incremental target map for scan-to-map loops (include/fast_vgicp_hip.h: fvh_vgicp_map_begin ...).
-      //   reg.begin_incremental_target(); reg.set_input_source(scan0); reg.insert_source_into_target(np.eye(4))
-      //   per scan: reg.set_input_source(scan); T = reg.align(guess); reg.insert_source_into_target(); reg.prune_target(T[:3, 3], radius)
-      .def("begin_incremental_target", &VGICPCuda::beginIncrementalTarget, py::arg("expected_voxels") = 0)
-      .def("insert_source_into_target", [](VGICPCuda& v, const py::object& T) {  // T = None: the final transformation of the last align
-        if (T.is_none()) v.insertSourceIntoTarget();
-        else v.insertSourceIntoTarget(numpy2mat4(T.cast<Mat4>()));
-      }, py::arg("T") = py::none())
-      .def("prune_target", [](VGICPCuda& v, const py::object& center, double radius, int max_age) {
-        if (center.is_none()) return v.pruneTarget(nullptr, radius, max_age);
-        const auto c = center.cast<py::array_t<double, py::array::c_style | py::array::forcecast>>();
-        if (c.size() != 3) throw std::invalid_argument("prune_target: center must have 3 elements");
-        return v.pruneTarget(c.data(), radius, max_age);
-      }, py::arg("center") = py::none(), py::arg("radius") = 0.0, py::arg("max_age") = 0)
-      // snapshots of the incremental target: save / restore / merge (fvh_vgicp_voxelmap_export / _import / _merge_from). The dict is
-      // {resolution, mode, num_inserts, num_points, num_voxels, coords (n, 3) int32, sums (n, 10) float64, ages (n,) uint32}
-      .def("export_target_map", [](VGICPCuda& v) {
-        const fast_gicp::TargetMapSnapshot m = v.exportTargetMap();
-        const py::ssize_t n = (py::ssize_t)m.ages.size();
-        py::array_t<int> coords({n, (py::ssize_t)3});
-        py::array_t<double> sums({n, (py::ssize_t)10});
-        py::array_t<unsigned> ages(n);
-        if (n) {
-          std::memcpy(coords.mutable_data(), m.coords.data(), sizeof(int) * m.coords.size());
-          std::memcpy(sums.mutable_data(), m.sums.data(), sizeof(double) * m.sums.size());
-          std::memcpy(ages.mutable_data(), m.ages.data(), sizeof(unsigned) * m.ages.size());
-        }
-        py::dict d;
-        d["resolution"] = m.resolution; d["mode"] = m.mode; d["num_inserts"] = m.num_inserts; d["num_points"] = m.num_points; d["num_voxels"] = (int)n;
-        d["coords"] = coords; d["sums"] = sums; d["ages"] = ages;
-        return d;
-      })
-      .def("import_target_map", [](VGICPCuda& v, const py::dict& d) {
-        fast_gicp::TargetMapSnapshot m;
-        m.resolution = d["resolution"].cast<double>(); m.mode = d["mode"].cast<int>(); m.num_inserts = d["num_inserts"].cast<int>(); m.num_points = d["num_points"].cast<long long>();
-        const auto coords = d["coords"].cast<py::array_t<int, py::array::c_style | py::array::forcecast>>();
-        const auto sums = d["sums"].cast<py::array_t<double, py::array::c_style | py::array::forcecast>>();
-        m.coords.assign(coords.data(), coords.data() + coords.size());
-        m.sums.assign(sums.data(), sums.data() + sums.size());
-        if (d.contains("ages") && !d["ages"].is_none()) {
-          const auto ages = d["ages"].cast<py::array_t<unsigned, py::array::c_style | py::array::forcecast>>();
-          m.ages.assign(ages.data(), ages.data() + ages.size());
-        } else {
-          m.ages.assign(m.coords.size() / 3, 0u);
-        }
-        v.importTargetMap(m);
-      }, py::arg("snapshot"))
-      .def("merge_target_from", &VGICPCuda::mergeTargetFrom, py::arg("other"))
-      .def("save_target_map", &VGICPCuda::saveTargetMap, py::arg("path"))
-      .def("load_target_map", &VGICPCuda::loadTargetMap, py::arg("path"));
+      .def("align_wait", [](VGICPCuda& v) { return mat4_to_numpy(v.alignWait()); });
+  def_incremental_target<VGICPCuda>(vgicp_cuda);
 
   py::class_<GICP, Lsq, std::shared_ptr<GICP>>(m, "FastGICP")  // main.cpp:183-190
       .def(py::init([](int device) { return std::make_shared<GICP>(device); }), py::arg("device") = 0)
@@ -349,7 +357,8 @@ PYBIND11_MODULE(pygicp, m) {
       .def("set_voxel_accumulation_mode", [](VGICP& v, const std::string& mode) { v.setVoxelAccumulationMode(voxel_accumulation_mode(mode)); })
       .def("set_neighbor_search_method", [](VGICP& v, const std::string& method) { v.setNeighborSearchMethod(search_method(method)); }, py::arg("method") = "DIRECT1");
 
-  py::class_<NDT, Lsq, std::shared_ptr<NDT>>(m, "NDTCuda")
+  py::class_<NDT, Lsq, std::shared_ptr<NDT>> ndt_cuda(m, "NDTCuda");
+  ndt_cuda
       .def(py::init([](int device) { return std::make_shared<NDT>(device); }), py::arg("device") = 0)
       .def("set_neighbor_search_method", [](NDT& n, const std::string& method, double radius) { n.setNeighborSearchMethod(search_method(method), radius); },
            py::arg("method") = "DIRECT1", py::arg("radius") = 1.5)
@@ -364,6 +373,12 @@ PYBIND11_MODULE(pygicp, m) {
       .def("adopt_prepared_source", &NDT::adoptPreparedSource)
       .def("align_async", [](NDT& n, const Mat4& initial_guess) { n.alignAsync(numpy2mat4(initial_guess)); }, py::arg("initial_guess") = identity4())
       .def("align_wait", [](NDT& n) { return mat4_to_numpy(n.alignWait()); });
+  // not in the reference: NDTCuda with an incremental target map (C++: the same NDTCuda methods; fvh_ndt_map_* / fvh_ndt_voxelmap_*). Its own
+  // Python class, so that NDTCuda keeps the reference's surface: everything of NDTCuda + the incremental-target methods of FastVGICPCuda,
+  // same names. The voxels are sums of the inserted points: snapshots carry mode 3.
+  py::class_<NDTMap, NDT, std::shared_ptr<NDTMap>> ndt_map(m, "NDTCudaMap");
+  ndt_map.def(py::init([](int device) { return std::make_shared<NDTMap>(device); }), py::arg("device") = 0);
+  def_incremental_target<NDTMap>(ndt_map);
 
   // testing hook: the host kd-tree behind NearestNeighborMethod::CPU_PARALLEL_KDTREE
   m.def("_kdtree_knn", [](const Points& points, int k) {

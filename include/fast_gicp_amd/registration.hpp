@@ -547,7 +547,23 @@ protected:
   Matrix6d final_hessian_;
 };
 
+/// A snapshot of an incremental target map (FastVGICPCuda / NDTCuda exportTargetMap / importTargetMap; C ABI: fvh_vgicp_voxelmap_export /
+/// _import, fvh_ndt_voxelmap_export / _import): per voxel coords[3], the device's ten fp64 sums and an age, rows in ascending packed-key
+/// order (z-major, then y, then x).
+struct TargetMapSnapshot {
+  double resolution = 1.0;
+  int mode = 0;          // 0 additive, 2 multiplicative (FastVGICPCuda); 3 = FVH_VOXEL_NDT_SUMS (NDTCuda)
+  int num_inserts = 0;   // the map's insert count
+  long long num_points = 0;
+  std::vector<int> coords;      // 3 per voxel
+  std::vector<double> sums;     // 10 per voxel: {sum p | sum C^-1 p (3), sum C | sum C^-1 | sum p p^T (6), count}
+  std::vector<unsigned> ages;   // inserts since the voxel was last touched
+  int num_voxels() const { return (int)ages.size(); }
+};
+
 namespace detail {
+inline void write_map_file(const std::string& path, const TargetMapSnapshot& m);  // (below: "Map snapshot files")
+inline TargetMapSnapshot read_map_file(const std::string& path);
 inline void check(int rc, const char* what, const char* err) {
   if (rc != 0) throw std::runtime_error(std::string(what) + " failed (status " + std::to_string(rc) + "): " + (err ? err : ""));
 }
@@ -598,6 +614,28 @@ inline constexpr DeviceCalls<fvh_ndt> kNdtCalls{
     {fvh_ndt_align, "align"}, {fvh_ndt_align_multi, "align_multi"}, {fvh_ndt_fitness_score, "fitness_score"},
     {fvh_ndt_set_lm_trace, "set_lm_trace"}, {fvh_ndt_get_lm_trace, "get_lm_trace"},
     {fvh_ndt_align_async, "align_async"}, {fvh_ndt_align_wait, "align_wait"}};
+/// The incremental target map and its snapshots (FastVGICPCuda, NDTCuda). Not part of the tables above: these are inline functions of a
+/// class template, so a program refers to a handle type's map calls only if it uses them
+template <typename Handle>
+struct MapCalls;
+template <>
+struct MapCalls<fvh_vgicp> {
+  static int begin(fvh_vgicp* h, int expected_voxels) { return fvh_vgicp_map_begin(h, expected_voxels); }
+  static int insert_source(fvh_vgicp* h, const double* T16) { return fvh_vgicp_map_insert_source(h, T16); }
+  static int prune(fvh_vgicp* h, const double* c3, double radius, int max_age, int* removed) { return fvh_vgicp_map_prune(h, c3, radius, max_age, removed); }
+  static int export_rows(fvh_vgicp* h, int* n, double* res, int* mode, int* inserts, long long* points, int* coords, double* sums, unsigned* ages) { return fvh_vgicp_voxelmap_export(h, n, res, mode, inserts, points, coords, sums, ages); }
+  static int import_rows(fvh_vgicp* h, int n, const int* coords, const double* sums, const unsigned* ages, double res, int mode, int inserts, long long points) { return fvh_vgicp_voxelmap_import(h, n, coords, sums, ages, res, mode, inserts, points); }
+  static int merge_from(fvh_vgicp* h, fvh_vgicp* other) { return fvh_vgicp_voxelmap_merge_from(h, other); }
+};
+template <>
+struct MapCalls<fvh_ndt> {
+  static int begin(fvh_ndt* h, int expected_voxels) { return fvh_ndt_map_begin(h, expected_voxels); }
+  static int insert_source(fvh_ndt* h, const double* T16) { return fvh_ndt_map_insert_source(h, T16); }
+  static int prune(fvh_ndt* h, const double* c3, double radius, int max_age, int* removed) { return fvh_ndt_map_prune(h, c3, radius, max_age, removed); }
+  static int export_rows(fvh_ndt* h, int* n, double* res, int* mode, int* inserts, long long* points, int* coords, double* sums, unsigned* ages) { return fvh_ndt_voxelmap_export(h, n, res, mode, inserts, points, coords, sums, ages); }
+  static int import_rows(fvh_ndt* h, int n, const int* coords, const double* sums, const unsigned* ages, double res, int mode, int inserts, long long points) { return fvh_ndt_voxelmap_import(h, n, coords, sums, ages, res, mode, inserts, points); }
+  static int merge_from(fvh_ndt* h, fvh_ndt* other) { return fvh_ndt_voxelmap_merge_from(h, other); }
+};
 }  // namespace detail
 
 /// What FastVGICPCuda, FastGICP, FastVGICP and NDTCuda share (no reference counterpart): the device handle and LsqRegistration's
@@ -606,6 +644,7 @@ inline constexpr DeviceCalls<fvh_ndt> kNdtCalls{
 template <typename Handle, typename PointSource, typename PointTarget>
 class DeviceRegistration : public LsqRegistration<PointSource, PointTarget> {
   using Base = LsqRegistration<PointSource, PointTarget>;
+  using Map = detail::MapCalls<Handle>;
 
 public:
   using PointCloudSourceConstPtr = typename Base::PointCloudSourceConstPtr;
@@ -654,6 +693,49 @@ protected:
     call(calls_->align_wait, &r);
     return this->final_transformation_ = this->take_result(r).cast_float();
   }
+
+  // ---- incremental target map and its snapshots (no reference counterpart; C ABI: fvh_vgicp_map_* / fvh_ndt_map_*, fvh_*_voxelmap_*, through detail::MapCalls): the
+  // classes whose handle offers them (FastVGICPCuda, NDTCuda) make these public; what is theirs -- setInputTarget ending the mode,
+  // loadTargetMap choosing the voxel type -- stays with them.
+  void beginIncrementalTarget(int expected_voxels = 0) {
+    call(Map::begin(core_, expected_voxels), "map_begin");
+    this->target_.reset();
+    incremental_target_ = true;
+  }
+  /// adds the current source (as setInputSource left it) to the map at pose T
+  void insertSourceIntoTarget(const Matrix4f& T) {
+    if (!this->input_) throw std::invalid_argument("insertSourceIntoTarget: source cloud not set");
+    double T16[16];
+    Isometry3d::from(T).to_colmajor16(T16);
+    call(Map::insert_source(core_, T16), "map_insert_source");
+  }
+  /// ... at the final transformation of the last align()
+  void insertSourceIntoTarget() { insertSourceIntoTarget(this->final_transformation_); }
+  /// drops voxels further than `radius` from `center` (null: no distance rule) and those untouched by the last max_age inserts (<= 0: no age rule); returns the number removed
+  int pruneTarget(const double* center3, double radius, int max_age = 0) {
+    int removed = 0;
+    call(Map::prune(core_, center3, radius, max_age, &removed), "map_prune");
+    return removed;
+  }
+  bool hasIncrementalTarget() const { return incremental_target_; }
+  TargetMapSnapshot exportTargetMap() {
+    TargetMapSnapshot m;
+    int n = 0;
+    call(Map::export_rows(core_, &n, &m.resolution, &m.mode, &m.num_inserts, &m.num_points, nullptr, nullptr, nullptr), "voxelmap_export");
+    m.coords.resize(3 * (size_t)n); m.sums.resize(10 * (size_t)n); m.ages.resize((size_t)n);
+    if (n) call(Map::export_rows(core_, &n, &m.resolution, &m.mode, &m.num_inserts, &m.num_points, m.coords.data(), m.sums.data(), m.ages.data()), "voxelmap_export");
+    return m;
+  }
+  /// adds the snapshot's voxels into the live incremental target (same resolution and mode)
+  void importTargetMap(const TargetMapSnapshot& m) {
+    const size_t n = m.ages.size();
+    if (m.coords.size() != 3 * n || m.sums.size() != 10 * n) throw std::invalid_argument("importTargetMap: coords, sums and ages differ in length");
+    call(Map::import_rows(core_, (int)n, n ? m.coords.data() : nullptr, n ? m.sums.data() : nullptr, n ? m.ages.data() : nullptr, m.resolution, m.mode, m.num_inserts, m.num_points), "voxelmap_import");
+  }
+  void merge_target_from(DeviceRegistration& other) { call(Map::merge_from(core_, other.core_), "voxelmap_merge_from"); }  // (the classes' mergeTargetFrom takes their own type)
+  void saveTargetMap(const std::string& path) { detail::write_map_file(path, exportTargetMap()); }
+  bool has_device_target() const override { return incremental_target_; }
+  bool incremental_target_ = false;  // beginIncrementalTarget .. setInputTarget
 
   double linearize(const Isometry3d& trans, Matrix6d* H, Vector6d* b) override {
     double T16[16], err = 0, Hc[36];
@@ -708,19 +790,6 @@ protected:
   const detail::DeviceCalls<Handle>* calls_;
   Handle* core_ = nullptr;
   std::vector<float> scratch_xyz_;  // only used for point types that are not 12 / 16 bytes of packed xyz
-};
-
-/// A snapshot of FastVGICPCuda's incremental target map (exportTargetMap / importTargetMap; C ABI: fvh_vgicp_voxelmap_export / _import):
-/// per voxel coords[3], the device's ten fp64 sums and an age, rows in ascending packed-key order (z-major, then y, then x).
-struct TargetMapSnapshot {
-  double resolution = 1.0;
-  int mode = 0;          // 0 additive, 2 multiplicative
-  int num_inserts = 0;   // the map's insert count
-  long long num_points = 0;
-  std::vector<int> coords;      // 3 per voxel
-  std::vector<double> sums;     // 10 per voxel: {sum p | sum C^-1 p (3), sum C | sum C^-1 (6), count}
-  std::vector<unsigned> ages;   // inserts since the voxel was last touched
-  int num_voxels() const { return (int)ages.size(); }
 };
 
 namespace detail {
@@ -789,6 +858,7 @@ class FastVGICPCuda : public DeviceRegistration<fvh_vgicp, PointSource, PointTar
   using Base = DeviceRegistration<fvh_vgicp, PointSource, PointTarget>;
   using Base::call;
   using Base::core_;
+  using Base::incremental_target_;
   using Base::input_;
   using Base::scratch_xyz_;
   using Base::target_;
@@ -877,49 +947,21 @@ public:
   //     per scan: setInputSource(scan); align(out, guess); insertSourceIntoTarget(); pruneTarget(position, radius);
   // The map has no host cloud behind it: getInputTarget() is null, align() does not ask for one, swapSourceAndTarget() throws
   // (FVH_ERR_BAD_STATE) and getFitnessScore() needs a target cloud as before. setInputTarget() ends the mode.
-  void beginIncrementalTarget(int expected_voxels = 0) {
-    call(fvh_vgicp_map_begin(core_, expected_voxels), "map_begin");
-    target_.reset();
-    incremental_target_ = true;
-  }
-  /// adds the current source (points + covariances as setInputSource left them) to the map at pose T
-  void insertSourceIntoTarget(const Matrix4f& T) {
-    if (!input_) throw std::invalid_argument("insertSourceIntoTarget: source cloud not set");
-    double T16[16];
-    Isometry3d::from(T).to_colmajor16(T16);
-    call(fvh_vgicp_map_insert_source(core_, T16), "map_insert_source");
-  }
-  /// ... at the final transformation of the last align()
-  void insertSourceIntoTarget() { insertSourceIntoTarget(this->final_transformation_); }
-  /// drops voxels further than `radius` from `center` (null: no distance rule) and those untouched by the last max_age inserts (<= 0: no age rule); returns the number removed
-  int pruneTarget(const double* center3, double radius, int max_age = 0) {
-    int removed = 0;
-    call(fvh_vgicp_map_prune(core_, center3, radius, max_age, &removed), "map_prune");
-    return removed;
-  }
-  bool hasIncrementalTarget() const { return incremental_target_; }
+  // (the calls themselves: DeviceRegistration, shared with NDTCuda; the source is added with its points + covariances as setInputSource left them)
+  using Base::beginIncrementalTarget;
+  using Base::insertSourceIntoTarget;
+  using Base::pruneTarget;
+  using Base::hasIncrementalTarget;
 
   // ---- snapshots of the incremental target map (C ABI: fvh_vgicp_voxelmap_export / _import / _merge_from): save, restore, merge.
   // Restore = loadTargetMap(path) on a fresh object, or beginIncrementalTarget() + importTargetMap(). Import and merge ADD: sums and
   // counts add per voxel (exactly: both voxel types are pure sums), ages and the insert count carry over, so pruneTarget(max_age) means on
   // a restored map what it meant on the original.
-  TargetMapSnapshot exportTargetMap() {
-    TargetMapSnapshot m;
-    int n = 0;
-    call(fvh_vgicp_voxelmap_export(core_, &n, &m.resolution, &m.mode, &m.num_inserts, &m.num_points, nullptr, nullptr, nullptr), "voxelmap_export");
-    m.coords.resize(3 * (size_t)n); m.sums.resize(10 * (size_t)n); m.ages.resize((size_t)n);
-    if (n) call(fvh_vgicp_voxelmap_export(core_, &n, &m.resolution, &m.mode, &m.num_inserts, &m.num_points, m.coords.data(), m.sums.data(), m.ages.data()), "voxelmap_export");
-    return m;
-  }
-  /// adds the snapshot's voxels into the live incremental target (same resolution and mode)
-  void importTargetMap(const TargetMapSnapshot& m) {
-    const size_t n = m.ages.size();
-    if (m.coords.size() != 3 * n || m.sums.size() != 10 * n) throw std::invalid_argument("importTargetMap: coords, sums and ages differ in length");
-    call(fvh_vgicp_voxelmap_import(core_, (int)n, n ? m.coords.data() : nullptr, n ? m.sums.data() : nullptr, n ? m.ages.data() : nullptr, m.resolution, m.mode, m.num_inserts, m.num_points), "voxelmap_import");
-  }
+  using Base::exportTargetMap;
+  using Base::importTargetMap;
   /// adds the live incremental target of `other` (same device, resolution and mode) into this one, device to device; `other` is unchanged
-  void mergeTargetFrom(FastVGICPCuda& other) { call(fvh_vgicp_voxelmap_merge_from(core_, other.core_), "voxelmap_merge_from"); }
-  void saveTargetMap(const std::string& path) { detail::write_map_file(path, exportTargetMap()); }
+  void mergeTargetFrom(FastVGICPCuda& other) { this->merge_target_from(other); }
+  using Base::saveTargetMap;
   /// adds the file's map into the incremental target; an object without one takes the file's resolution and voxel mode and starts one sized for it
   void loadTargetMap(const std::string& path) {
     const TargetMapSnapshot m = detail::read_map_file(path);
@@ -979,10 +1021,8 @@ protected:
   std::vector<int> find_neighbors_parallel_kdtree(const CloudT& cloud) const {
     return detail::host_kdtree_neighbors(cloud, k_correspondences_, host::omp_threads_for((int)cloud.size()));
   }
-  bool has_device_target() const override { return incremental_target_; }
 
 private:
-  bool incremental_target_ = false;                                                              // beginIncrementalTarget .. setInputTarget
   int k_correspondences_ = 20;                                                                   // :24
   double voxel_resolution_ = 1.0;                                                                // :25
   RegularizationMethod regularization_method_ = RegularizationMethod::PLANE;                     // :26
@@ -1136,6 +1176,7 @@ class NDTCuda : public DeviceRegistration<fvh_ndt, PointSource, PointTarget> {
   using Base = DeviceRegistration<fvh_ndt, PointSource, PointTarget>;
   using Base::call;
   using Base::core_;
+  using Base::incremental_target_;
   using Base::input_;
   using Base::scratch_xyz_;
   using Base::target_;
@@ -1153,7 +1194,34 @@ public:
 
   void swapSourceAndTarget() override { call(fvh_ndt_swap_source_and_target(core_), "swap_source_and_target"); input_.swap(target_); }
   void setInputSource(const PointCloudSourceConstPtr& cloud) override { this->take_source(cloud); }  // ndt_cuda_impl.hpp:52-60
-  void setInputTarget(const PointCloudTargetConstPtr& cloud) override { this->take_target(cloud); }  // :63-73
+  void setInputTarget(const PointCloudTargetConstPtr& cloud) override {  // :63-73
+    if (this->take_target(cloud)) incremental_target_ = false;  // (the next align builds the batch map of this cloud: an incremental target ends)
+  }
+
+  // ---- incremental target map (no reference counterpart; C ABI: fvh_ndt_map_begin / _insert_source / _prune, fvh_ndt_voxelmap_*), the calls
+  // FastVGICPCuda has for its own, for scan-to-map localisation:
+  //     beginIncrementalTarget(); setInputSource(scan 0); insertSourceIntoTarget(Identity);
+  //     per scan: setInputSource(scan); align(out, guess); insertSourceIntoTarget(); pruneTarget(position, radius);
+  // The voxels are sums of the inserted POINTS (sum p, sum p p^T): the map is the one setInputTarget(all inserted points) would give. It has no
+  // host cloud behind it: getInputTarget() is null, align() does not ask for one, swapSourceAndTarget() throws (FVH_ERR_BAD_STATE) and
+  // getFitnessScore() needs a target cloud as before. setInputTarget() ends the mode. Snapshots carry mode 3 (FVH_VOXEL_NDT_SUMS).
+  using Base::beginIncrementalTarget;
+  using Base::insertSourceIntoTarget;
+  using Base::pruneTarget;
+  using Base::hasIncrementalTarget;
+  using Base::exportTargetMap;
+  using Base::importTargetMap;
+  void mergeTargetFrom(NDTCuda& other) { this->merge_target_from(other); }
+  using Base::saveTargetMap;
+  /// adds the file's map into the incremental target; an object without one takes the file's resolution and starts one sized for it
+  void loadTargetMap(const std::string& path) {
+    const TargetMapSnapshot m = detail::read_map_file(path);
+    if (!incremental_target_) {
+      call(fvh_ndt_set_resolution(core_, m.resolution), "set_resolution");
+      beginIncrementalTarget(std::max(m.num_voxels(), 1));
+    }
+    importTargetMap(m);
+  }
 
   // ---- frame streams as a two-stage pipeline (no reference counterpart; C ABI: fvh_ndt_align_async / _wait, fvh_ndt_prepare_source_device /
   // _adopt_prepared_source). kitti.cpp:95-128 with the preparation of frame k+1 hidden under the registration of frame k:

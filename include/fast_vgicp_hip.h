@@ -138,6 +138,9 @@ int fvh_vgicp_set_engine_params(fvh_vgicp* h, const fvh_engine_params* p);
  * the CUDA core only has the additive voxel): ADDITIVE / ADDITIVE_WEIGHTED -> AdditiveGaussianVoxel (fast_vgicp_voxel.hpp:105-122),
  * MULTIPLICATIVE -> MultiplicativeGaussianVoxel (:79-103: sum of C^-1 and C^-1 p, inverted at finalize). Takes effect at the next map build. */
 enum fvh_voxel_accumulation_mode { FVH_VOXEL_ADDITIVE = 0, FVH_VOXEL_ADDITIVE_WEIGHTED = 1, FVH_VOXEL_MULTIPLICATIVE = 2 };
+/* `mode` of a map snapshot taken from an NDT handle (fvh_ndt_voxelmap_export): its sums are {sum p, sum p p^T, count}. Never a voxel
+ * accumulation mode of a VGICP handle, whose snapshots carry 0 or 2. */
+enum { FVH_VOXEL_NDT_SUMS = 3 };
 int fvh_vgicp_set_voxel_accumulation_mode(fvh_vgicp* h, int mode);
 
 int fvh_vgicp_swap_source_and_target(fvh_vgicp* h);                                          /* [VC]:44, [VCU]:97-107 */
@@ -266,7 +269,7 @@ int fvh_vgicp_adopt_prepared_source(fvh_vgicp* h);
  * Refused by map_begin / map_insert_* / map_prune, the handle stays usable: multi-GPU handles (communicator, peers or tile attached) and
  * fvh_vgicp_set_target_map_sharding (FVH_ERR_UNSUPPORTED); FVH_COMPUTE_CUDA_COMPAT (FVH_ERR_UNSUPPORTED: its voxel sums are float sums in point order, which an in-place map
  * cannot reproduce); an align_async in flight, insert / prune without map_begin, a source without covariances (FVH_ERR_BAD_STATE); a
- * null or non-finite T (FVH_ERR_INVALID_ARGUMENT). NDT handles have no incremental map (their maps are rebuilt per frame by design). */
+ * null or non-finite T (FVH_ERR_INVALID_ARGUMENT). NDT handles: fvh_ndt_map_* below. */
 int fvh_vgicp_map_begin(fvh_vgicp* h, int expected_voxels);
 int fvh_vgicp_map_insert_source(fvh_vgicp* h, const double* T16);
 int fvh_vgicp_map_insert_cloud(fvh_vgicp* h, const float* xyz, int n, int stride_floats, const double* covs9, const double* T16, int on_device);
@@ -459,6 +462,31 @@ int fvh_ndt_align_wait(fvh_ndt* h, fvh_lm_result* result);
 int fvh_ndt_prepare_source_device(fvh_ndt* h, const float* d_xyz, int n, int stride_floats);
 int fvh_ndt_prepare_source(fvh_ndt* h, const float* xyz, int n, int stride_floats); /* the same for a HOST cloud, consumed before the call returns */
 int fvh_ndt_adopt_prepared_source(fvh_ndt* h);
+/* new: an INCREMENTAL NDT target map (scan-to-map localisation), the NDT counterpart of fvh_vgicp_map_* / fvh_vgicp_voxelmap_* above with
+ * the same semantics call by call; what differs:
+ *   - An NDT voxel is {sum p', sum p' p'^T, count} of the inserted points p' = (float)(T p) (formed in fp64, rounded once; the products are
+ *     fp64 products of the float values): points only, no covariances -- fvh_ndt_map_insert_cloud takes none. After every insert the map is
+ *     the map fvh_ndt_set_target_cloud(all p') + fvh_ndt_create_target_voxelmap would build: same voxel set, same counts exactly, means and
+ *     (MIN_EIG-regularised) covariances recomputed from the sums, equal up to the order of the fp64 sums.
+ *   - The map is the handle's TARGET map: fvh_ndt_get_voxels(h, 1, ...), update_correspondences, compute_error, align, align_multi,
+ *     align_async / _wait and the prepare_source* pipeline read it unchanged, in both distance modes (D2D still builds its source map from
+ *     the source cloud per frame), and none of them asks for a target cloud while it is live.
+ *   - Snapshots carry mode = FVH_VOXEL_NDT_SUMS (3); file format and version are those of the VGICP snapshots. fvh_ndt_voxelmap_import
+ *     refuses mode 0 / 1 / 2 and fvh_vgicp_voxelmap_import refuses mode 3 (FVH_ERR_INVALID_ARGUMENT): sums of different kinds never add.
+ *   - While it is live: fvh_ndt_set_resolution to another value, fvh_ndt_swap_source_and_target, fvh_ndt_comm_init / _set_source_tile with
+ *     nranks > 1 are FVH_ERR_BAD_STATE; FVH_COMPUTE_CUDA_COMPAT is FVH_ERR_UNSUPPORTED (set before or after map_begin); map_begin and the
+ *     other map calls on a tiled / multi-GPU handle are FVH_ERR_UNSUPPORTED; fvh_ndt_fitness_score still needs a target cloud.
+ *     fvh_ndt_set_target_cloud* leaves the map alone but marks the cloud as newer: the next fvh_ndt_create_target_voxelmap /
+ *     _create_voxelmaps -- fvh_ndt_align and _align_multi make that call themselves -- builds the batch map of that cloud and the mode ends
+ *     (a target cloud set BEFORE map_begin stays beside the map, e.g. for fitness_score). Every refusal leaves the handle usable. */
+int fvh_ndt_map_begin(fvh_ndt* h, int expected_voxels);
+int fvh_ndt_map_insert_source(fvh_ndt* h, const double* T16);
+int fvh_ndt_map_insert_cloud(fvh_ndt* h, const float* xyz, int n, int stride_floats, const double* T16, int on_device);
+int fvh_ndt_map_prune(fvh_ndt* h, const double* center3, double radius, int max_age, int* num_removed);
+int fvh_ndt_map_get_info(fvh_ndt* h, int* incremental, int* num_voxels, int* capacity, int* num_inserts, long long* num_points, int* num_dropped);
+int fvh_ndt_voxelmap_export(fvh_ndt* h, int* num_voxels, double* resolution, int* mode, int* num_inserts, long long* num_points, int* coords3, double* sums10, unsigned* ages);
+int fvh_ndt_voxelmap_import(fvh_ndt* h, int n, const int* coords3, const double* sums10, const unsigned* ages, double resolution, int mode, int num_inserts, long long num_points);
+int fvh_ndt_voxelmap_merge_from(fvh_ndt* h, fvh_ndt* other);
 /* new (round 6): the output of the filter's last ApproximateVoxelGrid call becomes the cloud WITHOUT a copy -- the filter's emit kernel wrote it as
  * float4 too, and that buffer is swapped with the cloud's (what fvh_voxelgrid_device_points + fvh_ndt_set_source_cloud_device /
  * _prepare_source_device do, minus the widening kernel and its launch: 8 of a LiDAR frame's 141 us). An output can be taken once; the filter's
