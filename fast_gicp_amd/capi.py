@@ -230,6 +230,27 @@ class _IncrementalMap:
         write_map_file(path, self.map_export())
 
 
+class _MapTarget:
+    """The live incremental map as the handle's target cloud (include/fast_vgicp_hip.h: fvh_{vgicp,ndt}_target_from_map, _get_target_points):
+    mixed into VGICPMapCore and NDTMapCore, the handle classes for scan-to-map work."""
+
+    def target_from_map(self, min_points=1):
+        """The target cloud becomes one point per voxel with >= min_points points -- the voxel's mean (VGICP: + its covariance as the target
+        covariance), rows in ascending packed-key order: with min_points <= 1 row i is row i of map_export(). A snapshot: call it again after
+        an insert or a prune. The map stays live and untouched. -> number of points (0: the handle has no target cloud)"""
+        n = C.c_int(0)
+        self._call("target_from_map", int(min_points), C.byref(n))
+        return n.value
+
+    def get_target_points(self):
+        """The current target cloud, (n, 3) float32 in its original order (however it was set: host, device, filter, target_from_map)."""
+        n = C.c_int(0)
+        self._call("get_num_target_points", C.byref(n))
+        out = np.empty((n.value, 3), np.float32)
+        self._call("get_target_points", _p(out) if n.value else None)
+        return out
+
+
 class _Core:
     _prefix = ""
 
@@ -719,6 +740,11 @@ class VGICPCore(_Core, _IncrementalMap):
         return n.value
 
 
+class VGICPMapCore(VGICPCore, _MapTarget):
+    """A VGICP handle for scan-to-map work: VGICPCore (which has the map_* calls) + target_from_map / get_target_points, on the same C handle
+    type -- as NDTMapCore is to NDTCore."""
+
+
 class VoxelGrid:
     """pcl::VoxelGrid / pcl::ApproximateVoxelGrid on the device (fvh_voxelgrid_*): same output points in the same
     order as the PCL filters the reference's callers run before registration (src/align.cpp:136-147)."""
@@ -906,7 +932,7 @@ class NDTCore(_Core):
         return coords, num, means, covs
 
 
-class NDTMapCore(NDTCore, _IncrementalMap):
+class NDTMapCore(NDTCore, _IncrementalMap, _MapTarget):
     """An NDT handle with the calls of its incremental target map (include/fast_vgicp_hip.h: fvh_ndt_map_* / fvh_ndt_voxelmap_*): map_begin,
     map_insert_source, map_prune, map_info, map_export, map_import, map_merge_from, map_save come from _IncrementalMap as on VGICPCore; NDT
     voxels take points only. Everything else is NDTCore's, on the same C handle type."""

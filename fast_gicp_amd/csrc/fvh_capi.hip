@@ -748,6 +748,27 @@ int fvh_vgicp_voxelmap_merge_from(fvh_vgicp* h, fvh_vgicp* other) {
   other->e.quiet = false;  // (its stream now holds a wait)
   return incmap_merge_from(&h->e, h->voxelmap, other->voxelmap, other->e.stream, h->merge_ev[0], h->merge_ev[1]);
 }
+// ---- the live incremental map as the handle's target cloud (host_incmap.inc.hpp: incmap_to_cloud) ----
+int fvh_vgicp_target_from_map(fvh_vgicp* h, int min_points, int* num_points_out) {
+  CHECK_HANDLE(h);
+  if (!h->incremental()) return h->e.fail(FVH_ERR_BAD_STATE, "target_from_map: no incremental map is live (fvh_vgicp_map_begin)");
+  // the target cloud is replaced as by set_target_cloud -- but the map and the VOXEL correspondences stored against it are not the cloud's:
+  // only nearest-point correspondences (indices into the old cloud) and the per-point records die with it
+  h->gicp_records.invalidate();
+  if (h->e.corr_kind == 1) h->e.has_corr = false;
+  return incmap_to_cloud(&h->e, h->voxelmap, min_points, h->target, true, true, num_points_out);
+}
+static int get_points_host(Engine* e, const CloudDev& c, float* xyz3, const char* who) {
+  if (!c.has_pts) return e->fail(FVH_ERR_BAD_STATE, std::string(who) + ": cloud not set");
+  if (c.n == 0) return FVH_OK;
+  if (!xyz3) return e->fail(FVH_ERR_INVALID_ARGUMENT, std::string(who) + ": null");
+  std::vector<float4> h((size_t)c.n);
+  HIP_OR_FAIL(e, hipMemcpyAsync(h.data(), c.pts.p, sizeof(float4) * h.size(), hipMemcpyDeviceToHost, e->stream));
+  HIP_OR_FAIL(e, hipStreamSynchronize(e->stream));
+  for (int i = 0; i < c.n; i++) { xyz3[3 * (size_t)i] = h[(size_t)i].x; xyz3[3 * (size_t)i + 1] = h[(size_t)i].y; xyz3[3 * (size_t)i + 2] = h[(size_t)i].z; }
+  return FVH_OK;
+}
+int fvh_vgicp_get_target_points(fvh_vgicp* h, float* xyz3) { CHECK_HANDLE(h); return get_points_host(&h->e, h->target, xyz3, "get_target_points"); }
 int fvh_vgicp_set_voxel_accumulation_mode(fvh_vgicp* h, int mode) {
   CHECK_HANDLE(h);
   if (mode < 0 || mode > 2) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "unknown voxel accumulation mode");
@@ -1512,6 +1533,16 @@ int fvh_ndt_voxelmap_merge_from(fvh_ndt* h, fvh_ndt* other) {
   other->e.quiet = false;  // (its stream now holds a wait)
   return incmap_merge_from(&h->e, h->target_vm, other->target_vm, other->e.stream, h->merge_ev[0], h->merge_ev[1]);
 }
+// The live map as the handle's target cloud (points only). The map stays the target MAP: the cloud is a snapshot OF it, not a cloud set
+// beside it -- target_newer is fvh_ndt_set_target_cloud*'s rule, and a cloud such a call left behind is gone now, so nothing is newer.
+int fvh_ndt_target_from_map(fvh_ndt* h, int min_points, int* num_points_out) {
+  CHECK_HANDLE(h);
+  { const int rc = ndt_map_live(h, "target_from_map"); if (rc) return rc; }
+  h->target_newer = false;
+  return incmap_to_cloud(&h->e, h->target_vm, min_points, h->target, false, false, num_points_out);
+}
+int fvh_ndt_get_num_target_points(const fvh_ndt* h, int* n) { if (!h || !n) return FVH_ERR_INVALID_ARGUMENT; *n = h->target.has_pts ? h->target.n : 0; return FVH_OK; }
+int fvh_ndt_get_target_points(fvh_ndt* h, float* xyz3) { CHECK_HANDLE(h); return get_points_host(&h->e, h->target, xyz3, "get_target_points"); }
 static int ndt_ready(fvh_ndt* h) {
   if (!h->source.has_pts) return h->e.fail(FVH_ERR_BAD_STATE, "source cloud not set");
   if (!h->target_vm.valid) return h->e.fail(FVH_ERR_BAD_STATE, "target voxel map not built (create_voxelmaps)");

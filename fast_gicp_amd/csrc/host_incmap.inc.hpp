@@ -382,3 +382,84 @@ int incmap_merge_from(Engine* e, VoxelMapDev& vm, VoxelMapDev& from, hipStream_t
   HIP_OR_FAIL(e, hipStreamWaitEvent(from_stream, ev_after, 0));
   return rc;
 }
+
+// ---- the live map as a point target (fvh_vgicp_target_from_map / fvh_ndt_target_from_map; kernels_voxelmap.hpp: "point target") ---------
+// Cloud `c` becomes one point per voxel with >= min_points points -- the record's float mean, with_cov: + the record's covariance -- rows in
+// ascending packed-key order (the row order of incmap_export). The map is only read. Everything is queued on the main stream with scratch of
+// the map's own (VoxelMapDev::inc.tm_*): a preparation on the second stream may hold the Engine-wide sort buffers (finding 1),
+// which is also why the cloud's Morton order stays lazy here (ensure_sorted where it is consumed, as for any cloud).
+// One readback {selected, voxel count, bounds} sizes the sort and names the key route; the cloud's size is host state, so it is not optional.
+// Order by the 63-bit key: ONE radix sweep over the key compressed against the bounds of the selected voxels whenever that box fits 32 bits
+// (a 300 m x 300 m x 30 m map at 0.5 m: 10 + 10 + 6 bits = 3 passes of 9 bits), else two stable sweeps, low word then high word (8 passes).
+inline int bits_for_span(unsigned span) { int b = 0; while (b < 32 && (span >> b) != 0u) b++; return b; }  // values 0..span need this many bits
+
+int incmap_to_cloud(Engine* e, VoxelMapDev& vm, int min_points, CloudDev& c, bool with_cov, bool want_box, int* num_points) {
+  VoxelMapDev::Incremental& inc = vm.inc;
+  const int bound = (int)std::min<long long>(inc.voxel_bound, (long long)vm.capacity);  // (the host keeps the load factor <= 0.5: capacity bounds the count too)
+  HIP_OR_FAIL(e, inc.tm_ctl.ensure(sizeof(VmTargetCtl)));
+  VmTargetCtl* d_ctl = inc.tm_ctl.as<VmTargetCtl>();
+  unsigned long long* sel_keys = nullptr;
+  unsigned* sel_buckets = nullptr;
+  VmTargetCtl ctl;
+  std::memset(&ctl, 0, sizeof(ctl));
+  if (bound > 0) {
+    HIP_OR_FAIL(e, inc.tm_sel.ensure((sizeof(unsigned long long) + sizeof(unsigned)) * (size_t)bound));
+    sel_keys = inc.tm_sel.as<unsigned long long>();
+    sel_buckets = reinterpret_cast<unsigned*>(sel_keys + bound);
+    {
+      ProfScope ps(e, "map_target");
+      const int chunks = (bound + VM_FIN_THREADS - 1) / VM_FIN_THREADS;
+      vm_target_begin_kernel<<<1, 64, 0, e->stream>>>(d_ctl);
+      vm_target_select_kernel<<<std::min(chunks, VM_TARGET_MAX_WGS), VM_FIN_THREADS, 0, e->stream>>>(vm.table.as<uint4>(), vm.occupied.as<int>(), vm.counters_cur(), bound, min_points, sel_keys,
+                                                                                                      sel_buckets, d_ctl);
+    }
+    HIP_OR_FAIL(e, hipGetLastError());
+    HIP_OR_FAIL(e, hipMemcpyAsync(&ctl, d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, e->stream));
+    HIP_OR_FAIL(e, hipStreamSynchronize(e->stream));
+    inc.voxel_bound = ctl.num_voxels;
+  }
+  const int m = ctl.selected;
+  // from here on the cloud is replaced (what set_*_cloud drops: covariances, neighbours, Morton order)
+  c.has_cov = false; c.has_nbr = false; c.has_cov_sorted = false; c.has_sorted = false;
+  if (num_points) *num_points = m;
+  if (m == 0) { c.n = 0; c.has_pts = false; return FVH_OK; }  // no voxel qualifies: no target cloud
+  HIP_OR_FAIL(e, inc.tm_keys.ensure(sizeof(unsigned) * 2 * (size_t)m));
+  HIP_OR_FAIL(e, inc.tm_idx.ensure(sizeof(int) * 2 * (size_t)m));
+  HIP_OR_FAIL(e, inc.tm_rows.ensure(sizeof(float4) * (size_t)m));
+  if (with_cov) HIP_OR_FAIL(e, c.cov.ensure(sizeof(float4) * 2 * (size_t)m));
+  unsigned* keys[2] = {inc.tm_keys.as<unsigned>(), inc.tm_keys.as<unsigned>() + m};
+  int* idx[2] = {inc.tm_idx.as<int>(), inc.tm_idx.as<int>() + m};
+  const int blocks = (m + 255) / 256;
+  VmTargetKey kp;
+  std::memset(&kp, 0, sizeof(kp));
+  const int bx = bits_for_span(ctl.umax[0] - ctl.umin[0]), by = bits_for_span(ctl.umax[1] - ctl.umin[1]), bz = bits_for_span(ctl.umax[2] - ctl.umin[2]);
+  const int* order = nullptr;
+  {
+    ProfScope ps(e, "map_target");
+    int sorted = 0;
+    if (bx + by + bz <= 32) {
+      for (int a = 0; a < 3; a++) kp.lo[a] = ctl.umin[a];
+      kp.bx = bx; kp.bxy = bx + by; kp.part = 0;
+      vm_target_keys_kernel<<<blocks, 256, 0, e->stream>>>(sel_keys, nullptr, m, kp, keys[0], idx[0]);
+      { const int rc = radix_sort_pairs(e, keys, idx, m, bx + by + bz, &sorted, e->stream, &inc.tm_hist); if (rc) return rc; }
+      order = idx[sorted];
+    } else {
+      kp.part = 1;
+      vm_target_keys_kernel<<<blocks, 256, 0, e->stream>>>(sel_keys, nullptr, m, kp, keys[0], idx[0]);
+      { const int rc = radix_sort_pairs(e, keys, idx, m, 32, &sorted, e->stream, &inc.tm_hist); if (rc) return rc; }
+      // the second sweep starts from the first one's result: radix_sort_pairs reads pair 0 first
+      unsigned* keys2[2] = {keys[sorted], keys[sorted ^ 1]};
+      int* idx2[2] = {idx[sorted], idx[sorted ^ 1]};
+      kp.part = 2;
+      vm_target_keys_kernel<<<blocks, 256, 0, e->stream>>>(sel_keys, idx2[0], m, kp, keys2[0], idx2[0]);
+      { const int rc = radix_sort_pairs(e, keys2, idx2, m, 31, &sorted, e->stream, &inc.tm_hist); if (rc) return rc; }
+      order = idx2[sorted];
+    }
+    vm_target_gather_kernel<<<blocks, 256, 0, e->stream>>>(vm.table.as<float4>(), sel_buckets, order, m, inc.tm_rows.as<float4>(), with_cov ? c.cov.as<float4>() : nullptr);
+  }
+  HIP_OR_FAIL(e, hipGetLastError());
+  // into the cloud as fvh_*_set_target_cloud_device takes a float4 array: the same pack kernel, the same bounding cube for the sort
+  { const int rc = upload_cloud(e, c, inc.tm_rows.as<float>(), m, 4, true, want_box); if (rc) return rc; }
+  c.has_cov = with_cov;
+  return FVH_OK;
+}

@@ -611,8 +611,11 @@ int fetch_voxelmap_host(Engine* e, VoxelMapDev& vm, const Rebuild* rebuild_safe 
   vm.num_skipped = counters[2];
   vm.h_occupied.resize(counters[0]);
   vm.h_table.resize((size_t)vm.capacity * 4);
-  if (counters[0]) HIP_OR_FAIL(e, hipMemcpyAsync(vm.h_occupied.data(), vm.occupied.p, sizeof(int) * counters[0], hipMemcpyDeviceToHost, e->stream));
-  HIP_OR_FAIL(e, hipMemcpyAsync(vm.h_table.data(), vm.table.p, (size_t)vm.capacity * 64, hipMemcpyDeviceToHost, e->stream));
+  {
+    ProfScope ps(e, "map_fetch");  // (the table's trip over PCIe: what tools/target_from_map_timing.py holds the device route against)
+    if (counters[0]) HIP_OR_FAIL(e, hipMemcpyAsync(vm.h_occupied.data(), vm.occupied.p, sizeof(int) * counters[0], hipMemcpyDeviceToHost, e->stream));
+    HIP_OR_FAIL(e, hipMemcpyAsync(vm.h_table.data(), vm.table.p, (size_t)vm.capacity * 64, hipMemcpyDeviceToHost, e->stream));
+  }
   HIP_OR_FAIL(e, hipStreamSynchronize(e->stream));
   vm.bucket_to_index.clear();
   for (int i = 0; i < counters[0]; i++) vm.bucket_to_index[vm.h_occupied[i]] = i;

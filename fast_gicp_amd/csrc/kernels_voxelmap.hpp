@@ -845,4 +845,112 @@ __global__ __launch_bounds__(VM_SNAP_THREADS) void vm_export_kernel(const unsign
   }
 }
 
+// ---- the live incremental map as a point target (fvh_vgicp_target_from_map / fvh_ndt_target_from_map: host_incmap.inc.hpp) --------
+// One point per voxel (the record's float mean; VGICP: + the record's covariance), rows in ascending packed-key order, written where a
+// target cloud lives -- so the exact 1-NN search, the fitness score and the FastGICP cost run on the map unchanged. Three steps:
+//   select : the compact list -> (key, bucket) of the voxels with >= min_points points, in whatever order the workgroups arrive (the sort
+//            below makes the rows deterministic: keys are unique), their count and the bounds of their biased coordinates
+//   keys   : the 32-bit words radix_sort_pairs (host_downsample.inc.hpp) sorts by: the key compressed against those bounds when the box
+//            fits 32 bits -- one sweep over exactly the bits the box needs --, else the key's low word, then, re-gathered through the
+//            first sweep's order, its high word (two stable sweeps = one 63-bit sort)
+//   gather : row r <- the record of the r-th bucket in key order
+struct VmTargetCtl { int selected, num_voxels; unsigned umin[3], umax[3]; };
+__global__ void vm_target_begin_kernel(VmTargetCtl* __restrict__ ctl) {
+  if (threadIdx.x < 3) { ctl->umin[threadIdx.x] = 0xFFFFFFFFu; ctl->umax[threadIdx.x] = 0u; }
+  if (threadIdx.x == 0) { ctl->selected = 0; ctl->num_voxels = 0; }
+}
+
+// Workgroups of VM_FIN_THREADS walk the list grid-stride: one counter atomic per 1,024 voxels hands out the output range, and the bounds
+// stay in registers until the end -- six atomics per WORKGROUP, on a grid capped at VM_TARGET_MAX_WGS (same-address atomics retire one
+// after the other at the memory side: vm_finalize_kernel's note). n_bound: what the host sized sel_keys / sel_buckets for.
+constexpr int VM_TARGET_MAX_WGS = 64;
+__global__ __launch_bounds__(VM_FIN_THREADS) void vm_target_select_kernel(const uint4* __restrict__ table, const int* __restrict__ occupied, const int* __restrict__ counters, int n_bound,
+                                                                          int min_points, unsigned long long* __restrict__ sel_keys, unsigned* __restrict__ sel_buckets,
+                                                                          VmTargetCtl* __restrict__ ctl) {
+  __shared__ int s_wave_cnt[VM_FIN_THREADS / 64], s_base;
+  __shared__ unsigned s_min[3], s_max[3];
+  if (threadIdx.x < 3) { s_min[threadIdx.x] = 0xFFFFFFFFu; s_max[threadIdx.x] = 0u; }
+  const int nv = min(counters[0], n_bound);
+  if (blockIdx.x == 0 && threadIdx.x == 0) ctl->num_voxels = counters[0];
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  unsigned mn[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, mx[3] = {0u, 0u, 0u};
+  for (int base = blockIdx.x * VM_FIN_THREADS; base < nv; base += gridDim.x * VM_FIN_THREADS) {  // (uniform per workgroup: the barriers are safe)
+    const int i = base + (int)threadIdx.x;
+    bool pass = false;
+    unsigned b = 0;
+    unsigned long long key = 0;
+    if (i < nv) {
+      b = (unsigned)occupied[i];
+      const uint4 q0 = table[(size_t)b * 4];  // {key_lo, key_hi, num_points, 0}
+      key = (unsigned long long)q0.x | ((unsigned long long)q0.y << 32);
+      pass = (int)q0.z >= min_points;
+    }
+    const unsigned long long mask = __ballot(pass);
+    const int slot_in_wave = __popcll(mask & ((1ull << lane) - 1ull));
+    if (lane == 0) s_wave_cnt[wv] = __popcll(mask);
+    __syncthreads();
+    int total = 0, local = slot_in_wave;
+    for (int w = 0; w < VM_FIN_THREADS / 64; w++) { const int c = s_wave_cnt[w]; total += c; local += (w < wv) ? c : 0; }
+    if (threadIdx.x == 0) s_base = total ? atomicAdd(&ctl->selected, total) : 0;
+    __syncthreads();
+    if (pass) {
+      const int r = s_base + local;  // (< nv <= n_bound: every selected voxel takes one slot)
+      sel_keys[r] = key;
+      sel_buckets[r] = b;
+      const unsigned c[3] = {(unsigned)(key & 0x1FFFFF), (unsigned)((key >> 21) & 0x1FFFFF), (unsigned)((key >> 42) & 0x1FFFFF)};
+#pragma unroll
+      for (int a = 0; a < 3; a++) { mn[a] = min(mn[a], c[a]); mx[a] = max(mx[a], c[a]); }
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    for (int o = 32; o >= 1; o >>= 1) { mn[a] = min(mn[a], (unsigned)__shfl_xor((int)mn[a], o)); mx[a] = max(mx[a], (unsigned)__shfl_xor((int)mx[a], o)); }
+  }
+  __syncthreads();  // (s_min / s_max initialised: a workgroup with no chunk never met a barrier above)
+  if (lane == 0) {
+#pragma unroll
+    for (int a = 0; a < 3; a++) { atomicMin(&s_min[a], mn[a]); atomicMax(&s_max[a], mx[a]); }
+  }
+  __syncthreads();
+  if (threadIdx.x < 3 && s_min[threadIdx.x] != 0xFFFFFFFFu) { atomicMin(&ctl->umin[threadIdx.x], s_min[threadIdx.x]); atomicMax(&ctl->umax[threadIdx.x], s_max[threadIdx.x]); }
+}
+
+// part 0: the key compressed against the box of the selected voxels, z-major like pack_key: (z - lo_z) << bxy | (y - lo_y) << bx | (x - lo_x)
+// part 1: the key's low word; part 2: its high word. idx_in null: the identity (rows of the select pass); part 2 runs in place over the
+// first sweep's result (idx_out == idx_in: every thread rewrites the element it read).
+struct VmTargetKey { unsigned lo[3]; int bx, bxy, part; };
+__global__ __launch_bounds__(256) void vm_target_keys_kernel(const unsigned long long* __restrict__ sel_keys, const int* idx_in, int m, VmTargetKey kp, unsigned* __restrict__ keys_out,
+                                                             int* idx_out) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= m) return;
+  const int src = idx_in ? idx_in[r] : r;
+  const unsigned long long k = sel_keys[src];
+  unsigned v;
+  if (kp.part == 0) {
+    const unsigned long long dx = (unsigned)(k & 0x1FFFFF) - kp.lo[0], dy = (unsigned)((k >> 21) & 0x1FFFFF) - kp.lo[1], dz = (unsigned)((k >> 42) & 0x1FFFFF) - kp.lo[2];
+    v = (unsigned)(dx | (dy << kp.bx) | (dz << kp.bxy));  // (64-bit shifts: bxy may be 32 when the box is one voxel thick in z -- dz is 0 then)
+  } else {
+    v = kp.part == 1 ? (unsigned)k : (unsigned)(k >> 32);
+  }
+  keys_out[r] = v;
+  idx_out[r] = src;
+}
+
+// Row r <- the record of bucket sel_buckets[order[r]]: the point {mean, 0} as pack_points_kernel writes one, the covariance in the cloud's
+// layout {xx, xy, xz, yy | yz, zz, 0, 0} -- the record's q2 and q3.xy (q3.zw of a record is the weight sqrt(n), not covariance). Moves only:
+// every float arrives bit for bit. out_cov null: points only (NDT handles).
+__global__ __launch_bounds__(256) void vm_target_gather_kernel(const float4* __restrict__ table, const unsigned* __restrict__ sel_buckets, const int* __restrict__ order, int m,
+                                                               float4* __restrict__ out_pts, float4* __restrict__ out_cov) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= m) return;
+  const size_t b = sel_buckets[order[r]];
+  const float4 q1 = table[b * 4 + 1];
+  out_pts[r] = make_float4(q1.x, q1.y, q1.z, 0.f);
+  if (out_cov) {
+    const float4 q3 = table[b * 4 + 3];
+    out_cov[2 * (size_t)r] = table[b * 4 + 2];
+    out_cov[2 * (size_t)r + 1] = make_float4(q3.x, q3.y, 0.f, 0.f);
+  }
+}
+
 }  // namespace fvh

@@ -205,6 +205,9 @@ static void def_incremental_target(PyClass& c) {
         if (c.size() != 3) throw std::invalid_argument("prune_target: center must have 3 elements");
         return v.pruneTarget(c.data(), radius, max_age);
       }, py::arg("center") = py::none(), py::arg("radius") = 0.0, py::arg("max_age") = 0)
+      // the map as the handle's target cloud too (one point per voxel with >= min_points points; a snapshot): get_fitness_score() and
+      // align_best() then work in this mode. -> number of points
+      .def("target_cloud_from_map", [](Reg& v, int min_points) { return v.targetCloudFromMap(min_points); }, py::arg("min_points") = 1)
       // snapshots of the incremental target: save / restore / merge (fvh_*_voxelmap_export / _import / _merge_from). The dict is
       // {resolution, mode, num_inserts, num_points, num_voxels, coords (n, 3) int32, sums (n, 10) float64, ages (n,) uint32}
       .def("export_target_map", [](Reg& v) {

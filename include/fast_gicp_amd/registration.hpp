@@ -626,6 +626,7 @@ struct MapCalls<fvh_vgicp> {
   static int export_rows(fvh_vgicp* h, int* n, double* res, int* mode, int* inserts, long long* points, int* coords, double* sums, unsigned* ages) { return fvh_vgicp_voxelmap_export(h, n, res, mode, inserts, points, coords, sums, ages); }
   static int import_rows(fvh_vgicp* h, int n, const int* coords, const double* sums, const unsigned* ages, double res, int mode, int inserts, long long points) { return fvh_vgicp_voxelmap_import(h, n, coords, sums, ages, res, mode, inserts, points); }
   static int merge_from(fvh_vgicp* h, fvh_vgicp* other) { return fvh_vgicp_voxelmap_merge_from(h, other); }
+  static int target_from_map(fvh_vgicp* h, int min_points, int* num_points) { return fvh_vgicp_target_from_map(h, min_points, num_points); }
 };
 template <>
 struct MapCalls<fvh_ndt> {
@@ -635,6 +636,7 @@ struct MapCalls<fvh_ndt> {
   static int export_rows(fvh_ndt* h, int* n, double* res, int* mode, int* inserts, long long* points, int* coords, double* sums, unsigned* ages) { return fvh_ndt_voxelmap_export(h, n, res, mode, inserts, points, coords, sums, ages); }
   static int import_rows(fvh_ndt* h, int n, const int* coords, const double* sums, const unsigned* ages, double res, int mode, int inserts, long long points) { return fvh_ndt_voxelmap_import(h, n, coords, sums, ages, res, mode, inserts, points); }
   static int merge_from(fvh_ndt* h, fvh_ndt* other) { return fvh_ndt_voxelmap_merge_from(h, other); }
+  static int target_from_map(fvh_ndt* h, int min_points, int* num_points) { return fvh_ndt_target_from_map(h, min_points, num_points); }
 };
 }  // namespace detail
 
@@ -718,6 +720,14 @@ protected:
     return removed;
   }
   bool hasIncrementalTarget() const { return incremental_target_; }
+  /// The live map becomes the handle's target CLOUD as well: one point per voxel with >= min_points points (the voxel's mean; VGICP: + its
+  /// covariance), rows in ascending key order -- the row order of exportTargetMap(). getFitnessScore() and alignBest() then work on the map.
+  /// A snapshot: call it again after an insert or a prune. The map stays the align target. Returns the number of points.
+  int targetCloudFromMap(int min_points = 1) {
+    int n = 0;
+    call(Map::target_from_map(core_, min_points, &n), "target_from_map");
+    return n;
+  }
   TargetMapSnapshot exportTargetMap() {
     TargetMapSnapshot m;
     int n = 0;
@@ -946,12 +956,14 @@ public:
   //     beginIncrementalTarget(); setInputSource(scan 0); insertSourceIntoTarget(Identity);
   //     per scan: setInputSource(scan); align(out, guess); insertSourceIntoTarget(); pruneTarget(position, radius);
   // The map has no host cloud behind it: getInputTarget() is null, align() does not ask for one, swapSourceAndTarget() throws
-  // (FVH_ERR_BAD_STATE) and getFitnessScore() needs a target cloud as before. setInputTarget() ends the mode.
+  // (FVH_ERR_BAD_STATE) and getFitnessScore() needs a target cloud as before: targetCloudFromMap() makes one of the map (one point per
+  // voxel), after which getFitnessScore() and alignBest() work in this mode. setInputTarget() ends the mode.
   // (the calls themselves: DeviceRegistration, shared with NDTCuda; the source is added with its points + covariances as setInputSource left them)
   using Base::beginIncrementalTarget;
   using Base::insertSourceIntoTarget;
   using Base::pruneTarget;
   using Base::hasIncrementalTarget;
+  using Base::targetCloudFromMap;
 
   // ---- snapshots of the incremental target map (C ABI: fvh_vgicp_voxelmap_export / _import / _merge_from): save, restore, merge.
   // Restore = loadTargetMap(path) on a fresh object, or beginIncrementalTarget() + importTargetMap(). Import and merge ADD: sums and
@@ -1204,11 +1216,13 @@ public:
   //     per scan: setInputSource(scan); align(out, guess); insertSourceIntoTarget(); pruneTarget(position, radius);
   // The voxels are sums of the inserted POINTS (sum p, sum p p^T): the map is the one setInputTarget(all inserted points) would give. It has no
   // host cloud behind it: getInputTarget() is null, align() does not ask for one, swapSourceAndTarget() throws (FVH_ERR_BAD_STATE) and
-  // getFitnessScore() needs a target cloud as before. setInputTarget() ends the mode. Snapshots carry mode 3 (FVH_VOXEL_NDT_SUMS).
+  // getFitnessScore() needs a target cloud as before: targetCloudFromMap() makes one of the map (one point per voxel), after which
+  // getFitnessScore() and alignBest() work in this mode. setInputTarget() ends the mode. Snapshots carry mode 3 (FVH_VOXEL_NDT_SUMS).
   using Base::beginIncrementalTarget;
   using Base::insertSourceIntoTarget;
   using Base::pruneTarget;
   using Base::hasIncrementalTarget;
+  using Base::targetCloudFromMap;
   using Base::exportTargetMap;
   using Base::importTargetMap;
   void mergeTargetFrom(NDTCuda& other) { this->merge_target_from(other); }

@@ -264,7 +264,7 @@ int fvh_vgicp_adopt_prepared_source(fvh_vgicp* h);
  * FVH_ERR_BAD_STATE (every rank would grow a private map: end the mode first);
  * fvh_vgicp_swap_source_and_target / _gicp_swap_source_and_target are FVH_ERR_BAD_STATE (there is no cloud behind the map to become a
  * source); a change of the resolution or between additive and multiplicative voxels is FVH_ERR_BAD_STATE (call map_begin again);
- * fvh_vgicp_set_target_cloud* leaves the map alone (fvh_vgicp_fitness_score still needs a target cloud). With no incremental map live
+ * fvh_vgicp_set_target_cloud* leaves the map alone (fvh_vgicp_fitness_score still needs a target cloud: fvh_vgicp_target_from_map below makes one of the map). With no incremental map live
  * all of those behave as before.
  * Refused by map_begin / map_insert_* / map_prune, the handle stays usable: multi-GPU handles (communicator, peers or tile attached) and
  * fvh_vgicp_set_target_map_sharding (FVH_ERR_UNSUPPORTED); FVH_COMPUTE_CUDA_COMPAT (FVH_ERR_UNSUPPORTED: its voxel sums are float sums in point order, which an in-place map
@@ -297,6 +297,28 @@ int fvh_vgicp_map_get_info(fvh_vgicp* h, int* incremental, int* num_voxels, int*
 int fvh_vgicp_voxelmap_export(fvh_vgicp* h, int* num_voxels, double* resolution, int* mode, int* num_inserts, long long* num_points, int* coords3, double* sums10, unsigned* ages);
 int fvh_vgicp_voxelmap_import(fvh_vgicp* h, int n, const int* coords3, const double* sums10, const unsigned* ages, double resolution, int mode, int num_inserts, long long num_points);
 int fvh_vgicp_voxelmap_merge_from(fvh_vgicp* h, fvh_vgicp* other);
+/* new: the live incremental map as the handle's TARGET CLOUD -- what fvh_vgicp_fitness_score, fvh_vgicp_gicp_* (FastGICP), find_target_neighbors
+ * and debug_get_spatial_order(which = 1) need and a map does not have. Made on the device (select, radix sort by key, gather), nothing
+ * crosses PCIe but one 32-byte readback.
+ *   target_from_map    the target cloud becomes ONE POINT PER VOXEL of the live map that holds at least min_points points (<= 1: every
+ *                      voxel): the point is the voxel's float mean, bit for bit what fvh_vgicp_get_voxel_means returns, and its covariance
+ *                      -- stored as the target covariances: fvh_vgicp_get_target_covariances returns it -- the voxel's record covariance,
+ *                      bit for bit what fvh_vgicp_get_voxel_covs returns. Rows come in ascending packed-key order (z-major, then y, then x:
+ *                      the row order of fvh_vgicp_voxelmap_export; with min_points <= 1 index i IS row i of an export), so two handles that
+ *                      hold equal maps hold bit-identical target clouds and the target indices of fvh_vgicp_gicp_get_correspondences mean
+ *                      the same on both. *num_points_out (may be NULL) receives the number of points; the call reads that count back either
+ *                      way (the size of a cloud is host state): one readback, one stream synchronisation. If no voxel qualifies the
+ *                      count is 0 and the handle has NO target cloud (fitness_score: FVH_ERR_BAD_STATE, as without one).
+ *   get_target_points  packed xyz (fvh_vgicp_get_num_target_points rows) of the current target cloud in its ORIGINAL order, however it was
+ *                      set; FVH_ERR_BAD_STATE without one.
+ * A SNAPSHOT: a later insert, prune, import or merge leaves the target cloud as it was; call target_from_map again to refresh it. The map
+ * is only read and stays live: align, update_correspondences, compute_error after the call run on the map and give the bits they gave
+ * before; stored voxel correspondences are kept (stored nearest-point ones index the old cloud and are dropped). Whatever the target
+ * cloud held before is replaced as by fvh_vgicp_set_target_cloud: points, covariances, neighbour lists, Morton order and tiles.
+ * Refusals (the handle and its target cloud stay as they were): no live incremental map, an align_async in flight (FVH_ERR_BAD_STATE).
+ * Legal between prepare_source* and adopt_prepared_source: the call uses scratch of its own, not the preparation's. */
+int fvh_vgicp_target_from_map(fvh_vgicp* h, int min_points, int* num_points_out);
+int fvh_vgicp_get_target_points(fvh_vgicp* h, float* xyz3);
 /* setDebugPrint(true) on the device LM: with the trace on, an align records one row per trial step -- {inner iteration i, y0,
  * yi, rho, lambda, |d|}, the columns LsqRegistration prints (lsq_registration_impl.hpp:143-149) -- fetched afterwards
  * (rows6 may be NULL to query the count). */
@@ -487,6 +509,15 @@ int fvh_ndt_map_get_info(fvh_ndt* h, int* incremental, int* num_voxels, int* cap
 int fvh_ndt_voxelmap_export(fvh_ndt* h, int* num_voxels, double* resolution, int* mode, int* num_inserts, long long* num_points, int* coords3, double* sums10, unsigned* ages);
 int fvh_ndt_voxelmap_import(fvh_ndt* h, int n, const int* coords3, const double* sums10, const unsigned* ages, double resolution, int mode, int num_inserts, long long num_points);
 int fvh_ndt_voxelmap_merge_from(fvh_ndt* h, fvh_ndt* other);
+/* new: the live incremental NDT map as the handle's target cloud, as fvh_vgicp_target_from_map / _get_target_points above: one point per
+ * voxel with >= min_points points (the float mean fvh_ndt_get_voxels(h, 1, ...) returns, bit for bit), rows in ascending packed-key order,
+ * a snapshot. POINTS ONLY (an NDT handle keeps no target covariances). The map stays the target map and stays live: the call does NOT mark
+ * the cloud as newer than the map -- that is fvh_ndt_set_target_cloud*'s rule; a cloud such a call left behind is replaced, so nothing is
+ * newer afterwards -- and fvh_ndt_align after it runs on the incremental map, bit for bit as before; stored correspondences are kept.
+ * FVH_ERR_BAD_STATE without a live incremental map or with an align_async in flight. */
+int fvh_ndt_target_from_map(fvh_ndt* h, int min_points, int* num_points_out);
+int fvh_ndt_get_num_target_points(const fvh_ndt* h, int* n); /* rows of fvh_ndt_get_target_points: 0 without a target cloud */
+int fvh_ndt_get_target_points(fvh_ndt* h, float* xyz3);
 /* new (round 6): the output of the filter's last ApproximateVoxelGrid call becomes the cloud WITHOUT a copy -- the filter's emit kernel wrote it as
  * float4 too, and that buffer is swapped with the cloud's (what fvh_voxelgrid_device_points + fvh_ndt_set_source_cloud_device /
  * _prepare_source_device do, minus the widening kernel and its launch: 8 of a LiDAR frame's 141 us). An output can be taken once; the filter's
