@@ -74,6 +74,12 @@ def load():
             fn.restype = C.c_int
         L.fvh_debug_lm_replay.argtypes = LM_REPLAY_ARGTYPES
         L.fvh_debug_lm_replay.restype = C.c_int
+        for name, argtypes in OUTLIER_ARGTYPES.items():  # (doubles in the middle of the list: a bare Python float would not convert)
+            fn = getattr(L, name, None)
+            if fn is None:  # FVH_LIB_PATH names an older build of the ABI (A/B runs): calling the method then raises AttributeError
+                continue
+            fn.argtypes = argtypes
+            fn.restype = C.c_int
         _LIB = L
     return _LIB
 
@@ -81,6 +87,24 @@ def load():
 # fvh_{vgicp,ndt}_align_multi(handle, k, guesses16, params, results, grid_blocks_out)
 ALIGN_MULTI_ARGTYPES = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 MAX_MULTI = 64  # hypotheses per align_multi call
+
+
+def _outlier_argtypes():
+    """fvh_voxelgrid_{crop_range, remove_statistical_outliers, remove_radius_outliers}[_strided|_device] + the getters, as the header declares them"""
+    h, p, i, d = C.c_void_p, C.c_void_p, C.c_int, C.c_double
+    params = {"crop_range": [d, d], "remove_statistical_outliers": [i, d], "remove_radius_outliers": [d, i]}
+    out = {}
+    for base, tail in params.items():
+        out["fvh_voxelgrid_" + base] = [h, p, i] + tail + [p]
+        out["fvh_voxelgrid_" + base + "_strided"] = [h, p, i, i] + tail + [p]
+        out["fvh_voxelgrid_" + base + "_device"] = [h, p, i, i] + tail + [p]
+    out["fvh_voxelgrid_get_kept_indices"] = [h, p]
+    out["fvh_voxelgrid_get_scores"] = [h, p, p]
+    out["fvh_voxelgrid_profile_get_class"] = [h, C.c_char_p, p, p]
+    return out
+
+
+OUTLIER_ARGTYPES = _outlier_argtypes()
 
 
 def declared_symbols():
@@ -754,6 +778,7 @@ class VoxelGrid:
     def __init__(self, device=0):
         self._lib = load()
         self._h = C.c_void_p()
+        self._n_in = 0  # input size of the last crop / outlier call (scores())
         rc = self._lib.fvh_voxelgrid_create(int(device), C.byref(self._h))
         if rc != 0:
             raise FvhError("fvh_voxelgrid_create failed: %d" % rc)
@@ -835,10 +860,78 @@ class VoxelGrid:
     def profile_reset(self):
         self._check(self._lib.fvh_voxelgrid_profile_reset(self._h), "profile_reset")
 
-    def profile_get(self):
+    def profile_get(self, cls="downsample"):
+        """(total ms, launches) of one profile class of the filter's engine: "downsample", "sort", "knn", "outlier_count", "outlier_score", "compact" """
         ms, n = C.c_double(0), C.c_int(0)
-        self._check(self._lib.fvh_voxelgrid_profile_get(self._h, C.byref(ms), C.byref(n)), "profile_get")
+        if cls == "downsample":
+            self._check(self._lib.fvh_voxelgrid_profile_get(self._h, C.byref(ms), C.byref(n)), "profile_get")
+        else:
+            self._check(self._lib.fvh_voxelgrid_profile_get_class(self._h, cls.encode(), C.byref(ms), C.byref(n)), "profile_get_class")
         return ms.value, n.value
+
+    # ---- range crop / outlier removal (fvh_voxelgrid_crop_range, _remove_statistical_outliers, _remove_radius_outliers): the kept points in
+    # input order, bit copies of the input; kept_indices() / scores() describe the last of these calls ----
+    def _outlier_host(self, name, xyz, stride, *params):
+        a = _f32(np.asarray(xyz).reshape(-1, stride))
+        n = C.c_int(0)
+        self._n_in = len(a)
+        if stride == 3:
+            rc = getattr(self._lib, "fvh_voxelgrid_" + name)(self._h, _p(a), len(a), *params, C.byref(n))
+        else:
+            rc = getattr(self._lib, "fvh_voxelgrid_" + name + "_strided")(self._h, _p(a), len(a), int(stride), *params, C.byref(n))
+        self._check(rc, "fvh_voxelgrid_" + name)
+        return self.get_points(n.value)
+
+    def _outlier_device(self, name, d_ptr, n, stride, *params):
+        m = C.c_int(0)
+        self._n_in = int(n)
+        self._check(getattr(self._lib, "fvh_voxelgrid_" + name + "_device")(self._h, C.c_void_p(d_ptr), int(n), int(stride), *params, C.byref(m)), "fvh_voxelgrid_" + name + "_device")
+        ptr = C.c_void_p()
+        self._check(self._lib.fvh_voxelgrid_device_points(self._h, C.byref(ptr), C.byref(m)), "fvh_voxelgrid_device_points")
+        return ptr.value or 0, m.value
+
+    def crop_range(self, xyz, min_sq_norm=1e-3, max_sq_norm=float("inf"), stride=3):
+        """Keep the finite points with min_sq_norm <= |p|^2 (fp32) <= max_sq_norm; (m, 3) float32. The defaults are the reference's origin filter."""
+        return self._outlier_host("crop_range", xyz, stride, float(min_sq_norm), float(max_sq_norm))
+
+    def crop_range_device(self, d_ptr, n, min_sq_norm=1e-3, max_sq_norm=float("inf"), stride=3):
+        """Device pointer in; (device pointer to packed xyz, count) as filter_device returns them."""
+        return self._outlier_device("crop_range", d_ptr, n, stride, float(min_sq_norm), float(max_sq_norm))
+
+    def remove_statistical_outliers(self, xyz, mean_k=20, stddev_mul=1.0, stride=3):
+        """Keep the points whose mean distance to their mean_k nearest neighbours is at most mean + stddev_mul * stddev of that quantity."""
+        return self._outlier_host("remove_statistical_outliers", xyz, stride, int(mean_k), float(stddev_mul))
+
+    def remove_statistical_outliers_device(self, d_ptr, n, mean_k=20, stddev_mul=1.0, stride=3):
+        return self._outlier_device("remove_statistical_outliers", d_ptr, n, stride, int(mean_k), float(stddev_mul))
+
+    def remove_radius_outliers(self, xyz, radius=0.8, min_neighbors=2, stride=3):
+        """Keep the points with at least min_neighbors other points within `radius`."""
+        return self._outlier_host("remove_radius_outliers", xyz, stride, float(radius), int(min_neighbors))
+
+    def remove_radius_outliers_device(self, d_ptr, n, radius=0.8, min_neighbors=2, stride=3):
+        """The pointer may be this handle's own device_points(): stages chain on one handle."""
+        return self._outlier_device("remove_radius_outliers", d_ptr, n, stride, float(radius), int(min_neighbors))
+
+    def device_points(self):
+        """(device pointer to the packed xyz of the last output, count)"""
+        ptr, m = C.c_void_p(), C.c_int(0)
+        self._check(self._lib.fvh_voxelgrid_device_points(self._h, C.byref(ptr), C.byref(m)), "fvh_voxelgrid_device_points")
+        return ptr.value or 0, m.value
+
+    def kept_indices(self):
+        """Ascending indices into the input of the points the last crop / outlier call kept (int32)."""
+        _, m = self.device_points()
+        idx = np.empty(m, np.int32)
+        self._check(self._lib.fvh_voxelgrid_get_kept_indices(self._h, _p(idx)), "fvh_voxelgrid_get_kept_indices")
+        return idx
+
+    def scores(self):
+        """(float32[n_in] score per INPUT point of the last crop / outlier call, the threshold it was held against)"""
+        s = np.empty(self._n_in, np.float32)
+        t = C.c_double(0)
+        self._check(self._lib.fvh_voxelgrid_get_scores(self._h, _p(s), C.byref(t)), "fvh_voxelgrid_get_scores")
+        return s, t.value
 
 
 class NDTCore(_Core):

@@ -25,6 +25,7 @@
 #include "kernels_cost.hpp"
 #include "kernels_cov.hpp"
 #include "kernels_downsample.hpp"
+#include "kernels_outlier.hpp"
 #include "kernels_peer.hpp"
 #include "kernels_sort.hpp"
 #include "kernels_voxelmap.hpp"
@@ -443,6 +444,7 @@ inline void pose_to_rowmajor12f(const double* T16, float* T12) {  // what the se
 #include "host_incmap.inc.hpp"
 #include "host_gicp.inc.hpp"
 #include "host_downsample.inc.hpp"
+#include "host_outlier.inc.hpp"
 
 }  // namespace
 
@@ -588,6 +590,7 @@ struct fvh_ndt {
 struct fvh_voxelgrid {
   Engine e;
   DownsampleDev d;
+  OutlierDev o;  // side outputs of crop_range / remove_*_outliers (host_outlier.inc.hpp)
   bool in_flight() const { return false; }  // (a filter has no pipeline: CHECK_HANDLE never refuses on it)
   static constexpr const char* align_wait_fn = "";
 };
@@ -1764,6 +1767,7 @@ int fvh_voxelgrid_destroy(fvh_voxelgrid* h) {
   (void)hipSetDevice(h->e.device);
   if (h->e.stream) (void)hipStreamSynchronize(h->e.stream);
   h->d.release();
+  h->o.release();
   h->e.shutdown();
   delete h;
   return FVH_OK;
@@ -1785,9 +1789,9 @@ struct FilterStream {
   }
   ~FilterStream() { e->stream = saved; }
 };
-int fvh_voxelgrid_filter(fvh_voxelgrid* h, int method, const float* xyz, int n, float leaf, int* out_n) { CHECK_HANDLE(h); FilterStream fs(&h->e); if (fs.rc) return fs.rc; return downsample(&h->e, h->d, method, xyz, n, 3, false, leaf, out_n); }
-int fvh_voxelgrid_filter_strided(fvh_voxelgrid* h, int method, const float* xyz, int n, int stride, float leaf, int* out_n) { CHECK_HANDLE(h); FilterStream fs(&h->e); if (fs.rc) return fs.rc; return downsample(&h->e, h->d, method, xyz, n, stride, false, leaf, out_n); }
-int fvh_voxelgrid_filter_device(fvh_voxelgrid* h, int method, const float* d_xyz, int n, int stride, float leaf, int* out_n) { CHECK_HANDLE(h); FilterStream fs(&h->e); if (fs.rc) return fs.rc; return downsample(&h->e, h->d, method, d_xyz, n, stride, true, leaf, out_n); }
+int fvh_voxelgrid_filter(fvh_voxelgrid* h, int method, const float* xyz, int n, float leaf, int* out_n) { CHECK_HANDLE(h); h->o.valid = false; FilterStream fs(&h->e); if (fs.rc) return fs.rc; return downsample(&h->e, h->d, method, xyz, n, 3, false, leaf, out_n); }
+int fvh_voxelgrid_filter_strided(fvh_voxelgrid* h, int method, const float* xyz, int n, int stride, float leaf, int* out_n) { CHECK_HANDLE(h); h->o.valid = false; FilterStream fs(&h->e); if (fs.rc) return fs.rc; return downsample(&h->e, h->d, method, xyz, n, stride, false, leaf, out_n); }
+int fvh_voxelgrid_filter_device(fvh_voxelgrid* h, int method, const float* d_xyz, int n, int stride, float leaf, int* out_n) { CHECK_HANDLE(h); h->o.valid = false; FilterStream fs(&h->e); if (fs.rc) return fs.rc; return downsample(&h->e, h->d, method, d_xyz, n, stride, true, leaf, out_n); }
 // Extension for a device-resident pipeline (no PCL counterpart): the filter runs on the registration handle's stream, so what it
 // writes is ordered before whatever that handle queues next, and the _async call returns as soon as the COUNT is known (it comes
 // from the scan kernel, one kernel before the centroids exist): set_*_cloud_device + align are queued behind the emit kernel
@@ -1809,6 +1813,7 @@ int fvh_voxelgrid_share_prepare_stream_with_ndt(fvh_voxelgrid* h, fvh_ndt* other
 int fvh_voxelgrid_share_prepare_stream_with_vgicp(fvh_voxelgrid* h, fvh_vgicp* other) { CHECK_HANDLE(h); return share_stream(&h->e, other ? &other->e : nullptr, true); }
 int fvh_voxelgrid_filter_device_async(fvh_voxelgrid* h, int method, const float* d_xyz, int n, int stride, float leaf, int* out_n) {
   CHECK_HANDLE(h);
+  h->o.valid = false;
   const bool shared = h->e.stream != h->e.owned_stream;
   FilterStream fs(&h->e); if (fs.rc) return fs.rc;
   return downsample(&h->e, h->d, method, d_xyz, n, stride, true, leaf, out_n, /*early=*/shared);
@@ -1832,5 +1837,22 @@ int fvh_voxelgrid_device_points(fvh_voxelgrid* h, const float** d_xyz, int* n) {
 int fvh_voxelgrid_profile_enable(fvh_voxelgrid* h, int on) { CHECK_HANDLE(h); h->e.prof.on = on != 0; h->e.prof.cost_only = on == 2; return FVH_OK; }
 int fvh_voxelgrid_profile_reset(fvh_voxelgrid* h) { CHECK_HANDLE(h); HIP_OR_FAIL(&h->e, hipStreamSynchronize(h->e.stream)); h->e.prof.reset(); return FVH_OK; }
 int fvh_voxelgrid_profile_get(fvh_voxelgrid* h, double* ms, int* n) { CHECK_HANDLE(h); return profile_get(&h->e, "downsample", ms, n); }
+
+// ---- range crop / outlier removal on the filter handle (host_outlier.inc.hpp, kernels_outlier.hpp) ----
+#define FVH_OUTLIER_CALL(kind, xyz, stride, on_device, p0, p1, k) \
+  CHECK_HANDLE(h); FilterStream fs(&h->e); if (fs.rc) return fs.rc; return outlier_filter(&h->e, h->d, h->o, kind, xyz, n, stride, on_device, p0, p1, k, out_n)
+int fvh_voxelgrid_crop_range(fvh_voxelgrid* h, const float* xyz, int n, double min_sq_norm, double max_sq_norm, int* out_n) { FVH_OUTLIER_CALL(OUTLIER_CROP, xyz, 3, false, min_sq_norm, max_sq_norm, 0); }
+int fvh_voxelgrid_crop_range_strided(fvh_voxelgrid* h, const float* xyz, int n, int stride, double min_sq_norm, double max_sq_norm, int* out_n) { FVH_OUTLIER_CALL(OUTLIER_CROP, xyz, stride, false, min_sq_norm, max_sq_norm, 0); }
+int fvh_voxelgrid_crop_range_device(fvh_voxelgrid* h, const float* d_xyz, int n, int stride, double min_sq_norm, double max_sq_norm, int* out_n) { FVH_OUTLIER_CALL(OUTLIER_CROP, d_xyz, stride, true, min_sq_norm, max_sq_norm, 0); }
+int fvh_voxelgrid_remove_statistical_outliers(fvh_voxelgrid* h, const float* xyz, int n, int mean_k, double stddev_mul, int* out_n) { FVH_OUTLIER_CALL(OUTLIER_STATISTICAL, xyz, 3, false, stddev_mul, 0.0, mean_k); }
+int fvh_voxelgrid_remove_statistical_outliers_strided(fvh_voxelgrid* h, const float* xyz, int n, int stride, int mean_k, double stddev_mul, int* out_n) { FVH_OUTLIER_CALL(OUTLIER_STATISTICAL, xyz, stride, false, stddev_mul, 0.0, mean_k); }
+int fvh_voxelgrid_remove_statistical_outliers_device(fvh_voxelgrid* h, const float* d_xyz, int n, int stride, int mean_k, double stddev_mul, int* out_n) { FVH_OUTLIER_CALL(OUTLIER_STATISTICAL, d_xyz, stride, true, stddev_mul, 0.0, mean_k); }
+int fvh_voxelgrid_remove_radius_outliers(fvh_voxelgrid* h, const float* xyz, int n, double radius, int min_neighbors, int* out_n) { FVH_OUTLIER_CALL(OUTLIER_RADIUS, xyz, 3, false, radius, 0.0, min_neighbors); }
+int fvh_voxelgrid_remove_radius_outliers_strided(fvh_voxelgrid* h, const float* xyz, int n, int stride, double radius, int min_neighbors, int* out_n) { FVH_OUTLIER_CALL(OUTLIER_RADIUS, xyz, stride, false, radius, 0.0, min_neighbors); }
+int fvh_voxelgrid_remove_radius_outliers_device(fvh_voxelgrid* h, const float* d_xyz, int n, int stride, double radius, int min_neighbors, int* out_n) { FVH_OUTLIER_CALL(OUTLIER_RADIUS, d_xyz, stride, true, radius, 0.0, min_neighbors); }
+#undef FVH_OUTLIER_CALL
+int fvh_voxelgrid_get_kept_indices(fvh_voxelgrid* h, int* idx) { CHECK_HANDLE(h); return outlier_get_kept(&h->e, h->d, h->o, idx); }
+int fvh_voxelgrid_get_scores(fvh_voxelgrid* h, float* scores, double* threshold) { CHECK_HANDLE(h); return outlier_get_scores(&h->e, h->o, scores, threshold); }
+int fvh_voxelgrid_profile_get_class(fvh_voxelgrid* h, const char* kernel_class, double* total_ms, int* launches) { CHECK_HANDLE(h); return profile_get(&h->e, kernel_class, total_ms, launches); }
 
 }  // extern "C"

@@ -123,6 +123,50 @@ static py::array_t<double> downsample_device(const Points& points, double resolu
   return res;
 }
 
+// The kept points of a filter call as an (m, 3) float64 array (fvh_voxelgrid_get_points), optionally with their indices into the input
+static py::object filtered_result(fvh_voxelgrid* vg, int rc, int n, bool return_indices, const char* what) {
+  std::vector<float> out((size_t)3 * n);
+  std::vector<int> idx(return_indices ? (size_t)n : 0);
+  if (!rc) rc = fvh_voxelgrid_get_points(vg, out.data());
+  if (!rc && return_indices) rc = fvh_voxelgrid_get_kept_indices(vg, idx.data());
+  const std::string err = rc ? fvh_voxelgrid_last_error(vg) : "";
+  fvh_voxelgrid_destroy(vg);
+  detail::check(rc, what, err.c_str());
+  py::array_t<double> res({(py::ssize_t)n, (py::ssize_t)3});
+  auto w = res.mutable_unchecked<2>();
+  for (int i = 0; i < n; i++) for (int a = 0; a < 3; a++) w(i, a) = out[3 * (size_t)i + a];
+  if (!return_indices) return std::move(res);
+  py::array_t<int> ids((py::ssize_t)n);
+  std::copy(idx.begin(), idx.end(), ids.mutable_data());
+  return py::make_tuple(res, ids);
+}
+
+// the origin / range filter of the reference's callers (src/align.cpp:127-133) on the device: fvh_voxelgrid_crop_range
+static py::object crop_range_device(const Points& points, double min_sq_norm, double max_sq_norm, bool return_indices, int device) {
+  auto cloud = numpy2cloud(points);
+  const std::vector<float> xyz = detail::pack_xyz(*cloud);
+  fvh_voxelgrid* vg = nullptr;
+  detail::check(fvh_voxelgrid_create(device, &vg), "fvh_voxelgrid_create", "cannot create the HIP engine (no GPU? there is no CPU fallback)");
+  int n = 0;
+  const int rc = fvh_voxelgrid_crop_range(vg, xyz.data(), (int)cloud->size(), min_sq_norm, max_sq_norm, &n);
+  return filtered_result(vg, rc, n, return_indices, "fvh_voxelgrid_crop_range");
+}
+
+// statistical / radius outlier removal on the device (fvh_voxelgrid_remove_statistical_outliers / _remove_radius_outliers)
+static py::object remove_outliers_device(const Points& points, const std::string& method, int mean_k, double stddev_mul, double radius, int min_neighbors, bool return_indices,
+                                         int device) {
+  if (method != "STATISTICAL" && method != "RADIUS") throw std::invalid_argument("unknown outlier removal method " + method + " (STATISTICAL, RADIUS)");
+  auto cloud = numpy2cloud(points);
+  const std::vector<float> xyz = detail::pack_xyz(*cloud);
+  fvh_voxelgrid* vg = nullptr;
+  detail::check(fvh_voxelgrid_create(device, &vg), "fvh_voxelgrid_create", "cannot create the HIP engine (no GPU? there is no CPU fallback)");
+  int n = 0;
+  const bool stat = method == "STATISTICAL";
+  const int rc = stat ? fvh_voxelgrid_remove_statistical_outliers(vg, xyz.data(), (int)cloud->size(), mean_k, stddev_mul, &n)
+                      : fvh_voxelgrid_remove_radius_outliers(vg, xyz.data(), (int)cloud->size(), radius, min_neighbors, &n);
+  return filtered_result(vg, rc, n, return_indices, stat ? "fvh_voxelgrid_remove_statistical_outliers" : "fvh_voxelgrid_remove_radius_outliers");
+}
+
 // align_points, main.cpp:64-150. "VGICP" (the CPU FastVGICP in the reference, main.cpp:102-108) runs on the same GPU engine in
 // its fp64 arithmetic WITH k_correspondences honoured (class FastVGICP of registration.hpp; "VGICP_CUDA" ignores it like the
 // reference's FastVGICPCuda: k = 20); "GICP" (nearest-point correspondences, no voxels) runs on the device too.
@@ -251,6 +295,11 @@ PYBIND11_MODULE(pygicp, m) {
   m.def("downsample", &downsample, "downsample points", py::arg("points"), py::arg("downsample_resolution"));
   m.def("downsample_device", &downsample_device, "downsample points on the GPU (bit-identical to downsample; exact=True: pcl::VoxelGrid)", py::arg("points"),
         py::arg("downsample_resolution"), py::arg("exact") = false, py::arg("device") = 0);
+  m.def("crop_range_device", &crop_range_device, "keep the finite points with min_sq_norm <= |p|^2 <= max_sq_norm, on the GPU (the defaults: the origin filter)", py::arg("points"),
+        py::arg("min_sq_norm") = 1e-3, py::arg("max_sq_norm") = std::numeric_limits<double>::infinity(), py::arg("return_indices") = false, py::arg("device") = 0);
+  m.def("remove_outliers_device", &remove_outliers_device, "statistical (mean_k, stddev_mul) or radius (radius, min_neighbors) outlier removal on the GPU; kept points in input order",
+        py::arg("points"), py::arg("method") = "STATISTICAL", py::arg("mean_k") = 20, py::arg("stddev_mul") = 1.0, py::arg("radius") = 0.8, py::arg("min_neighbors") = 2,
+        py::arg("return_indices") = false, py::arg("device") = 0);
   m.def("align_points", &align_points, "align two point sets", py::arg("target"), py::arg("source"), py::arg("method") = "VGICP_CUDA", py::arg("downsample_resolution") = -1.0,
         py::arg("k_correspondences") = 15, py::arg("max_correspondence_distance") = std::numeric_limits<double>::max(), py::arg("voxel_resolution") = 1.0,
         py::arg("num_threads") = 0, py::arg("neighbor_search_method") = "DIRECT1", py::arg("neighbor_search_radius") = 1.5, py::arg("initial_guess") = identity4());

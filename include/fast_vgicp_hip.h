@@ -590,6 +590,47 @@ int fvh_voxelgrid_device_points(fvh_voxelgrid* h, const float** d_xyz, int* n);
 int fvh_voxelgrid_profile_enable(fvh_voxelgrid* h, int on);
 int fvh_voxelgrid_profile_reset(fvh_voxelgrid* h);
 int fvh_voxelgrid_profile_get(fvh_voxelgrid* h, double* total_ms, int* launches);
+int fvh_voxelgrid_profile_get_class(fvh_voxelgrid* h, const char* kernel_class, double* total_ms, int* launches); /* any class of the filter's engine: "downsample", "sort", "knn", "outlier_count", "outlier_score", "compact" */
+
+/* ---- range crop, statistical and radius outlier removal (no counterpart in the reference's cores: the stages a LiDAR front end runs
+ * around the voxel filter -- the origin / range filter of src/align.cpp:127-133, pcl::StatisticalOutlierRemoval,
+ * pcl::RadiusOutlierRemoval -- on the filter handle, so a device-resident loop needs no host pass over the scan) ----
+ * Forms as for fvh_voxelgrid_filter: host xyz, host rows of stride_floats (3 or 4), device pointer. Output: the kept points IN INPUT
+ * ORDER, as bit copies of the input xyz, in the handle's output state -- fvh_voxelgrid_get_points, _device_points and
+ * fvh_ndt_{set_source,set_target,prepare_source}_cloud_from_voxelgrid work on it as on a voxel filter's. Side outputs, kept on the device
+ * until the next call on the handle: the ascending input indices of the kept points (fvh_voxelgrid_get_kept_indices: out_n ints) and one
+ * score per INPUT point with the threshold it was held against (fvh_voxelgrid_get_scores: n floats; either pointer may be NULL). Both
+ * getters answer FVH_ERR_BAD_STATE when the last call on the handle was not one of these filters.
+ * Chaining: the input may be the handle's own fvh_voxelgrid_device_points() pointer (voxel filter -> outlier removal -> registration
+ * on one handle); the input is copied before the output is written. n == 0: out_n = 0, FVH_OK. Argument errors: FVH_ERR_INVALID_ARGUMENT.
+ *
+ * The definitions below are the contract. They follow PCL's published algorithms; PCL's own boundary behaviour (ties at the radius,
+ * its kd-tree's choice among equidistant neighbours, float vs double accumulation) was not available to compare against, and no bit
+ * parity with PCL is claimed. d2(i, j) is fp32 (dx*dx + dy*dy) + dz*dz without contraction: what the exact k-NN of this library ranks by.
+ *  crop_range   s = (x*x + y*y) + z*z in fp32 without contraction; keep iff x, y, z are finite and min_sq_norm <= (double)s <= max_sq_norm
+ *               (max_sq_norm may be +inf). The one stage that DROPS non-finite points silently (pcl::removeNaNFromPointCloud + the
+ *               range test): its output is valid input for every other filter. (1e-3, +inf) is the reference's origin filter.
+ *               Score: s. Threshold reported: max_sq_norm.
+ *  statistical  1 <= mean_k <= 63, n > mean_k, stddev_mul finite. d_i = (float)(sum of (double)sqrtf(d2(i, j)) / mean_k) over the
+ *               mean_k + 1 nearest points of the cloud in (d2, index) order -- the nearest is the point itself or a duplicate, at
+ *               distance 0 (PCL: search mean_k + 1, skip the first). mu = sum d_i / n, var = max(0, (sum d_i^2 - (sum d_i)^2 / n) / (n - 1)),
+ *               t = mu + stddev_mul * sqrt(var) in fp64, summed in a fixed order (two runs give the same bits). Keep iff (double)d_i <= t.
+ *               Score: d_i. Threshold: t.
+ *  radius       radius finite and > 0, min_neighbors >= 1. r2 = (float)radius * (float)radius, at most 1e37. Keep iff
+ *               #{ j != i (by index) : d2(i, j) <= r2 } >= min_neighbors; duplicates of a point count as its neighbours.
+ *               Score: min(count, min_neighbors) as a float (the kernel stops counting once the answer is known). Threshold: min_neighbors.
+ * The two outlier filters refuse a cloud with a non-finite coordinate as the voxel filters do (out_n = 0, FVH_ERR_INVALID_ARGUMENT). */
+int fvh_voxelgrid_crop_range(fvh_voxelgrid* h, const float* xyz, int n, double min_sq_norm, double max_sq_norm, int* out_n);
+int fvh_voxelgrid_crop_range_strided(fvh_voxelgrid* h, const float* xyz, int n, int stride_floats, double min_sq_norm, double max_sq_norm, int* out_n);
+int fvh_voxelgrid_crop_range_device(fvh_voxelgrid* h, const float* d_xyz, int n, int stride_floats, double min_sq_norm, double max_sq_norm, int* out_n);
+int fvh_voxelgrid_remove_statistical_outliers(fvh_voxelgrid* h, const float* xyz, int n, int mean_k, double stddev_mul, int* out_n);
+int fvh_voxelgrid_remove_statistical_outliers_strided(fvh_voxelgrid* h, const float* xyz, int n, int stride_floats, int mean_k, double stddev_mul, int* out_n);
+int fvh_voxelgrid_remove_statistical_outliers_device(fvh_voxelgrid* h, const float* d_xyz, int n, int stride_floats, int mean_k, double stddev_mul, int* out_n);
+int fvh_voxelgrid_remove_radius_outliers(fvh_voxelgrid* h, const float* xyz, int n, double radius, int min_neighbors, int* out_n);
+int fvh_voxelgrid_remove_radius_outliers_strided(fvh_voxelgrid* h, const float* xyz, int n, int stride_floats, double radius, int min_neighbors, int* out_n);
+int fvh_voxelgrid_remove_radius_outliers_device(fvh_voxelgrid* h, const float* d_xyz, int n, int stride_floats, double radius, int min_neighbors, int* out_n);
+int fvh_voxelgrid_get_kept_indices(fvh_voxelgrid* h, int* idx /* out_n ints, host */);
+int fvh_voxelgrid_get_scores(fvh_voxelgrid* h, float* scores /* n floats (the INPUT size), host, may be NULL */, double* threshold /* may be NULL */);
 
 #ifdef __cplusplus
 }
