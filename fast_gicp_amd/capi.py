@@ -74,6 +74,10 @@ def load():
             fn.restype = C.c_int
         L.fvh_debug_lm_replay.argtypes = LM_REPLAY_ARGTYPES
         L.fvh_debug_lm_replay.restype = C.c_int
+        fn = getattr(L, "fvh_debug_regularize", None)  # (absent from an older build of the ABI named by FVH_LIB_PATH)
+        if fn is not None:
+            fn.argtypes = REGULARIZE_ARGTYPES
+            fn.restype = C.c_int
         for name, argtypes in OUTLIER_ARGTYPES.items():  # (doubles in the middle of the list: a bare Python float would not convert)
             fn = getattr(L, name, None)
             if fn is None:  # FVH_LIB_PATH names an older build of the ABI (A/B runs): calling the method then raises AttributeError
@@ -515,6 +519,27 @@ def debug_lm_replay(guess, sums, device=0, **lm):
     if rc != 0:
         raise FvhError("fvh_debug_lm_replay: status %d" % rc)
     return [lm_replay_row(r) for r in rows[:max(taken.value, 1)]]
+
+
+# fvh_debug_regularize(device, n, sym6, method, w3, V9, reg6)
+REGULARIZE_ARGTYPES = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+
+
+def debug_regularize(sym6, method, device=0):
+    """The device eigen solver and regulariser alone (dev_math.hpp: sym_eig3, regularize_cov), fp64 in and out. sym6: (n, 6) {xx, xy, xz, yy, yz, zz}
+    or (n, 3, 3) symmetric. -> (w (n, 3) ascending, V (n, 3, 3) with the eigenvectors in the columns, reg (n, 3, 3) = regularize_cov(method))."""
+    s = np.asarray(sym6, dtype=np.float64)
+    if s.ndim == 3 and s.shape[1:] == (3, 3):
+        s = s.reshape(-1, 9)[:, [0, 1, 2, 4, 5, 8]]
+    if s.ndim != 2 or s.shape[1] != 6:
+        raise FvhError("debug_regularize: sym6 must be (n, 6) or (n, 3, 3), got %s" % (s.shape,))
+    s = np.ascontiguousarray(s)
+    n = s.shape[0]
+    w, V, r = np.full((max(n, 1), 3), np.nan), np.full((max(n, 1), 9), np.nan), np.full((max(n, 1), 6), np.nan)
+    rc = load().fvh_debug_regularize(int(device), n, _p(s), int(method), _p(w), _p(V), _p(r))
+    if rc != 0:
+        raise FvhError("fvh_debug_regularize: status %d" % rc)
+    return w, V.reshape(-1, 3, 3), r[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(-1, 3, 3)
 
 
 def device_count():

@@ -222,21 +222,24 @@ __device__ __forceinline__ Sym3<double> vdvt(const double V[9], const double d[3
 
 // RegularizationMethod (ordinals of gicp_settings.hpp:7): reference CPU fast_gicp_impl.hpp:267-297,
 // GPU covariance_regularization.cu:34-124. NONE and NORMALIZED_MIN_EIG are unimplemented on the
-// reference GPU; implemented here with the CPU semantics.
+// reference GPU; implemented here with the CPU semantics. Every method but NONE goes through sym_eig3 (domain: finite C with
+// 1e-100 <= |C|max <= 1e100, or C = 0; the zero matrix gives NONE 0, MIN_EIG and NORMALIZED_MIN_EIG 1e-3 I -- fmax drops the NaN of 0 / 0 --,
+// FROBENIUS sqrt(3) I). Held on its own, in fp64, by tests/test_gpu_cov_edges.py through fvh_debug_regularize.
 __device__ inline Sym3<double> regularize_cov(const Sym3<double>& C, int method) {
   if (method == 0) return C;
-  if (method == 4) {  // FROBENIUS
-    Sym3<double> A = C;
-    A.xx += 1e-3; A.yy += 1e-3; A.zz += 1e-3;
-    Sym3<double> Ai = inverse(A);
-    double nrm = sqrt(Ai.xx * Ai.xx + Ai.yy * Ai.yy + Ai.zz * Ai.zz + 2.0 * (Ai.xy * Ai.xy + Ai.xz * Ai.xz + Ai.yz * Ai.yz));
-    double s = 1.0 / nrm;
-    Ai.xx *= s; Ai.xy *= s; Ai.xz *= s; Ai.yy *= s; Ai.yz *= s; Ai.zz *= s;
-    return inverse(Ai);
-  }
   double w[3], V[9], d[3];
   sym_eig3(C, w, V);
-  if (method == 3) { d[0] = 1e-3; d[1] = 1.0; d[2] = 1.0; }                                            // PLANE
+  if (method == 4) {
+    // FROBENIUS: A = C + 1e-3 I, A^-1 scaled to Frobenius norm 1, inverted again = A |A^-1|_F = V diag(mu_i sqrt(sum_j mu_j^-2)) V^T with
+    // mu = w + 1e-3. The reference inverts twice by cofactors; the determinant of a rank-deficient C formed that way loses cond(A)^2 eps
+    // with cond(A) = |C| / 1e-3 -- more than the fp32 store for collinear or coplanar neighbours a few metres across, every digit at a
+    // spread of 1e3 (tests/test_gpu_cov_edges.py: 0.2 |R| off). Through the eigenvalues the error is the function's own, cond(A) eps.
+    const double m0 = w[0] + 1e-3, m1 = w[1] + 1e-3, m2 = w[2] + 1e-3;
+    const double r0 = 1.0 / m0, r1 = 1.0 / m1, r2 = 1.0 / m2;
+    const double nrm = sqrt(r0 * r0 + r1 * r1 + r2 * r2);
+    d[0] = m0 * nrm; d[1] = m1 * nrm; d[2] = m2 * nrm;
+  }
+  else if (method == 3) { d[0] = 1e-3; d[1] = 1.0; d[2] = 1.0; }                                       // PLANE
   else if (method == 1) { d[0] = fmax(w[0], 1e-3); d[1] = fmax(w[1], 1e-3); d[2] = fmax(w[2], 1e-3); }  // MIN_EIG
   else { d[0] = fmax(w[0] / w[2], 1e-3); d[1] = fmax(w[1] / w[2], 1e-3); d[2] = fmax(w[2] / w[2], 1e-3); }  // NORMALIZED_MIN_EIG
   return vdvt(V, d);

@@ -1215,6 +1215,31 @@ int fvh_debug_lm_replay(int device, const double* guess16, const fvh_lm_params* 
   *steps_run = taken;
   return FVH_OK;
 }
+// ---- test hook: the eigen solver and the regulariser alone, fp64 in and out (kernels_cov.hpp: debug_regularize_kernel) ----
+int fvh_debug_regularize(int device, int n, const double* sym6, int method, double* w3, double* V9, double* reg6) {
+  if (!sym6 || !w3 || !V9 || !reg6) return FVH_ERR_INVALID_ARGUMENT;
+  if (n < 1 || method < 0 || method > 4) return FVH_ERR_INVALID_ARGUMENT;
+  for (size_t i = 0, m = (size_t)n * 6; i < m; i++) if (!std::isfinite(sym6[i])) return FVH_ERR_INVALID_ARGUMENT;
+  if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return FVH_ERR_HIP; }
+  hipStream_t stream = nullptr;
+  double* d = nullptr;  // one allocation: n x (6 in, 3 w, 9 V, 6 reg)
+  const size_t N = (size_t)n;
+  bool ok = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) == hipSuccess;
+  ok = ok && hipMalloc(reinterpret_cast<void**>(&d), sizeof(double) * 24 * N) == hipSuccess;
+  ok = ok && hipMemcpyAsync(d, sym6, sizeof(double) * 6 * N, hipMemcpyHostToDevice, stream) == hipSuccess;
+  if (ok) {
+    double *dw = d + 6 * N, *dV = d + 9 * N, *dr = d + 18 * N;
+    debug_regularize_kernel<<<(unsigned)((N + 255) / 256), 256, 0, stream>>>(d, n, method, dw, dV, dr);
+    ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(w3, dw, sizeof(double) * 3 * N, hipMemcpyDeviceToHost, stream) == hipSuccess &&
+         hipMemcpyAsync(V9, dV, sizeof(double) * 9 * N, hipMemcpyDeviceToHost, stream) == hipSuccess &&
+         hipMemcpyAsync(reg6, dr, sizeof(double) * 6 * N, hipMemcpyDeviceToHost, stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
+  }
+  if (!ok) (void)hipGetLastError();
+  if (stream) (void)hipStreamSynchronize(stream);
+  if (d) (void)hipFree(d);
+  if (stream) (void)hipStreamDestroy(stream);
+  return ok ? FVH_OK : FVH_ERR_HIP;
+}
 int fvh_vgicp_debug_get_table_capacity(fvh_vgicp* h, int* capacity) { CHECK_HANDLE(h); if (!capacity) return FVH_ERR_INVALID_ARGUMENT; *capacity = (int)h->voxelmap.capacity; return FVH_OK; }
 int fvh_vgicp_debug_get_skipped_points(fvh_vgicp* h, int* n) {
   CHECK_HANDLE(h);

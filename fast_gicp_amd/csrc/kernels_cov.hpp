@@ -815,6 +815,25 @@ __global__ __launch_bounds__(256) void regularize_kernel(float4* __restrict__ co
   store_cov(cov, i, regularize_cov(C, method));
 }
 
+// Test hook (fvh_debug_regularize): sym_eig3 and regularize_cov alone, fp64 in and out, one matrix per thread -- what every
+// covariance kernel above and the NDT voxel finalisation run, before the fp32 store hides everything below 1e-7.
+__global__ __launch_bounds__(256) void debug_regularize_kernel(const double* __restrict__ sym6, int n, int method, double* __restrict__ w3, double* __restrict__ V9,
+                                                               double* __restrict__ reg6) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double* s = sym6 + (size_t)i * 6;
+  const Sym3<double> S = {s[0], s[1], s[2], s[3], s[4], s[5]};
+  double w[3], V[9];
+  sym_eig3(S, w, V);
+#pragma unroll
+  for (int j = 0; j < 3; j++) w3[(size_t)i * 3 + j] = w[j];
+#pragma unroll
+  for (int j = 0; j < 9; j++) V9[(size_t)i * 9 + j] = V[j];
+  const Sym3<double> R = regularize_cov(S, method);
+  double* r = reg6 + (size_t)i * 6;
+  r[0] = R.xx; r[1] = R.xy; r[2] = R.xz; r[3] = R.yy; r[4] = R.yz; r[5] = R.zz;
+}
+
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);

@@ -378,6 +378,14 @@ int fvh_debug_slot_pool(int device, int* reserved, int* active, int* recent);   
 #define FVH_LM_REPLAY_ROW 133
 int fvh_debug_lm_replay(int device, const double* guess16, const fvh_lm_params* params, int n_steps, const double* sums /* n_steps x 32 */,
                         double* rows /* n_steps x FVH_LM_REPLAY_ROW */, int* steps_run);
+/* test hook: the symmetric 3x3 eigen solver and the covariance regulariser (dev_math.hpp: sym_eig3, regularize_cov -- what the k-NN and RBF
+ * covariance kernels, the NDT voxel finalisation and the incremental NDT record run on every matrix) ALONE, in fp64 in and out: one thread per
+ * matrix calls the two functions themselves, on a stream of its own. sym6: n x 6 {xx, xy, xz, yy, yz, zz}. w3: n x 3 eigenvalues, ascending.
+ * V9: n x 9, row-major, eigenvectors in the COLUMNS (column j belongs to w3[j]). reg6: n x 6, regularize_cov(method) before any fp32 rounding
+ * (method: the RegularizationMethod ordinal, 0 NONE .. 4 FROBENIUS). Everything is freed before the call returns.
+ * FVH_ERR_INVALID_ARGUMENT: a null pointer, n < 1, a method outside 0..4, a non-finite entry (checked before the device is touched). The
+ * solver's domain is finite matrices with 1e-100 <= |S|max <= 1e100 (or S = 0): DESIGN.md, "The eigen solver on its own". */
+int fvh_debug_regularize(int device, int n, const double* sym6, int method, double* w3, double* V9, double* reg6);
 /* persistent LM kernel, XCD-local hand-offs (kernels_cost.hpp): *wanted = 1 while the process still asks for them, *placement_aborts =
  * launches that ended because the dispatcher had not placed the workgroups of a group on one XCD (3 of those switch the flavour off) */
 int fvh_debug_xcd_local(int* wanted, int* placement_aborts);
