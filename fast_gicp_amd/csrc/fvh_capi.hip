@@ -365,6 +365,11 @@ struct Engine {
     if (side_done) (void)hipEventDestroy(side_done);
     if (side) (void)hipStreamDestroy(side);
   }
+  int comm_destroy() {  // fvh_*_comm_destroy
+    if (comm) { g_rccl.CommDestroy(comm); comm = nullptr; }
+    nranks = 1; rank = 0;
+    return FVH_OK;
+  }
   void peer_detach() {
     for (int i = 0; i < FVH_MAX_PEERS; i++) {
       if (peer.ipc_opened[i] && peer.peer_region[i]) (void)hipIpcCloseMemHandle(peer.peer_region[i]);
@@ -465,7 +470,6 @@ struct fvh_vgicp {
   Pipeline pipe;
   VoxelMapDev source_map;
   bool in_flight() const { return pipe.in_flight(); }
-  static constexpr const char* align_wait_fn = "fvh_vgicp_align_wait";
   void source_changed() { source_map.invalidate(); }
   bool live_map_stale = false;  // the target's covariances changed after `voxelmap` was built (legal: the map stays as built until create_target_voxelmap -- but it must not be carried over a swap)
   void map_rules_changed() { source_map.invalidate(); pipe.invalidate(); }  // accumulation mode / precision: prepared maps were built under the old rule
@@ -489,9 +493,37 @@ struct fvh_vgicp {
   int shard_margin = 2;      // voxels of pose motion the halo allows for on top of the reach of the neighbour offsets
   int shard_fallbacks = 0;   // aligns redone on the full map because a source element left the shard's inner box
   // Incremental target map (fvh_vgicp_map_*, host_incmap.inc.hpp): `voxelmap` keeps its sums and grows in place; there is no cloud behind it
-  bool incremental() const { return voxelmap.inc.live && voxelmap.valid; }
   CloudDev insert_cloud;     // staging of fvh_vgicp_map_insert_cloud
   hipEvent_t merge_ev[2] = {nullptr, nullptr};  // fvh_vgicp_voxelmap_merge_from: the other handle's stream -> ours before the kernel, ours -> its stream after it
+  // ---- what the shared entry-point bodies (namespace shared, below) ask of a handle type ----
+  static constexpr const char* prefix = "fvh_vgicp";   // of its C functions: every function name in a message is built from it
+  static constexpr bool gang_kernels = true;           // Engine::init
+  static constexpr bool side_stream_first = true;      // destroy: drain the side stream, then the main one
+  static constexpr bool map_has_cov = true;            // map voxels hold covariances: map_insert_cloud needs them, target_from_map carries them (and the cloud's box)
+  static constexpr const char* foreign_snapshot = nullptr;  // voxelmap_import: no refusal of its own in front of incmap_import's
+  VoxelMapDev& target_map() { return voxelmap; }
+  const VoxelMapDev& target_map() const { return voxelmap; }
+  bool incremental() const { return target_map().inc.live && target_map().valid; }
+  int created() { return FVH_OK; }
+  void release_all() {
+    pipe.release();
+    source.release(); target.release(); voxelmap.release(); gicp_records.release(); source_map.release(); insert_cloud.release();
+    for (hipEvent_t ev : merge_ev) if (ev) (void)hipEventDestroy(ev);
+  }
+  int map_refusal(const char* who) {
+    if (e.sharded()) return e.fail(FVH_ERR_UNSUPPORTED, std::string(who) + ": not on a multi-GPU handle (communicator / peers / tile attached)");
+    if (shard_map) return e.fail(FVH_ERR_UNSUPPORTED, std::string(who) + ": not with target map sharding on");
+    if (e.precision == FVH_COMPUTE_CUDA_COMPAT) return e.fail(FVH_ERR_UNSUPPORTED, std::string(who) + ": FVH_COMPUTE_CUDA_COMPAT has no incremental target map (its voxel sums are float sums in point order)");
+    return FVH_OK;
+  }
+  const char* not_a_merge_source() const { return e.sharded() || shard_map || e.precision == FVH_COMPUTE_CUDA_COMPAT ? "multi-GPU / sharded / FVH_COMPUTE_CUDA_COMPAT" : nullptr; }
+  int map_begin_mode() const { return voxel_mode == 2 ? 2 : 0; }  // (ADDITIVE_WEIGHTED: the additive voxel type)
+  void before_map_begin() { live_map_stale = false; }
+  void after_map_begin() {}
+  // target_from_map replaces the target cloud as set_target_cloud does -- but the map and the VOXEL correspondences stored against it are not
+  // the cloud's: only nearest-point correspondences (indices into the old cloud) and the per-point records die with it
+  void before_target_from_map() { gicp_records.invalidate(); if (e.corr_kind == 1) e.has_corr = false; }
+  void arithmetic_changed() { voxelmap.invalidate(); map_rules_changed(); e.has_corr = false; }  // CUDA-compat <-> native: the voxel records of the two arithmetics differ (kernels_compat.hpp)
   // the target cloud was replaced: the batch map built from the old one is dead; an incremental map never depended on it
   void target_replaced() { e.has_corr = false; if (!incremental()) voxelmap.invalidate(); gicp_records.invalidate(); }
   int build_map(double res, bool force_safe = false, hipStream_t on_side = nullptr, bool shard = false) {
@@ -505,7 +537,7 @@ struct fvh_vgicp {
   Rebuild rebuild_safe() {
     return [this] {
       // (an insert secures its capacity before it launches: an incremental map never reports an overflow, and has no cloud to rebuild from)
-      if (incremental()) return e.fail(FVH_ERR_BAD_STATE, "the incremental target map reported a table overflow; start again with fvh_vgicp_map_begin");
+      if (incremental()) return e.fail(FVH_ERR_BAD_STATE, std::string("the incremental target map reported a table overflow; start again with ") + prefix + "_map_begin");
       return build_map(voxelmap.res, true, nullptr, voxelmap.is_shard);
     };
   }
@@ -525,7 +557,6 @@ struct fvh_ndt {
   // voxel map are built in `pipe` on the handle's second stream while the LM kernel of the current frame runs on the main one
   Pipeline pipe;
   bool in_flight() const { return pipe.in_flight(); }
-  static constexpr const char* align_wait_fn = "fvh_ndt_align_wait";
   // the instantiation of the handle's distance mode: f(std::integral_constant<int, MODE_NDT_P2D or MODE_NDT_D2D>{})
   template <class F>
   int by_mode(F&& f) const { return distance_mode == FVH_NDT_P2D ? f(std::integral_constant<int, MODE_NDT_P2D>{}) : f(std::integral_constant<int, MODE_NDT_D2D>{}); }
@@ -559,10 +590,37 @@ struct fvh_ndt {
   // Incremental target map (fvh_ndt_map_*, host_incmap.inc.hpp): `target_vm` keeps its sums (sum p, sum p p^T, count) and grows in place; there
   // is no cloud behind it. `target_newer`: a target cloud was set while it was live -- the next create_target_voxelmap (an align makes that
   // call itself) builds the batch map of that cloud and the mode ends.
-  bool incremental() const { return target_vm.inc.live && target_vm.valid; }
   bool target_newer = false;
   CloudDev insert_cloud;     // staging of fvh_ndt_map_insert_cloud
   hipEvent_t merge_ev[2] = {nullptr, nullptr};  // fvh_ndt_voxelmap_merge_from: the other handle's stream -> ours before the kernel, ours -> its stream after it
+  // ---- what the shared entry-point bodies (namespace shared, below) ask of a handle type: see fvh_vgicp ----
+  static constexpr const char* prefix = "fvh_ndt";
+  static constexpr bool gang_kernels = true;
+  static constexpr bool side_stream_first = false;     // destroy: the main stream, then the side stream
+  static constexpr bool map_has_cov = false;           // points only
+  static constexpr const char* foreign_snapshot = "voxelmap_import: the snapshot's accumulation mode is not the live map's (an NDT map takes FVH_VOXEL_NDT_SUMS snapshots only: VGICP sums are of another kind)";
+  VoxelMapDev& target_map() { return target_vm; }
+  const VoxelMapDev& target_map() const { return target_vm; }
+  bool incremental() const { return target_map().inc.live && target_map().valid; }
+  int created() { return e.set_offsets(FVH_DIRECT7, 0.0); }  // ndt_cuda.cu:22
+  void release_all() {
+    pipe.release();
+    source.release(); target.release(); source_vm.release(); target_vm.release(); insert_cloud.release();
+    for (hipEvent_t ev : merge_ev) if (ev) (void)hipEventDestroy(ev);
+  }
+  int map_refusal(const char* who) {
+    if (e.sharded()) return e.fail(FVH_ERR_UNSUPPORTED, std::string(who) + ": not on a multi-GPU handle (communicator / tile attached)");
+    if (e.precision == FVH_COMPUTE_CUDA_COMPAT) return e.fail(FVH_ERR_UNSUPPORTED, std::string(who) + ": FVH_COMPUTE_CUDA_COMPAT has no incremental target map (its voxel sums are float sums in point order)");
+    return FVH_OK;
+  }
+  const char* not_a_merge_source() const { return e.sharded() || e.precision == FVH_COMPUTE_CUDA_COMPAT ? "multi-GPU / FVH_COMPUTE_CUDA_COMPAT" : nullptr; }
+  int map_begin_mode() const { return 1; }
+  void before_map_begin() {}
+  void after_map_begin() { target_newer = false; }
+  // The map stays the target MAP: the cloud target_from_map makes is a snapshot OF it, not a cloud set beside it -- target_newer is
+  // fvh_ndt_set_target_cloud*'s rule, and a cloud such a call left behind is gone now, so nothing is newer.
+  void before_target_from_map() { target_newer = false; }
+  void arithmetic_changed() { source_vm.invalidate(); target_vm.invalidate(); e.has_corr = false; }  // CUDA-compat <-> native: the voxel records of the two arithmetics differ
   int build_target_map() {
     const int rc = build_voxelmap<1>(&e, target, target_vm, resolution, true);
     if (rc == FVH_OK || !target_vm.valid) { target_vm.inc.live = false; target_newer = false; }  // (a call refused for want of a target cloud leaves an incremental map as it was)
@@ -573,7 +631,7 @@ struct fvh_ndt {
       // (an insert secures its capacity before it launches: an incremental map never reports an overflow, and has no cloud to rebuild from.
       // The D2D source map is a hint-sized batch map like any other)
       const bool inc = incremental();
-      if (inc && distance_mode != FVH_NDT_D2D) return e.fail(FVH_ERR_BAD_STATE, "the incremental target map reported a table overflow; start again with fvh_ndt_map_begin");
+      if (inc && distance_mode != FVH_NDT_D2D) return e.fail(FVH_ERR_BAD_STATE, std::string("the incremental target map reported a table overflow; start again with ") + prefix + "_map_begin");
       int rc = inc ? (int)FVH_OK : build_voxelmap<1>(&e, target, target_vm, target_vm.res, true, true);
       if (!rc && distance_mode == FVH_NDT_D2D) {
         rc = build_voxelmap<1>(&e, source, source_vm, source_vm.res, true, true);
@@ -592,7 +650,11 @@ struct fvh_voxelgrid {
   DownsampleDev d;
   OutlierDev o;  // side outputs of crop_range / remove_*_outliers (host_outlier.inc.hpp)
   bool in_flight() const { return false; }  // (a filter has no pipeline: CHECK_HANDLE never refuses on it)
-  static constexpr const char* align_wait_fn = "";
+  static constexpr const char* prefix = "fvh_voxelgrid";
+  static constexpr bool gang_kernels = false;          // a filter never launches a persistent / cooperative kernel
+  static constexpr bool side_stream_first = false;     // (it has no side stream of its own)
+  int created() { return FVH_OK; }
+  void release_all() { d.release(); o.release(); }
 };
 
 // CHECK_HANDLE_SOURCE_CHAIN: the calls that only touch the SOURCE cloud -- they may run beside a target-map build on the side
@@ -602,7 +664,7 @@ struct fvh_voxelgrid {
 #define CHECK_HANDLE_SOURCE_CHAIN(h) \
   if (!(h)) return FVH_ERR_INVALID_ARGUMENT; \
   { hipError_t _e = hipSetDevice((h)->e.device); if (_e != hipSuccess) return (h)->e.hipfail(_e, "hipSetDevice"); } \
-  if ((h)->in_flight()) return (h)->e.fail(FVH_ERR_BAD_STATE, std::string("an align_async is in flight: call ") + (h)->align_wait_fn + " first"); \
+  if ((h)->in_flight()) return (h)->e.fail(FVH_ERR_BAD_STATE, std::string("an align_async is in flight: call ") + (h)->prefix + "_align_wait first"); \
   (h)->e.was_quiet = (h)->e.quiet; (h)->e.quiet = false;
 // CHECK_HANDLE_HOST_ONLY: plain host-side setters that queue nothing: they leave the engine's stream bookkeeping alone.
 #define CHECK_HANDLE_HOST_ONLY(h) \
@@ -612,156 +674,82 @@ struct fvh_voxelgrid {
   CHECK_HANDLE_SOURCE_CHAIN(h) \
   { int _j = (h)->e.settle(); if (_j) return _j; }
 
-extern "C" {
+// ---------------------------------------------------------------------------------------------
+// Entry points the handle types share: ONE body each, written against the vocabulary on the handle structs above. The extern "C"
+// wrapper of each prefix is the guard (which differs between the types here and there) and the call: { GUARD(h); return shared::f(h, ...); }
+// ---------------------------------------------------------------------------------------------
+namespace {
+inline void cloud_replaced(CloudDev& c) { c.has_cov = false; c.has_nbr = false; c.has_cov_sorted = false; }  // what every replaced cloud drops
+namespace shared {
 
-void fvh_default_lm_params(fvh_lm_params* p) {
-  if (!p) return;
-  p->max_iterations = 64; p->rotation_epsilon = 2e-3; p->transformation_epsilon = 5e-4; p->lm_max_iterations = 10; p->lm_init_lambda_factor = 1e-9; p->optimizer = 0;
+template <class H>
+int create(int device, H** out) {
+  if (!out) return FVH_ERR_INVALID_ARGUMENT;
+  *out = nullptr;
+  H* h = new (std::nothrow) H();
+  if (!h) return FVH_ERR_HIP;
+  int rc = h->e.init(device, H::gang_kernels);
+  if (!rc) rc = h->created();
+  if (rc) { std::fprintf(stderr, "%s_create: %s\n", H::prefix, h->e.err.c_str()); h->e.shutdown(); delete h; return rc; }
+  *out = h;
+  return FVH_OK;
 }
-void fvh_default_engine_params(fvh_engine_params* p) { if (p) *p = env_engine_defaults(); }
-static int get_engine_params(Engine* e, fvh_engine_params* out) { if (!out) return e->fail(FVH_ERR_INVALID_ARGUMENT, "get_engine_params: null"); *out = e->params; return FVH_OK; }
-static int set_engine_params(Engine* e, const fvh_engine_params* p) {
+template <class H>
+int destroy(H* h) {
+  if (!h) return FVH_ERR_INVALID_ARGUMENT;
+  (void)hipSetDevice(h->e.device);
+  h->e.deferred = nullptr;
+  for (hipStream_t s : {H::side_stream_first ? h->e.side : h->e.stream, H::side_stream_first ? h->e.stream : h->e.side}) if (s) (void)hipStreamSynchronize(s);
+  h->release_all();
+  h->e.shutdown();
+  delete h;
+  return FVH_OK;
+}
+template <class H>
+const char* last_error(const H* h) { return h ? h->e.err.c_str() : "null handle"; }
+
+int get_engine_params(Engine* e, fvh_engine_params* out) { if (!out) return e->fail(FVH_ERR_INVALID_ARGUMENT, "get_engine_params: null"); *out = e->params; return FVH_OK; }
+int set_engine_params(Engine* e, const fvh_engine_params* p) {
   if (!p) return e->fail(FVH_ERR_INVALID_ARGUMENT, "set_engine_params: null");
   if (const char* why = check_engine_params(*p)) return e->fail(FVH_ERR_INVALID_ARGUMENT, why);
   e->params = *p;
   return FVH_OK;
 }
-int fvh_device_count(int* count) {
-  if (!count) return FVH_ERR_INVALID_ARGUMENT;
-  return hipGetDeviceCount(count) == hipSuccess ? FVH_OK : FVH_ERR_HIP;
-}
-
-// ---- VGICP -------------------------------------------------------------------------------------
-int fvh_vgicp_create(int device, fvh_vgicp** out) {
-  if (!out) return FVH_ERR_INVALID_ARGUMENT;
-  *out = nullptr;
-  fvh_vgicp* h = new (std::nothrow) fvh_vgicp();
-  if (!h) return FVH_ERR_HIP;
-  int rc = h->e.init(device);
-  if (rc) { std::fprintf(stderr, "fvh_vgicp_create: %s\n", h->e.err.c_str()); h->e.shutdown(); delete h; return rc; }
-  *out = h;
-  return FVH_OK;
-}
-int fvh_vgicp_destroy(fvh_vgicp* h) {
-  if (!h) return FVH_ERR_INVALID_ARGUMENT;
-  (void)hipSetDevice(h->e.device);
-  h->e.deferred = nullptr;
-  if (h->e.side) (void)hipStreamSynchronize(h->e.side);
-  if (h->e.stream) (void)hipStreamSynchronize(h->e.stream);
-  h->pipe.release();
-  h->source.release(); h->target.release(); h->voxelmap.release(); h->gicp_records.release(); h->source_map.release(); h->insert_cloud.release();
-  for (hipEvent_t ev : h->merge_ev) if (ev) (void)hipEventDestroy(ev);
-  h->e.shutdown();
-  delete h;
-  return FVH_OK;
-}
-const char* fvh_vgicp_last_error(const fvh_vgicp* h) { return h ? h->e.err.c_str() : "null handle"; }
-int fvh_vgicp_set_resolution(fvh_vgicp* h, double r) {
-  CHECK_HANDLE_HOST_ONLY(h);
+template <class H>
+int set_resolution(H* h, double r) {
   if (!(r > 0)) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "resolution must be > 0");
-  if (h->incremental() && r != h->voxelmap.res) return h->e.fail(FVH_ERR_BAD_STATE, "set_resolution: an incremental target map is live at another resolution; call fvh_vgicp_map_begin again");
+  if (h->incremental() && r != h->target_map().res) return h->e.fail(FVH_ERR_BAD_STATE, std::string("set_resolution: an incremental target map is live at another resolution; call ") + H::prefix + "_map_begin again");
   h->resolution = r;
   return FVH_OK;
 }
-int fvh_vgicp_set_kernel_params(fvh_vgicp* h, double w, double d) { CHECK_HANDLE_HOST_ONLY(h); h->kernel_width = w; h->kernel_max_dist = d; return FVH_OK; }
-int fvh_vgicp_set_neighbor_search_method(fvh_vgicp* h, int m, double radius) { CHECK_HANDLE(h); return h->e.set_offsets(m, radius); }
-int fvh_vgicp_set_precision(fvh_vgicp* h, int p) {
-  CHECK_HANDLE(h);
+template <class H>
+int set_precision(H* h, int p) {
   if (p != FVH_COMPUTE_FP64 && p != FVH_COMPUTE_FP32 && p != FVH_COMPUTE_CUDA_COMPAT) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "bad precision");
   if (p == FVH_COMPUTE_CUDA_COMPAT && h->incremental()) return h->e.fail(FVH_ERR_UNSUPPORTED, "set_precision: FVH_COMPUTE_CUDA_COMPAT has no incremental target map (its voxel sums are float sums in point order)");
-  if ((p == FVH_COMPUTE_CUDA_COMPAT) != (h->e.precision == FVH_COMPUTE_CUDA_COMPAT)) { h->voxelmap.invalidate(); h->map_rules_changed(); h->e.has_corr = false; }  // the voxel records of the two arithmetics differ (kernels_compat.hpp)
+  if ((p == FVH_COMPUTE_CUDA_COMPAT) != (h->e.precision == FVH_COMPUTE_CUDA_COMPAT)) h->arithmetic_changed();
   h->e.precision = p;
   return FVH_OK;
 }
-
-int fvh_vgicp_get_engine_params(fvh_vgicp* h, fvh_engine_params* out) { CHECK_HANDLE_HOST_ONLY(h); return get_engine_params(&h->e, out); }
-int fvh_vgicp_set_engine_params(fvh_vgicp* h, const fvh_engine_params* p) { CHECK_HANDLE(h); return set_engine_params(&h->e, p); }
-
-int fvh_vgicp_create_target_voxelmap(fvh_vgicp* h) { CHECK_HANDLE(h); return h->build_map(h->resolution); }
-// ---- incremental target map (host_incmap.inc.hpp) ----
-static void cloud_replaced(CloudDev& c);
-static int map_refusal(fvh_vgicp* h, const char* who) {
-  if (h->e.sharded()) return h->e.fail(FVH_ERR_UNSUPPORTED, std::string(who) + ": not on a multi-GPU handle (communicator / peers / tile attached)");
-  if (h->shard_map) return h->e.fail(FVH_ERR_UNSUPPORTED, std::string(who) + ": not with target map sharding on");
-  if (h->e.precision == FVH_COMPUTE_CUDA_COMPAT) return h->e.fail(FVH_ERR_UNSUPPORTED, std::string(who) + ": FVH_COMPUTE_CUDA_COMPAT has no incremental target map (its voxel sums are float sums in point order)");
+template <class H>
+int set_lm_trace(H* h, int on) { h->e.lm_trace_on = on != 0; return FVH_OK; }
+int get_lm_trace(Engine* e, int* n, double* rows6) {
+  if (!n) return e->fail(FVH_ERR_INVALID_ARGUMENT, "get_lm_trace: null count");
+  *n = e->lm_trace_rows;
+  if (rows6 && e->lm_trace_rows > 0) {
+    HIP_OR_FAIL(e, hipMemcpyAsync(rows6, e->lm_trace.p, sizeof(double) * 6 * (size_t)e->lm_trace_rows, hipMemcpyDeviceToHost, e->stream));
+    HIP_OR_FAIL(e, hipStreamSynchronize(e->stream));
+  }
   return FVH_OK;
 }
-int fvh_vgicp_map_begin(fvh_vgicp* h, int expected_voxels) {
-  CHECK_HANDLE(h);
-  { const int rc = map_refusal(h, "map_begin"); if (rc) return rc; }
-  h->live_map_stale = false;
-  return incmap_begin(&h->e, h->voxelmap, h->resolution, h->voxel_mode == 2 ? 2 : 0, expected_voxels);  // (ADDITIVE_WEIGHTED: the additive voxel type)
-}
-int fvh_vgicp_map_insert_source(fvh_vgicp* h, const double* T16) {
-  CHECK_HANDLE(h);
-  { const int rc = map_refusal(h, "map_insert_source"); if (rc) return rc; }
-  return incmap_insert(&h->e, h->voxelmap, h->source, T16, "map_insert_source");
-}
-int fvh_vgicp_map_insert_cloud(fvh_vgicp* h, const float* xyz, int n, int stride_floats, const double* covs9, const double* T16, int on_device) {
-  CHECK_HANDLE(h);
-  { const int rc = map_refusal(h, "map_insert_cloud"); if (rc) return rc; }
-  if (!h->incremental()) return h->e.fail(FVH_ERR_BAD_STATE, "map_insert_cloud: no incremental map is live (fvh_vgicp_map_begin)");
-  if (n > 0 && !covs9) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "map_insert_cloud: null covariances");
-  cloud_replaced(h->insert_cloud);
-  int rc = upload_cloud(&h->e, h->insert_cloud, xyz, n, stride_floats, on_device != 0, false);
-  if (!rc && n > 0) rc = set_cov_host(&h->e, h->insert_cloud, covs9);
-  else if (!rc) h->insert_cloud.has_cov = true;
-  if (rc) return rc;
-  return incmap_insert(&h->e, h->voxelmap, h->insert_cloud, T16, "map_insert_cloud");
-}
-int fvh_vgicp_map_prune(fvh_vgicp* h, const double* center3, double radius, int max_age, int* num_removed) {
-  CHECK_HANDLE(h);
-  { const int rc = map_refusal(h, "map_prune"); if (rc) return rc; }
-  return incmap_prune(&h->e, h->voxelmap, center3, radius, max_age, num_removed);
-}
-int fvh_vgicp_map_get_info(fvh_vgicp* h, int* incremental, int* num_voxels, int* capacity, int* num_inserts, long long* num_points, int* num_dropped) {
-  CHECK_HANDLE(h);
-  const bool live = h->incremental();
-  if (incremental) *incremental = live ? 1 : 0;
-  if (capacity) *capacity = live ? (int)h->voxelmap.capacity : 0;
-  if (num_inserts) *num_inserts = live ? (int)h->voxelmap.inc.epoch : 0;
-  if (num_points) *num_points = live ? h->voxelmap.inc.num_points : 0;
-  int cnt[3] = {0, 0, 0};
-  if (live && (num_voxels || num_dropped)) { const int rc = incmap_read_counts(&h->e, h->voxelmap, cnt, nullptr); if (rc) return rc; h->voxelmap.inc.voxel_bound = cnt[0]; }
-  if (num_voxels) *num_voxels = cnt[0];
-  if (num_dropped) *num_dropped = cnt[1];
-  return FVH_OK;
-}
-// ---- snapshots of the incremental map: save / restore / merge (host_incmap.inc.hpp: "snapshots") ----
-int fvh_vgicp_voxelmap_export(fvh_vgicp* h, int* num_voxels, double* resolution, int* mode, int* num_inserts, long long* num_points, int* coords3, double* sums10, unsigned* ages) {
-  CHECK_HANDLE(h);
-  { const int rc = map_refusal(h, "voxelmap_export"); if (rc) return rc; }
-  return incmap_export(&h->e, h->voxelmap, num_voxels, resolution, mode, num_inserts, num_points, coords3, sums10, ages);
-}
-int fvh_vgicp_voxelmap_import(fvh_vgicp* h, int n, const int* coords3, const double* sums10, const unsigned* ages, double resolution, int mode, int num_inserts, long long num_points) {
-  CHECK_HANDLE(h);
-  { const int rc = map_refusal(h, "voxelmap_import"); if (rc) return rc; }
-  return incmap_import(&h->e, h->voxelmap, n, coords3, sums10, ages, resolution, mode, num_inserts, num_points);
-}
-int fvh_vgicp_voxelmap_merge_from(fvh_vgicp* h, fvh_vgicp* other) {
-  CHECK_HANDLE(h);
-  { const int rc = map_refusal(h, "voxelmap_merge_from"); if (rc) return rc; }
-  if (!other) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_merge_from: null other handle");
-  if (other == h) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_merge_from: a map cannot be merged into itself");
-  if (other->e.device != h->e.device) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_merge_from: the two handles are on different devices");
-  if (other->e.sharded() || other->shard_map || other->e.precision == FVH_COMPUTE_CUDA_COMPAT) return h->e.fail(FVH_ERR_UNSUPPORTED, "voxelmap_merge_from: the other handle is a multi-GPU / sharded / FVH_COMPUTE_CUDA_COMPAT handle");
-  if (other->in_flight()) return h->e.fail(FVH_ERR_BAD_STATE, "voxelmap_merge_from: an align_async is in flight on the other handle: call fvh_vgicp_align_wait first");
-  { const int rc = other->e.settle(); if (rc) return h->e.fail(rc, "voxelmap_merge_from: the other handle: " + other->e.err); }
-  for (hipEvent_t& ev : h->merge_ev) if (!ev) HIP_OR_FAIL(&h->e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  other->e.quiet = false;  // (its stream now holds a wait)
-  return incmap_merge_from(&h->e, h->voxelmap, other->voxelmap, other->e.stream, h->merge_ev[0], h->merge_ev[1]);
-}
-// ---- the live incremental map as the handle's target cloud (host_incmap.inc.hpp: incmap_to_cloud) ----
-int fvh_vgicp_target_from_map(fvh_vgicp* h, int min_points, int* num_points_out) {
-  CHECK_HANDLE(h);
-  if (!h->incremental()) return h->e.fail(FVH_ERR_BAD_STATE, "target_from_map: no incremental map is live (fvh_vgicp_map_begin)");
-  // the target cloud is replaced as by set_target_cloud -- but the map and the VOXEL correspondences stored against it are not the cloud's:
-  // only nearest-point correspondences (indices into the old cloud) and the per-point records die with it
-  h->gicp_records.invalidate();
-  if (h->e.corr_kind == 1) h->e.has_corr = false;
-  return incmap_to_cloud(&h->e, h->voxelmap, min_points, h->target, true, true, num_points_out);
-}
-static int get_points_host(Engine* e, const CloudDev& c, float* xyz3, const char* who) {
+template <class H>
+int profile_enable(H* h, int on) { h->e.prof.on = on != 0; h->e.prof.cost_only = on == 2; return FVH_OK; }
+template <class H>
+int profile_reset(H* h) { HIP_OR_FAIL(&h->e, hipStreamSynchronize(h->e.stream)); h->e.prof.reset(); return FVH_OK; }
+template <class H>
+int synchronize(H* h) { HIP_OR_FAIL(&h->e, hipStreamSynchronize(h->e.stream)); h->e.gang_clear(); return FVH_OK; }
+template <class H>
+int get_num_target_points(const H* h, int* n) { if (!h || !n) return FVH_ERR_INVALID_ARGUMENT; *n = h->target.has_pts ? h->target.n : 0; return FVH_OK; }
+int get_points_host(Engine* e, const CloudDev& c, float* xyz3, const char* who) {
   if (!c.has_pts) return e->fail(FVH_ERR_BAD_STATE, std::string(who) + ": cloud not set");
   if (c.n == 0) return FVH_OK;
   if (!xyz3) return e->fail(FVH_ERR_INVALID_ARGUMENT, std::string(who) + ": null");
@@ -771,11 +759,155 @@ static int get_points_host(Engine* e, const CloudDev& c, float* xyz3, const char
   for (int i = 0; i < c.n; i++) { xyz3[3 * (size_t)i] = h[(size_t)i].x; xyz3[3 * (size_t)i + 1] = h[(size_t)i].y; xyz3[3 * (size_t)i + 2] = h[(size_t)i].z; }
   return FVH_OK;
 }
-int fvh_vgicp_get_target_points(fvh_vgicp* h, float* xyz3) { CHECK_HANDLE(h); return get_points_host(&h->e, h->target, xyz3, "get_target_points"); }
+// the (source row, target voxel) pairs of a stored voxel correspondence list: offset-major then source element, invalid pairs removed
+// (the order of find_voxel_correspondences.cu:93-110); row_of: the row of source element i in `corr` (fetch_row_of_point)
+void emit_voxel_pairs(const Engine* e, VoxelMapDev& target_map, const std::vector<int>& corr, const std::vector<int>& row_of, int n_src, int* pairs) {
+  size_t w = 0;
+  for (int o = 0; o < e->n_off; o++)
+    for (int i = 0; i < n_src; i++) {
+      const int b = corr[(size_t)row_of[(size_t)i] * e->n_off + o];
+      if (b < 0) continue;
+      pairs[2 * w] = i;
+      pairs[2 * w + 1] = target_map.bucket_to_index[b];
+      w++;
+    }
+}
+
+// ---- incremental target map (host_incmap.inc.hpp): H::target_map() keeps its sums and grows in place ----
+// "is a map live": decided here, once, for every call that needs one (the incmap_* functions rely on it)
+template <class H>
+int map_live(H* h, const char* who) {
+  if (!h->incremental()) return h->e.fail(FVH_ERR_BAD_STATE, std::string(who) + ": no incremental map is live (" + H::prefix + "_map_begin)");
+  return FVH_OK;
+}
+// what the calls that work ON a live map ask first: may this handle have one at all (the type's own clauses), and has it one
+template <class H>
+int map_call(H* h, const char* who) {
+  const int rc = h->map_refusal(who);
+  return rc ? rc : map_live(h, who);
+}
+template <class H>
+int map_begin(H* h, int expected_voxels) {
+  { const int rc = h->map_refusal("map_begin"); if (rc) return rc; }
+  h->before_map_begin();
+  const int rc = incmap_begin(&h->e, h->target_map(), h->resolution, h->map_begin_mode(), expected_voxels);
+  if (rc == FVH_OK) h->after_map_begin();
+  return rc;
+}
+template <class H>
+int map_insert_source(H* h, const double* T16) {
+  { const int rc = map_call(h, "map_insert_source"); if (rc) return rc; }
+  return incmap_insert(&h->e, h->target_map(), h->source, T16, "map_insert_source");
+}
+template <class H>
+int map_insert_cloud(H* h, const float* xyz, int n, int stride_floats, const double* covs9 /* H::map_has_cov; else null */, const double* T16, int on_device) {
+  { const int rc = map_call(h, "map_insert_cloud"); if (rc) return rc; }
+  if (H::map_has_cov && n > 0 && !covs9) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "map_insert_cloud: null covariances");
+  cloud_replaced(h->insert_cloud);
+  int rc = upload_cloud(&h->e, h->insert_cloud, xyz, n, stride_floats, on_device != 0, false);
+  if (H::map_has_cov && !rc) {
+    if (n > 0) rc = set_cov_host(&h->e, h->insert_cloud, covs9);
+    else h->insert_cloud.has_cov = true;
+  }
+  if (rc) return rc;
+  return incmap_insert(&h->e, h->target_map(), h->insert_cloud, T16, "map_insert_cloud");
+}
+template <class H>
+int map_prune(H* h, const double* center3, double radius, int max_age, int* num_removed) {
+  { const int rc = map_call(h, "map_prune"); if (rc) return rc; }
+  return incmap_prune(&h->e, h->target_map(), center3, radius, max_age, num_removed);
+}
+template <class H>
+int map_get_info(H* h, int* incremental, int* num_voxels, int* capacity, int* num_inserts, long long* num_points, int* num_dropped) {
+  VoxelMapDev& vm = h->target_map();
+  const bool live = h->incremental();
+  if (incremental) *incremental = live ? 1 : 0;
+  if (capacity) *capacity = live ? (int)vm.capacity : 0;
+  if (num_inserts) *num_inserts = live ? (int)vm.inc.epoch : 0;
+  if (num_points) *num_points = live ? vm.inc.num_points : 0;
+  int cnt[3] = {0, 0, 0};
+  if (live && (num_voxels || num_dropped)) { const int rc = incmap_read_counts(&h->e, vm, cnt, nullptr); if (rc) return rc; vm.inc.voxel_bound = cnt[0]; }
+  if (num_voxels) *num_voxels = cnt[0];
+  if (num_dropped) *num_dropped = cnt[1];
+  return FVH_OK;
+}
+// ---- snapshots of the incremental map: save / restore / merge (host_incmap.inc.hpp: "snapshots") ----
+template <class H>
+int voxelmap_export(H* h, int* num_voxels, double* resolution, int* mode, int* num_inserts, long long* num_points, int* coords3, double* sums10, unsigned* ages) {
+  { const int rc = map_call(h, "voxelmap_export"); if (rc) return rc; }
+  return incmap_export(&h->e, h->target_map(), num_voxels, resolution, mode, num_inserts, num_points, coords3, sums10, ages);
+}
+template <class H>
+int voxelmap_import(H* h, int n, const int* coords3, const double* sums10, const unsigned* ages, double resolution, int mode, int num_inserts, long long num_points) {
+  { const int rc = map_call(h, "voxelmap_import"); if (rc) return rc; }
+  if (H::foreign_snapshot && mode != incmap_snapshot_mode(h->target_map())) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, H::foreign_snapshot);
+  return incmap_import(&h->e, h->target_map(), n, coords3, sums10, ages, resolution, mode, num_inserts, num_points);
+}
+template <class H>
+int voxelmap_merge_from(H* h, H* other) {
+  { const int rc = h->map_refusal("voxelmap_merge_from"); if (rc) return rc; }
+  if (!other) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_merge_from: null other handle");
+  if (other == h) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_merge_from: a map cannot be merged into itself");
+  if (other->e.device != h->e.device) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_merge_from: the two handles are on different devices");
+  if (const char* kind = other->not_a_merge_source()) return h->e.fail(FVH_ERR_UNSUPPORTED, std::string("voxelmap_merge_from: the other handle is a ") + kind + " handle");
+  if (other->in_flight()) return h->e.fail(FVH_ERR_BAD_STATE, std::string("voxelmap_merge_from: an align_async is in flight on the other handle: call ") + H::prefix + "_align_wait first");
+  { const int rc = map_live(h, "voxelmap_merge_from"); if (rc) return rc; }
+  if (!other->incremental()) return h->e.fail(FVH_ERR_BAD_STATE, std::string("voxelmap_merge_from: the other handle has no live incremental map (") + H::prefix + "_map_begin)");
+  // every refusal that needs no HIP call has been given: only now is the other handle's stream touched
+  { const int rc = other->e.settle(); if (rc) return h->e.fail(rc, "voxelmap_merge_from: the other handle: " + other->e.err); }
+  for (hipEvent_t& ev : h->merge_ev) if (!ev) HIP_OR_FAIL(&h->e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  other->e.quiet = false;  // (its stream now holds a wait)
+  return incmap_merge_from(&h->e, h->target_map(), other->target_map(), other->e.stream, h->merge_ev[0], h->merge_ev[1]);
+}
+// ---- the live incremental map as the handle's target cloud (host_incmap.inc.hpp: incmap_to_cloud) ----
+template <class H>
+int target_from_map(H* h, int min_points, int* num_points_out) {
+  { const int rc = map_live(h, "target_from_map"); if (rc) return rc; }
+  h->before_target_from_map();
+  return incmap_to_cloud(&h->e, h->target_map(), min_points, h->target, H::map_has_cov, H::map_has_cov, num_points_out);
+}
+}  // namespace shared
+}  // namespace
+
+extern "C" {
+
+void fvh_default_lm_params(fvh_lm_params* p) {
+  if (!p) return;
+  p->max_iterations = 64; p->rotation_epsilon = 2e-3; p->transformation_epsilon = 5e-4; p->lm_max_iterations = 10; p->lm_init_lambda_factor = 1e-9; p->optimizer = 0;
+}
+void fvh_default_engine_params(fvh_engine_params* p) { if (p) *p = env_engine_defaults(); }
+int fvh_device_count(int* count) {
+  if (!count) return FVH_ERR_INVALID_ARGUMENT;
+  return hipGetDeviceCount(count) == hipSuccess ? FVH_OK : FVH_ERR_HIP;
+}
+
+// ---- VGICP -------------------------------------------------------------------------------------
+int fvh_vgicp_create(int device, fvh_vgicp** out) { return shared::create(device, out); }
+int fvh_vgicp_destroy(fvh_vgicp* h) { return shared::destroy(h); }
+const char* fvh_vgicp_last_error(const fvh_vgicp* h) { return shared::last_error(h); }
+int fvh_vgicp_set_resolution(fvh_vgicp* h, double r) { CHECK_HANDLE_HOST_ONLY(h); return shared::set_resolution(h, r); }
+int fvh_vgicp_set_kernel_params(fvh_vgicp* h, double w, double d) { CHECK_HANDLE_HOST_ONLY(h); h->kernel_width = w; h->kernel_max_dist = d; return FVH_OK; }
+int fvh_vgicp_set_neighbor_search_method(fvh_vgicp* h, int m, double radius) { CHECK_HANDLE(h); return h->e.set_offsets(m, radius); }
+int fvh_vgicp_set_precision(fvh_vgicp* h, int p) { CHECK_HANDLE(h); return shared::set_precision(h, p); }
+int fvh_vgicp_get_engine_params(fvh_vgicp* h, fvh_engine_params* out) { CHECK_HANDLE_HOST_ONLY(h); return shared::get_engine_params(&h->e, out); }
+int fvh_vgicp_set_engine_params(fvh_vgicp* h, const fvh_engine_params* p) { CHECK_HANDLE(h); return shared::set_engine_params(&h->e, p); }
+
+int fvh_vgicp_create_target_voxelmap(fvh_vgicp* h) { CHECK_HANDLE(h); return h->build_map(h->resolution); }
+// ---- incremental target map, its snapshots, the map as the target cloud (namespace shared) ----
+int fvh_vgicp_map_begin(fvh_vgicp* h, int expected_voxels) { CHECK_HANDLE(h); return shared::map_begin(h, expected_voxels); }
+int fvh_vgicp_map_insert_source(fvh_vgicp* h, const double* T16) { CHECK_HANDLE(h); return shared::map_insert_source(h, T16); }
+int fvh_vgicp_map_insert_cloud(fvh_vgicp* h, const float* xyz, int n, int stride_floats, const double* covs9, const double* T16, int on_device) { CHECK_HANDLE(h); return shared::map_insert_cloud(h, xyz, n, stride_floats, covs9, T16, on_device); }
+int fvh_vgicp_map_prune(fvh_vgicp* h, const double* center3, double radius, int max_age, int* num_removed) { CHECK_HANDLE(h); return shared::map_prune(h, center3, radius, max_age, num_removed); }
+int fvh_vgicp_map_get_info(fvh_vgicp* h, int* incremental, int* num_voxels, int* capacity, int* num_inserts, long long* num_points, int* num_dropped) { CHECK_HANDLE(h); return shared::map_get_info(h, incremental, num_voxels, capacity, num_inserts, num_points, num_dropped); }
+int fvh_vgicp_voxelmap_export(fvh_vgicp* h, int* num_voxels, double* resolution, int* mode, int* num_inserts, long long* num_points, int* coords3, double* sums10, unsigned* ages) { CHECK_HANDLE(h); return shared::voxelmap_export(h, num_voxels, resolution, mode, num_inserts, num_points, coords3, sums10, ages); }
+int fvh_vgicp_voxelmap_import(fvh_vgicp* h, int n, const int* coords3, const double* sums10, const unsigned* ages, double resolution, int mode, int num_inserts, long long num_points) { CHECK_HANDLE(h); return shared::voxelmap_import(h, n, coords3, sums10, ages, resolution, mode, num_inserts, num_points); }
+int fvh_vgicp_voxelmap_merge_from(fvh_vgicp* h, fvh_vgicp* other) { CHECK_HANDLE(h); return shared::voxelmap_merge_from(h, other); }
+int fvh_vgicp_target_from_map(fvh_vgicp* h, int min_points, int* num_points_out) { CHECK_HANDLE(h); return shared::target_from_map(h, min_points, num_points_out); }
+int fvh_vgicp_get_target_points(fvh_vgicp* h, float* xyz3) { CHECK_HANDLE(h); return shared::get_points_host(&h->e, h->target, xyz3, "get_target_points"); }
 int fvh_vgicp_set_voxel_accumulation_mode(fvh_vgicp* h, int mode) {
   CHECK_HANDLE(h);
   if (mode < 0 || mode > 2) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "unknown voxel accumulation mode");
-  if (h->incremental() && (mode == 2) != (h->voxelmap.inc.mode == 2)) return h->e.fail(FVH_ERR_BAD_STATE, "set_voxel_accumulation_mode: an incremental target map is live in the other mode; call fvh_vgicp_map_begin again");
+  if (h->incremental() && (mode == 2) != (h->voxelmap.inc.mode == 2)) return h->e.fail(FVH_ERR_BAD_STATE, std::string("set_voxel_accumulation_mode: an incremental target map is live in the other mode; call ") + h->prefix + "_map_begin again");
   if (mode != h->voxel_mode && h->incremental()) h->map_rules_changed();  // (ADDITIVE <-> ADDITIVE_WEIGHTED: the same voxel type, the live map stays)
   else if (mode != h->voxel_mode) { h->voxelmap.invalidate(); h->map_rules_changed(); h->e.has_corr = false; }
   h->voxel_mode = mode;
@@ -848,7 +980,6 @@ int fvh_vgicp_gicp_swap_source_and_target(fvh_vgicp* h) {  // FastGICP::swapSour
   h->source_map.invalidate();
   return FVH_OK;
 }
-static void cloud_replaced(CloudDev& c) { c.has_cov = false; c.has_nbr = false; c.has_cov_sorted = false; }
 // The Morton order of a VGICP cloud is queued right behind its upload: every neighbour search needs it (and large clouds walk the LM
 // loop in it), and the caller's next call -- find_*_neighbors as a rule -- would launch it a few microseconds of host time later
 // with the stream idle in between (kernel trace: 4 us between the pack kernel and the sort).
@@ -881,7 +1012,7 @@ int fvh_vgicp_set_source_covariances(fvh_vgicp* h, const double* c) { CHECK_HAND
 int fvh_vgicp_set_target_covariances(fvh_vgicp* h, const double* c) { CHECK_HANDLE(h); h->live_map_stale = true; return set_cov_host(&h->e, h->target, c); }
 
 int fvh_vgicp_get_num_source_points(const fvh_vgicp* h, int* n) { if (!h || !n) return FVH_ERR_INVALID_ARGUMENT; *n = h->source.has_pts ? h->source.n : 0; return FVH_OK; }
-int fvh_vgicp_get_num_target_points(const fvh_vgicp* h, int* n) { if (!h || !n) return FVH_ERR_INVALID_ARGUMENT; *n = h->target.has_pts ? h->target.n : 0; return FVH_OK; }
+int fvh_vgicp_get_num_target_points(const fvh_vgicp* h, int* n) { return shared::get_num_target_points(h, n); }
 int fvh_vgicp_get_source_neighbors(fvh_vgicp* h, int* k, int* out) { CHECK_HANDLE(h); return get_nbr_host(&h->e, h->source, k, out); }
 int fvh_vgicp_get_target_neighbors(fvh_vgicp* h, int* k, int* out) { CHECK_HANDLE(h); return get_nbr_host(&h->e, h->target, k, out); }
 int fvh_vgicp_get_source_covariances(fvh_vgicp* h, float* c) { CHECK_HANDLE(h); return get_cov_host(&h->e, h->source, c); }
@@ -936,7 +1067,6 @@ int fvh_vgicp_get_num_correspondences(fvh_vgicp* h, int* n) {
   *n = c;
   return FVH_OK;
 }
-// offset-major then source index, invalid pairs removed: the order of find_voxel_correspondences.cu:93-110
 int fvh_vgicp_get_voxel_correspondences(fvh_vgicp* h, int* pairs) {
   CHECK_HANDLE(h);
   if (!pairs) return FVH_ERR_INVALID_ARGUMENT;
@@ -950,15 +1080,7 @@ int fvh_vgicp_get_voxel_correspondences(fvh_vgicp* h, int* pairs) {
   std::vector<int> row_of;
   rc = fetch_row_of_point(&h->e, h->source, h->e.corr_n_src, row_of);
   if (rc) return rc;
-  size_t w = 0;
-  for (int o = 0; o < h->e.n_off; o++)
-    for (int i = 0; i < h->e.corr_n_src; i++) {
-      int b = corr[(size_t)row_of[(size_t)i] * h->e.n_off + o];
-      if (b < 0) continue;
-      pairs[2 * w] = i;
-      pairs[2 * w + 1] = h->voxelmap.bucket_to_index[b];
-      w++;
-    }
+  shared::emit_voxel_pairs(&h->e, h->voxelmap, corr, row_of, h->e.corr_n_src, pairs);
   return FVH_OK;
 }
 
@@ -1122,20 +1244,11 @@ int fvh_vgicp_adopt_prepared_source(fvh_vgicp* h) {
   CHECK_HANDLE(h);  // (a map build swap_source_and_target() deferred runs here, in order on the main stream: queued on the second one it reached the LM kernel 10 us later -- measured)
   return h->pipe.adopt(&h->e, h->source, h->source_map, "fvh_vgicp_prepare_source_device");
 }
-static int get_lm_trace(Engine* e, int* n, double* rows6) {
-  if (!n) return e->fail(FVH_ERR_INVALID_ARGUMENT, "get_lm_trace: null count");
-  *n = e->lm_trace_rows;
-  if (rows6 && e->lm_trace_rows > 0) {
-    HIP_OR_FAIL(e, hipMemcpyAsync(rows6, e->lm_trace.p, sizeof(double) * 6 * (size_t)e->lm_trace_rows, hipMemcpyDeviceToHost, e->stream));
-    HIP_OR_FAIL(e, hipStreamSynchronize(e->stream));
-  }
-  return FVH_OK;
-}
-int fvh_vgicp_set_lm_trace(fvh_vgicp* h, int on) { CHECK_HANDLE(h); h->e.lm_trace_on = on != 0; return FVH_OK; }
-int fvh_vgicp_get_lm_trace(fvh_vgicp* h, int* n, double* rows6) { CHECK_HANDLE(h); return get_lm_trace(&h->e, n, rows6); }
+int fvh_vgicp_set_lm_trace(fvh_vgicp* h, int on) { CHECK_HANDLE(h); return shared::set_lm_trace(h, on); }
+int fvh_vgicp_get_lm_trace(fvh_vgicp* h, int* n, double* rows6) { CHECK_HANDLE(h); return shared::get_lm_trace(&h->e, n, rows6); }
 int fvh_vgicp_fitness_score(fvh_vgicp* h, const double* T, double max_range, double* score) { CHECK_HANDLE(h); return do_fitness(&h->e, h->source, h->target, T, max_range, score); }
-int fvh_vgicp_profile_enable(fvh_vgicp* h, int on) { CHECK_HANDLE_HOST_ONLY(h); h->e.prof.on = on != 0; h->e.prof.cost_only = on == 2; return FVH_OK; }
-int fvh_vgicp_profile_reset(fvh_vgicp* h) { CHECK_HANDLE(h); HIP_OR_FAIL(&h->e, hipStreamSynchronize(h->e.stream)); h->e.prof.reset(); return FVH_OK; }
+int fvh_vgicp_profile_enable(fvh_vgicp* h, int on) { CHECK_HANDLE_HOST_ONLY(h); return shared::profile_enable(h, on); }
+int fvh_vgicp_profile_reset(fvh_vgicp* h) { CHECK_HANDLE(h); return shared::profile_reset(h); }
 int fvh_vgicp_profile_get(fvh_vgicp* h, const char* cls, double* ms, int* n) { CHECK_HANDLE(h); return profile_get(&h->e, cls, ms, n); }
 int fvh_vgicp_debug_set_voxel_hint(fvh_vgicp* h, int num_voxels) { CHECK_HANDLE(h); h->voxelmap.nv_hint = num_voxels; return FVH_OK; }
 int fvh_vgicp_debug_get_persist_aborts(fvh_vgicp* h, int* n) { CHECK_HANDLE(h); if (!n) return FVH_ERR_INVALID_ARGUMENT; *n = h->e.persist_aborts; return FVH_OK; }
@@ -1249,7 +1362,7 @@ int fvh_vgicp_debug_get_skipped_points(fvh_vgicp* h, int* n) {
   HIP_OR_FAIL(&h->e, hipStreamSynchronize(h->e.stream));
   return FVH_OK;
 }
-int fvh_vgicp_synchronize(fvh_vgicp* h) { CHECK_HANDLE(h); HIP_OR_FAIL(&h->e, hipStreamSynchronize(h->e.stream)); h->e.gang_clear(); return FVH_OK; }
+int fvh_vgicp_synchronize(fvh_vgicp* h) { CHECK_HANDLE(h); return shared::synchronize(h); }
 
 #ifdef FVH_KNN_TIMING
 int fvh_debug_pair_counts(unsigned long long* out8, int reset) {  // candidate points / box tests the culled k-NN and RBF searches evaluated since the last reset
@@ -1403,52 +1516,18 @@ int fvh_vgicp_peer_selfcheck(fvh_vgicp* h, double timeout_seconds, int* missing_
   return FVH_OK;
 }
 int fvh_vgicp_peer_detach(fvh_vgicp* h) { CHECK_HANDLE(h); h->e.peer_detach(); h->e.has_corr = false; return FVH_OK; }
-int fvh_vgicp_comm_destroy(fvh_vgicp* h) { CHECK_HANDLE(h); if (h->e.comm) { g_rccl.CommDestroy(h->e.comm); h->e.comm = nullptr; } h->e.nranks = 1; h->e.rank = 0; return FVH_OK; }
+int fvh_vgicp_comm_destroy(fvh_vgicp* h) { CHECK_HANDLE(h); return h->e.comm_destroy(); }
 
 // ---- NDT ---------------------------------------------------------------------------------------
-int fvh_ndt_create(int device, fvh_ndt** out) {
-  if (!out) return FVH_ERR_INVALID_ARGUMENT;
-  *out = nullptr;
-  fvh_ndt* h = new (std::nothrow) fvh_ndt();
-  if (!h) return FVH_ERR_HIP;
-  int rc = h->e.init(device);
-  if (!rc) rc = h->e.set_offsets(FVH_DIRECT7, 0.0);  // ndt_cuda.cu:22
-  if (rc) { std::fprintf(stderr, "fvh_ndt_create: %s\n", h->e.err.c_str()); h->e.shutdown(); delete h; return rc; }
-  *out = h;
-  return FVH_OK;
-}
-int fvh_ndt_destroy(fvh_ndt* h) {
-  if (!h) return FVH_ERR_INVALID_ARGUMENT;
-  (void)hipSetDevice(h->e.device);
-  if (h->e.stream) (void)hipStreamSynchronize(h->e.stream);
-  if (h->e.side) (void)hipStreamSynchronize(h->e.side);
-  h->pipe.release();
-  h->source.release(); h->target.release(); h->source_vm.release(); h->target_vm.release(); h->insert_cloud.release();
-  for (hipEvent_t ev : h->merge_ev) if (ev) (void)hipEventDestroy(ev);
-  h->e.shutdown();
-  delete h;
-  return FVH_OK;
-}
-const char* fvh_ndt_last_error(const fvh_ndt* h) { return h ? h->e.err.c_str() : "null handle"; }
+int fvh_ndt_create(int device, fvh_ndt** out) { return shared::create(device, out); }
+int fvh_ndt_destroy(fvh_ndt* h) { return shared::destroy(h); }
+const char* fvh_ndt_last_error(const fvh_ndt* h) { return shared::last_error(h); }
 int fvh_ndt_set_distance_mode(fvh_ndt* h, int m) { CHECK_HANDLE(h); if (m != FVH_NDT_P2D && m != FVH_NDT_D2D) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "bad distance mode"); h->distance_mode = m; h->e.has_corr = false; return FVH_OK; }
-int fvh_ndt_set_resolution(fvh_ndt* h, double r) {
-  CHECK_HANDLE(h);
-  if (!(r > 0)) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "resolution must be > 0");
-  if (h->incremental() && r != h->target_vm.res) return h->e.fail(FVH_ERR_BAD_STATE, "set_resolution: an incremental target map is live at another resolution; call fvh_ndt_map_begin again");
-  h->resolution = r;
-  return FVH_OK;
-}
+int fvh_ndt_set_resolution(fvh_ndt* h, double r) { CHECK_HANDLE(h); return shared::set_resolution(h, r); }
 int fvh_ndt_set_neighbor_search_method(fvh_ndt* h, int m, double radius) { CHECK_HANDLE(h); return h->e.set_offsets(m, radius); }
-int fvh_ndt_set_precision(fvh_ndt* h, int p) {
-  CHECK_HANDLE(h);
-  if (p != FVH_COMPUTE_FP64 && p != FVH_COMPUTE_FP32 && p != FVH_COMPUTE_CUDA_COMPAT) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "bad precision");
-  if (p == FVH_COMPUTE_CUDA_COMPAT && h->incremental()) return h->e.fail(FVH_ERR_UNSUPPORTED, "set_precision: FVH_COMPUTE_CUDA_COMPAT has no incremental target map (its voxel sums are float sums in point order)");
-  if ((p == FVH_COMPUTE_CUDA_COMPAT) != (h->e.precision == FVH_COMPUTE_CUDA_COMPAT)) { h->source_vm.invalidate(); h->target_vm.invalidate(); h->e.has_corr = false; }  // the voxel records of the two arithmetics differ
-  h->e.precision = p;
-  return FVH_OK;
-}
-int fvh_ndt_get_engine_params(fvh_ndt* h, fvh_engine_params* out) { CHECK_HANDLE_HOST_ONLY(h); return get_engine_params(&h->e, out); }
-int fvh_ndt_set_engine_params(fvh_ndt* h, const fvh_engine_params* p) { CHECK_HANDLE(h); return set_engine_params(&h->e, p); }
+int fvh_ndt_set_precision(fvh_ndt* h, int p) { CHECK_HANDLE(h); return shared::set_precision(h, p); }
+int fvh_ndt_get_engine_params(fvh_ndt* h, fvh_engine_params* out) { CHECK_HANDLE_HOST_ONLY(h); return shared::get_engine_params(&h->e, out); }
+int fvh_ndt_set_engine_params(fvh_ndt* h, const fvh_engine_params* p) { CHECK_HANDLE(h); return shared::set_engine_params(&h->e, p); }
 int fvh_ndt_swap_source_and_target(fvh_ndt* h) {
   CHECK_HANDLE(h);
   if (h->incremental()) return h->e.fail(FVH_ERR_BAD_STATE, "swap_source_and_target: the live target map is incremental -- there is no cloud behind it to become a source");
@@ -1483,94 +1562,18 @@ int fvh_ndt_create_target_voxelmap(fvh_ndt* h) {
   return h->build_target_map();
 }
 int fvh_ndt_create_voxelmaps(fvh_ndt* h) { int rc = fvh_ndt_create_source_voxelmap(h); if (rc) return rc; return fvh_ndt_create_target_voxelmap(h); }
-// ---- incremental target map (host_incmap.inc.hpp; the VGICP calls above, for NDT voxels: points only) ----
-static int ndt_map_refusal(fvh_ndt* h, const char* who) {
-  if (h->e.sharded()) return h->e.fail(FVH_ERR_UNSUPPORTED, std::string(who) + ": not on a multi-GPU handle (communicator / tile attached)");
-  if (h->e.precision == FVH_COMPUTE_CUDA_COMPAT) return h->e.fail(FVH_ERR_UNSUPPORTED, std::string(who) + ": FVH_COMPUTE_CUDA_COMPAT has no incremental target map (its voxel sums are float sums in point order)");
-  return FVH_OK;
-}
-static int ndt_map_live(fvh_ndt* h, const char* who) {
-  if (!h->incremental()) return h->e.fail(FVH_ERR_BAD_STATE, std::string(who) + ": no incremental map is live (fvh_ndt_map_begin)");
-  return FVH_OK;
-}
-int fvh_ndt_map_begin(fvh_ndt* h, int expected_voxels) {
-  CHECK_HANDLE(h);
-  { const int rc = ndt_map_refusal(h, "map_begin"); if (rc) return rc; }
-  const int rc = incmap_begin(&h->e, h->target_vm, h->resolution, 1, expected_voxels);
-  if (rc == FVH_OK) h->target_newer = false;
-  return rc;
-}
-int fvh_ndt_map_insert_source(fvh_ndt* h, const double* T16) {
-  CHECK_HANDLE(h);
-  { const int rc = ndt_map_refusal(h, "map_insert_source"); if (rc) return rc; }
-  { const int rc = ndt_map_live(h, "map_insert_source"); if (rc) return rc; }
-  return incmap_insert(&h->e, h->target_vm, h->source, T16, "map_insert_source");
-}
-int fvh_ndt_map_insert_cloud(fvh_ndt* h, const float* xyz, int n, int stride_floats, const double* T16, int on_device) {
-  CHECK_HANDLE(h);
-  { const int rc = ndt_map_refusal(h, "map_insert_cloud"); if (rc) return rc; }
-  { const int rc = ndt_map_live(h, "map_insert_cloud"); if (rc) return rc; }
-  const int rc = upload_cloud(&h->e, h->insert_cloud, xyz, n, stride_floats, on_device != 0, false);
-  if (rc) return rc;
-  return incmap_insert(&h->e, h->target_vm, h->insert_cloud, T16, "map_insert_cloud");
-}
-int fvh_ndt_map_prune(fvh_ndt* h, const double* center3, double radius, int max_age, int* num_removed) {
-  CHECK_HANDLE(h);
-  { const int rc = ndt_map_refusal(h, "map_prune"); if (rc) return rc; }
-  { const int rc = ndt_map_live(h, "map_prune"); if (rc) return rc; }
-  return incmap_prune(&h->e, h->target_vm, center3, radius, max_age, num_removed);
-}
-int fvh_ndt_map_get_info(fvh_ndt* h, int* incremental, int* num_voxels, int* capacity, int* num_inserts, long long* num_points, int* num_dropped) {
-  CHECK_HANDLE(h);
-  const bool live = h->incremental();
-  if (incremental) *incremental = live ? 1 : 0;
-  if (capacity) *capacity = live ? (int)h->target_vm.capacity : 0;
-  if (num_inserts) *num_inserts = live ? (int)h->target_vm.inc.epoch : 0;
-  if (num_points) *num_points = live ? h->target_vm.inc.num_points : 0;
-  int cnt[3] = {0, 0, 0};
-  if (live && (num_voxels || num_dropped)) { const int rc = incmap_read_counts(&h->e, h->target_vm, cnt, nullptr); if (rc) return rc; h->target_vm.inc.voxel_bound = cnt[0]; }
-  if (num_voxels) *num_voxels = cnt[0];
-  if (num_dropped) *num_dropped = cnt[1];
-  return FVH_OK;
-}
-int fvh_ndt_voxelmap_export(fvh_ndt* h, int* num_voxels, double* resolution, int* mode, int* num_inserts, long long* num_points, int* coords3, double* sums10, unsigned* ages) {
-  CHECK_HANDLE(h);
-  { const int rc = ndt_map_refusal(h, "voxelmap_export"); if (rc) return rc; }
-  { const int rc = ndt_map_live(h, "voxelmap_export"); if (rc) return rc; }
-  return incmap_export(&h->e, h->target_vm, num_voxels, resolution, mode, num_inserts, num_points, coords3, sums10, ages);
-}
-int fvh_ndt_voxelmap_import(fvh_ndt* h, int n, const int* coords3, const double* sums10, const unsigned* ages, double resolution, int mode, int num_inserts, long long num_points) {
-  CHECK_HANDLE(h);
-  { const int rc = ndt_map_refusal(h, "voxelmap_import"); if (rc) return rc; }
-  { const int rc = ndt_map_live(h, "voxelmap_import"); if (rc) return rc; }
-  if (mode != FVH_VOXEL_NDT_SUMS) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_import: the snapshot's accumulation mode is not the live map's (an NDT map takes FVH_VOXEL_NDT_SUMS snapshots only: VGICP sums are of another kind)");
-  return incmap_import(&h->e, h->target_vm, n, coords3, sums10, ages, resolution, mode, num_inserts, num_points);
-}
-int fvh_ndt_voxelmap_merge_from(fvh_ndt* h, fvh_ndt* other) {
-  CHECK_HANDLE(h);
-  { const int rc = ndt_map_refusal(h, "voxelmap_merge_from"); if (rc) return rc; }
-  if (!other) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_merge_from: null other handle");
-  if (other == h) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_merge_from: a map cannot be merged into itself");
-  if (other->e.device != h->e.device) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_merge_from: the two handles are on different devices");
-  if (other->e.sharded() || other->e.precision == FVH_COMPUTE_CUDA_COMPAT) return h->e.fail(FVH_ERR_UNSUPPORTED, "voxelmap_merge_from: the other handle is a multi-GPU / FVH_COMPUTE_CUDA_COMPAT handle");
-  if (other->in_flight()) return h->e.fail(FVH_ERR_BAD_STATE, "voxelmap_merge_from: an align_async is in flight on the other handle: call fvh_ndt_align_wait first");
-  { const int rc = ndt_map_live(h, "voxelmap_merge_from"); if (rc) return rc; }
-  if (!other->incremental()) return h->e.fail(FVH_ERR_BAD_STATE, "voxelmap_merge_from: the other handle has no live incremental map (fvh_ndt_map_begin)");
-  { const int rc = other->e.settle(); if (rc) return h->e.fail(rc, "voxelmap_merge_from: the other handle: " + other->e.err); }
-  for (hipEvent_t& ev : h->merge_ev) if (!ev) HIP_OR_FAIL(&h->e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  other->e.quiet = false;  // (its stream now holds a wait)
-  return incmap_merge_from(&h->e, h->target_vm, other->target_vm, other->e.stream, h->merge_ev[0], h->merge_ev[1]);
-}
-// The live map as the handle's target cloud (points only). The map stays the target MAP: the cloud is a snapshot OF it, not a cloud set
-// beside it -- target_newer is fvh_ndt_set_target_cloud*'s rule, and a cloud such a call left behind is gone now, so nothing is newer.
-int fvh_ndt_target_from_map(fvh_ndt* h, int min_points, int* num_points_out) {
-  CHECK_HANDLE(h);
-  { const int rc = ndt_map_live(h, "target_from_map"); if (rc) return rc; }
-  h->target_newer = false;
-  return incmap_to_cloud(&h->e, h->target_vm, min_points, h->target, false, false, num_points_out);
-}
-int fvh_ndt_get_num_target_points(const fvh_ndt* h, int* n) { if (!h || !n) return FVH_ERR_INVALID_ARGUMENT; *n = h->target.has_pts ? h->target.n : 0; return FVH_OK; }
-int fvh_ndt_get_target_points(fvh_ndt* h, float* xyz3) { CHECK_HANDLE(h); return get_points_host(&h->e, h->target, xyz3, "get_target_points"); }
+// ---- incremental target map, its snapshots, the map as the target cloud (namespace shared; NDT voxels: points only) ----
+int fvh_ndt_map_begin(fvh_ndt* h, int expected_voxels) { CHECK_HANDLE(h); return shared::map_begin(h, expected_voxels); }
+int fvh_ndt_map_insert_source(fvh_ndt* h, const double* T16) { CHECK_HANDLE(h); return shared::map_insert_source(h, T16); }
+int fvh_ndt_map_insert_cloud(fvh_ndt* h, const float* xyz, int n, int stride_floats, const double* T16, int on_device) { CHECK_HANDLE(h); return shared::map_insert_cloud(h, xyz, n, stride_floats, nullptr, T16, on_device); }
+int fvh_ndt_map_prune(fvh_ndt* h, const double* center3, double radius, int max_age, int* num_removed) { CHECK_HANDLE(h); return shared::map_prune(h, center3, radius, max_age, num_removed); }
+int fvh_ndt_map_get_info(fvh_ndt* h, int* incremental, int* num_voxels, int* capacity, int* num_inserts, long long* num_points, int* num_dropped) { CHECK_HANDLE(h); return shared::map_get_info(h, incremental, num_voxels, capacity, num_inserts, num_points, num_dropped); }
+int fvh_ndt_voxelmap_export(fvh_ndt* h, int* num_voxels, double* resolution, int* mode, int* num_inserts, long long* num_points, int* coords3, double* sums10, unsigned* ages) { CHECK_HANDLE(h); return shared::voxelmap_export(h, num_voxels, resolution, mode, num_inserts, num_points, coords3, sums10, ages); }
+int fvh_ndt_voxelmap_import(fvh_ndt* h, int n, const int* coords3, const double* sums10, const unsigned* ages, double resolution, int mode, int num_inserts, long long num_points) { CHECK_HANDLE(h); return shared::voxelmap_import(h, n, coords3, sums10, ages, resolution, mode, num_inserts, num_points); }
+int fvh_ndt_voxelmap_merge_from(fvh_ndt* h, fvh_ndt* other) { CHECK_HANDLE(h); return shared::voxelmap_merge_from(h, other); }
+int fvh_ndt_target_from_map(fvh_ndt* h, int min_points, int* num_points_out) { CHECK_HANDLE(h); return shared::target_from_map(h, min_points, num_points_out); }
+int fvh_ndt_get_num_target_points(const fvh_ndt* h, int* n) { return shared::get_num_target_points(h, n); }
+int fvh_ndt_get_target_points(fvh_ndt* h, float* xyz3) { CHECK_HANDLE(h); return shared::get_points_host(&h->e, h->target, xyz3, "get_target_points"); }
 static int ndt_ready(fvh_ndt* h) {
   if (!h->source.has_pts) return h->e.fail(FVH_ERR_BAD_STATE, "source cloud not set");
   if (!h->target_vm.valid) return h->e.fail(FVH_ERR_BAD_STATE, "target voxel map not built (create_voxelmaps)");
@@ -1698,8 +1701,8 @@ int fvh_ndt_adopt_prepared_source(fvh_ndt* h) {
 }
 int fvh_ndt_debug_set_voxel_hint(fvh_ndt* h, int which, int num_voxels) { CHECK_HANDLE(h); (which ? h->target_vm : h->source_vm).nv_hint = num_voxels; return FVH_OK; }
 int fvh_ndt_debug_get_table_capacity(fvh_ndt* h, int which, int* capacity) { CHECK_HANDLE(h); if (!capacity) return FVH_ERR_INVALID_ARGUMENT; *capacity = (int)(which ? h->target_vm : h->source_vm).capacity; return FVH_OK; }
-int fvh_ndt_set_lm_trace(fvh_ndt* h, int on) { CHECK_HANDLE(h); h->e.lm_trace_on = on != 0; return FVH_OK; }
-int fvh_ndt_get_lm_trace(fvh_ndt* h, int* n, double* rows6) { CHECK_HANDLE(h); return get_lm_trace(&h->e, n, rows6); }
+int fvh_ndt_set_lm_trace(fvh_ndt* h, int on) { CHECK_HANDLE(h); return shared::set_lm_trace(h, on); }
+int fvh_ndt_get_lm_trace(fvh_ndt* h, int* n, double* rows6) { CHECK_HANDLE(h); return shared::get_lm_trace(&h->e, n, rows6); }
 int fvh_ndt_fitness_score(fvh_ndt* h, const double* T, double max_range, double* score) { CHECK_HANDLE(h); return do_fitness(&h->e, h->source, h->target, T, max_range, score); }
 int fvh_ndt_get_num_voxels(fvh_ndt* h, int which, int* n) {
   CHECK_HANDLE(h);
@@ -1733,7 +1736,7 @@ int fvh_ndt_get_num_correspondences(fvh_ndt* h, int* n) {
   *n = c;
   return FVH_OK;
 }
-// offset-major then source element, invalid pairs removed (ndt_cuda.cu:142-161 builds the list with the functor of find_voxel_correspondences.cu:84-111)
+// (ndt_cuda.cu:142-161 builds the list with the functor of find_voxel_correspondences.cu:84-111)
 int fvh_ndt_get_voxel_correspondences(fvh_ndt* h, int* pairs) {
   CHECK_HANDLE(h);
   if (h->e.tile_n > 1) return h->e.fail(FVH_ERR_UNSUPPORTED, "correspondence getters: not on a tiled handle (only its tile's rows of the list exist)");
@@ -1753,53 +1756,27 @@ int fvh_ndt_get_voxel_correspondences(fvh_ndt* h, int* pairs) {
   std::vector<int> row_of;  // (P2D on a large cloud: rows by Morton position; D2D: by source-voxel index)
   rc = fetch_row_of_point(&h->e, h->source, nsrc, row_of);
   if (rc) return rc;
-  size_t w = 0;
-  for (int o = 0; o < h->e.n_off; o++)
-    for (int i = 0; i < nsrc; i++) {
-      const int b = corr[(size_t)row_of[(size_t)i] * h->e.n_off + o];
-      if (b < 0) continue;
-      pairs[2 * w] = i;
-      pairs[2 * w + 1] = h->target_vm.bucket_to_index[b];
-      w++;
-    }
+  shared::emit_voxel_pairs(&h->e, h->target_vm, corr, row_of, nsrc, pairs);
   return FVH_OK;
 }
-int fvh_ndt_profile_enable(fvh_ndt* h, int on) { CHECK_HANDLE(h); h->e.prof.on = on != 0; h->e.prof.cost_only = on == 2; return FVH_OK; }
-int fvh_ndt_profile_reset(fvh_ndt* h) { CHECK_HANDLE(h); HIP_OR_FAIL(&h->e, hipStreamSynchronize(h->e.stream)); h->e.prof.reset(); return FVH_OK; }
+int fvh_ndt_profile_enable(fvh_ndt* h, int on) { CHECK_HANDLE(h); return shared::profile_enable(h, on); }
+int fvh_ndt_profile_reset(fvh_ndt* h) { CHECK_HANDLE(h); return shared::profile_reset(h); }
 int fvh_ndt_profile_get(fvh_ndt* h, const char* cls, double* ms, int* n) { CHECK_HANDLE(h); return profile_get(&h->e, cls, ms, n); }
-int fvh_ndt_synchronize(fvh_ndt* h) { CHECK_HANDLE(h); HIP_OR_FAIL(&h->e, hipStreamSynchronize(h->e.stream)); h->e.gang_clear(); return FVH_OK; }
+int fvh_ndt_synchronize(fvh_ndt* h) { CHECK_HANDLE(h); return shared::synchronize(h); }
 int fvh_ndt_comm_init(fvh_ndt* h, const void* id, int nranks, int rank) {
   CHECK_HANDLE(h);
   if (h->e.tile_n > 1 && (h->e.tile_n != nranks || h->e.tile_rank != rank)) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "comm_init: rank / nranks differ from fvh_ndt_set_source_tile's");
   if (nranks > 1 && h->incremental()) return h->e.fail(FVH_ERR_BAD_STATE, "comm_init: an incremental target map is live (every rank would grow a private map); end it first (create_target_voxelmap / a new handle)");
   return comm_init(&h->e, id, nranks, rank);
 }
-int fvh_ndt_comm_destroy(fvh_ndt* h) { CHECK_HANDLE(h); if (h->e.comm) { g_rccl.CommDestroy(h->e.comm); h->e.comm = nullptr; } h->e.nranks = 1; h->e.rank = 0; return FVH_OK; }
+int fvh_ndt_comm_destroy(fvh_ndt* h) { CHECK_HANDLE(h); return h->e.comm_destroy(); }
 
 // ---- voxel-grid downsampling ----
-int fvh_voxelgrid_create(int device, fvh_voxelgrid** out) {
-  if (!out) return FVH_ERR_INVALID_ARGUMENT;
-  *out = nullptr;
-  auto* h = new (std::nothrow) fvh_voxelgrid();
-  if (!h) return FVH_ERR_HIP;
-  int rc = h->e.init(device, false);
-  if (rc) { fprintf(stderr, "fvh_voxelgrid_create: %s\n", h->e.err.c_str()); h->e.shutdown(); delete h; return rc; }
-  *out = h;
-  return FVH_OK;
-}
-int fvh_voxelgrid_destroy(fvh_voxelgrid* h) {
-  if (!h) return FVH_ERR_INVALID_ARGUMENT;
-  (void)hipSetDevice(h->e.device);
-  if (h->e.stream) (void)hipStreamSynchronize(h->e.stream);
-  h->d.release();
-  h->o.release();
-  h->e.shutdown();
-  delete h;
-  return FVH_OK;
-}
-const char* fvh_voxelgrid_last_error(const fvh_voxelgrid* h) { return h ? h->e.err.c_str() : "null handle"; }
-int fvh_voxelgrid_get_engine_params(fvh_voxelgrid* h, fvh_engine_params* out) { CHECK_HANDLE_HOST_ONLY(h); return get_engine_params(&h->e, out); }
-int fvh_voxelgrid_set_engine_params(fvh_voxelgrid* h, const fvh_engine_params* p) { CHECK_HANDLE(h); return set_engine_params(&h->e, p); }
+int fvh_voxelgrid_create(int device, fvh_voxelgrid** out) { return shared::create(device, out); }
+int fvh_voxelgrid_destroy(fvh_voxelgrid* h) { return shared::destroy(h); }
+const char* fvh_voxelgrid_last_error(const fvh_voxelgrid* h) { return shared::last_error(h); }
+int fvh_voxelgrid_get_engine_params(fvh_voxelgrid* h, fvh_engine_params* out) { CHECK_HANDLE_HOST_ONLY(h); return shared::get_engine_params(&h->e, out); }
+int fvh_voxelgrid_set_engine_params(fvh_voxelgrid* h, const fvh_engine_params* p) { CHECK_HANDLE(h); return shared::set_engine_params(&h->e, p); }
 // A filter that shares a registration handle's PREPARE stream goes where that handle's preparations go (Engine::feeder_stream): the main
 // stream while an LM grid that crowds the chip is in flight. For the length of the call only: the sharing itself stays.
 struct FilterStream {
@@ -1859,8 +1836,8 @@ int fvh_voxelgrid_device_points(fvh_voxelgrid* h, const float** d_xyz, int* n) {
   *n = h->d.out_n;
   return FVH_OK;
 }
-int fvh_voxelgrid_profile_enable(fvh_voxelgrid* h, int on) { CHECK_HANDLE(h); h->e.prof.on = on != 0; h->e.prof.cost_only = on == 2; return FVH_OK; }
-int fvh_voxelgrid_profile_reset(fvh_voxelgrid* h) { CHECK_HANDLE(h); HIP_OR_FAIL(&h->e, hipStreamSynchronize(h->e.stream)); h->e.prof.reset(); return FVH_OK; }
+int fvh_voxelgrid_profile_enable(fvh_voxelgrid* h, int on) { CHECK_HANDLE(h); return shared::profile_enable(h, on); }
+int fvh_voxelgrid_profile_reset(fvh_voxelgrid* h) { CHECK_HANDLE(h); return shared::profile_reset(h); }
 int fvh_voxelgrid_profile_get(fvh_voxelgrid* h, double* ms, int* n) { CHECK_HANDLE(h); return profile_get(&h->e, "downsample", ms, n); }
 
 // ---- range crop / outlier removal on the filter handle (host_outlier.inc.hpp, kernels_outlier.hpp) ----

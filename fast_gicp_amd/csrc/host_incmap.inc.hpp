@@ -7,6 +7,7 @@
 // everything that consumes a target map (launch_cost, the getters) reads it unchanged. The sums, stamps and the dirty list are its own
 // (VoxelMapDev::inc); VoxelMapDev::acc and its clean / dirty bookkeeping stay build_voxelmap's.
 // Everything is queued on the handle's main stream; the callers (CHECK_HANDLE) have ordered it after a pending side-stream build.
+// Whether a map is live is the callers' question too (fvh_capi.hip: map_live, asked once in front of every call below but incmap_begin).
 
 constexpr int INCMAP_DEFAULT_VOXELS = 16384;
 constexpr unsigned INCMAP_MIN_CAPACITY = 64;
@@ -54,7 +55,7 @@ int incmap_begin(Engine* e, VoxelMapDev& vm, double res, int mode, int expected_
   { int rc = incmap_prepare_side(e, vm, vm.cur, cap); if (rc) return rc; }
   HIP_OR_FAIL(e, hipMemsetAsync(vm.counters.p, 0, 2 * 16 * sizeof(int), e->stream));
   HIP_OR_FAIL(e, hipMemsetAsync(vm.inc.ctl.p, 0, 4 * sizeof(int), e->stream));
-  vm.inc.mode = mode == 2 ? 2 : (mode == 1 ? 1 : 0);  // (VGICP's ADDITIVE_WEIGHTED never reaches here as 1: fvh_vgicp_map_begin folds it into 0)
+  vm.inc.mode = mode == 2 ? 2 : (mode == 1 ? 1 : 0);  // (VGICP's ADDITIVE_WEIGHTED never reaches here as 1: fvh_vgicp::map_begin_mode folds it into 0)
   vm.inc.epoch = 0;
   vm.inc.num_points = 0;
   vm.inc.voxel_bound = 0;
@@ -129,7 +130,6 @@ int incmap_read_counts(Engine* e, VoxelMapDev& vm, int* counters3, int* ctl4) {
 // add cloud `c` (points + covariances) at pose T. Capacity is secured BEFORE the launch from a host-side upper bound of the voxel
 // count (every point could open a voxel): an insert can neither drop a point nor need to be redone.
 int incmap_insert(Engine* e, VoxelMapDev& vm, const CloudDev& c, const double* T16, const char* who) {
-  if (!vm.inc.live || !vm.valid) return e->fail(FVH_ERR_BAD_STATE, std::string(who) + ": no incremental map is live (fvh_vgicp_map_begin)");
   if (vm.inc.mode == 1 ? !c.has_pts : (!c.has_pts || !c.has_cov)) return e->fail(FVH_ERR_BAD_STATE, std::string(who) + (vm.inc.mode == 1 ? ": the cloud is not set" : ": the cloud needs points and covariances"));
   if (!T16) return e->fail(FVH_ERR_INVALID_ARGUMENT, std::string(who) + ": null pose");
   for (int i = 0; i < 16; i++)
@@ -187,7 +187,6 @@ int incmap_insert(Engine* e, VoxelMapDev& vm, const CloudDev& c, const double* T
 }
 
 int incmap_prune(Engine* e, VoxelMapDev& vm, const double* center3, double radius, int max_age, int* num_removed) {
-  if (!vm.inc.live || !vm.valid) return e->fail(FVH_ERR_BAD_STATE, "map_prune: no incremental map is live (fvh_vgicp_map_begin)");
   VmPrune p = incmap_no_prune(vm);
   if (center3) {
     if (!std::isfinite(center3[0]) || !std::isfinite(center3[1]) || !std::isfinite(center3[2]) || !(radius >= 0.0)) return e->fail(FVH_ERR_INVALID_ARGUMENT, "map_prune: centre must be finite and radius >= 0");
@@ -236,7 +235,6 @@ int incmap_secure(Engine* e, VoxelMapDev& vm, long long n, const char* who) {
 }
 
 int incmap_export(Engine* e, VoxelMapDev& vm, int* num_voxels, double* resolution, int* mode, int* num_inserts, long long* num_points, int* coords3, double* sums10, unsigned* ages) {
-  if (!vm.inc.live || !vm.valid) return e->fail(FVH_ERR_BAD_STATE, "voxelmap_export: no incremental map is live (fvh_vgicp_map_begin)");
   const bool rows = coords3 || sums10 || ages;
   if (rows && !(coords3 && sums10 && ages)) return e->fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_export: coords3, sums10 and ages go together (all NULL: the header only)");
   int cnt[3];
@@ -320,7 +318,6 @@ int incmap_add_rows(Engine* e, VoxelMapDev& vm, int n_rows, const int* d_coords,
 }
 
 int incmap_import(Engine* e, VoxelMapDev& vm, int n, const int* coords3, const double* sums10, const unsigned* ages, double resolution, int mode, int num_inserts, long long num_points) {
-  if (!vm.inc.live || !vm.valid) return e->fail(FVH_ERR_BAD_STATE, "voxelmap_import: no incremental map is live (fvh_vgicp_map_begin)");
   // everything is validated on the host before anything is queued: a refused import leaves the map as it was
   if (n < 0) return e->fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_import: n < 0");
   if ((long long)n > INCMAP_MAX_VOXELS) return e->fail(FVH_ERR_UNSUPPORTED, "voxelmap_import: more than 2^28 voxels");
@@ -362,8 +359,6 @@ int incmap_import(Engine* e, VoxelMapDev& vm, int n, const int* coords3, const d
 // `from` (a live map of another handle on the same device, stream from_stream) added into `vm`, device to device. The reads of `from` are
 // fenced on both sides: e's stream waits for what from_stream holds, and from_stream waits for the kernel.
 int incmap_merge_from(Engine* e, VoxelMapDev& vm, VoxelMapDev& from, hipStream_t from_stream, hipEvent_t ev_before, hipEvent_t ev_after) {
-  if (!vm.inc.live || !vm.valid) return e->fail(FVH_ERR_BAD_STATE, "voxelmap_merge_from: no incremental map is live (fvh_vgicp_map_begin)");
-  if (!from.inc.live || !from.valid) return e->fail(FVH_ERR_BAD_STATE, "voxelmap_merge_from: the other handle has no live incremental map (fvh_vgicp_map_begin)");
   if (!(from.res == vm.res)) return e->fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_merge_from: the two maps differ in resolution");
   if (from.inc.mode != vm.inc.mode) return e->fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_merge_from: the two maps differ in accumulation mode");
   HIP_OR_FAIL(e, hipEventRecord(ev_before, from_stream));

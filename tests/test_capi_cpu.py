@@ -160,3 +160,53 @@ def test_every_environment_knob_is_documented():
     named = set(re.findall(r"`(FVH_[A-Z_0-9]+)`", table))
     test_build_only = {"FVH_KNN_MODE", "FVH_RBF_MODE", "FVH_FIT_MODE", "FVH_GICP_NN_MODE"}
     assert read - test_build_only == named - {"FVH_LIB_PATH"}, (sorted(read - test_build_only - named), sorted(named - read))
+
+
+# handle-taking functions that do NOT answer a null handle with FVH_ERR_INVALID_ARGUMENT, by name, each with its reason (none: every
+# guard -- CHECK_HANDLE*, the `if (!h ...)` of the unguarded getters -- looks at the handle before anything else)
+_NULL_HANDLE_EXCEPTIONS = {}
+
+
+def _handle_taking_prototypes():
+    """(return type, name, [parameter type]) of every function in the header whose first parameter is a handle"""
+    hdr = open(os.path.join(util.ROOT, "include", "fast_vgicp_hip.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    out = []
+    for ret, name, params in re.findall(r"^(int|const char\*)\s+(fvh_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", hdr, flags=re.M | re.S):
+        params = [" ".join(p.split()) for p in params.split(",")]
+        if not re.match(r"(const )?fvh_(vgicp|ndt|voxelgrid)\* \w+$", params[0]):
+            continue
+        types = [p.rsplit(" ", 1)[0] if "*" not in p else "pointer" for p in params]
+        out.append((ret, name, types))
+    return out
+
+
+def test_every_entry_point_refuses_a_null_handle():
+    """Every handle-taking function the header declares, called with a null handle and zeros for everything else, returns
+    FVH_ERR_INVALID_ARGUMENT before it touches anything (no GPU needed: the guard comes first); *_last_error(NULL) is "null handle"."""
+    from fast_gicp_amd import build
+    lib = ctypes.CDLL(build.build_lib())  # (an instance of its own: no argtypes set by capi.load())
+    zero = {"pointer": lambda: ctypes.c_void_p(None), "int": lambda: ctypes.c_int(0), "unsigned": lambda: ctypes.c_uint(0), "double": lambda: ctypes.c_double(0.0),
+            "float": lambda: ctypes.c_float(0.0), "long long": lambda: ctypes.c_longlong(0), "unsigned long long": lambda: ctypes.c_ulonglong(0)}
+    protos = _handle_taking_prototypes()
+    names = {n for _, n, _ in protos}
+    assert len(protos) >= 170 and {"fvh_vgicp_align", "fvh_ndt_voxelmap_merge_from", "fvh_voxelgrid_get_scores", "fvh_vgicp_map_get_info"} <= names, len(protos)
+    assert set(_NULL_HANDLE_EXCEPTIONS) <= names
+    wrong = {}
+    for ret, name, types in protos:
+        fn = getattr(lib, name)
+        args = [zero[t]() for t in types]
+        if ret == "const char*":
+            fn.restype = ctypes.c_char_p
+            assert name.endswith("_last_error")
+            got = fn(*args)
+            if got != b"null handle":
+                wrong[name] = got
+            continue
+        fn.restype = ctypes.c_int
+        got = fn(*args)
+        if name in _NULL_HANDLE_EXCEPTIONS:
+            continue
+        if got != 1:  # FVH_ERR_INVALID_ARGUMENT
+            wrong[name] = got
+    assert not wrong, wrong
