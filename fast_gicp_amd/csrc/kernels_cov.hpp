@@ -1424,6 +1424,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
     for (int j = 0; j < 12; j++) Tl[j] = T12[j];
   }
   const float qx = transform_row_nofma(qv, Tl + 0), qy = transform_row_nofma(qv, Tl + 4), qz = transform_row_nofma(qv, Tl + 8);
+  // A transformed query that is not finite has no nearest point: every distance to it is NaN or +inf, and what the walk below would write is
+  // "no correspondence, best_out = +inf". The walk would not notice, though: point_box_sq takes fmaxf(0, fmaxf(NaN, NaN)) = 0 on a NaN axis and
+  // +inf on an infinite one, neither above the initial `best`, so the row would sweep EVERY tile of the target to say so (one NaN among 2,000
+  // queries in a 1.1M-point target: see HISTORY.md). It leaves here with the same output (tests/test_gpu_nn1_edges.py, the "bad" cloud). The
+  // whole row takes the branch together; the other rows of the wave go on.
+  if (!(fabsf(qx) < __builtin_inff() && fabsf(qy) < __builtin_inff() && fabsf(qz) < __builtin_inff())) {
+    if (rl == 0) {
+      if (corr) corr[__float_as_int(qv.w)] = -1;
+      if (best_out) best_out[q] = __builtin_inff();
+    }
+    return;
+  }
   unsigned long long best = 0x7f800000ffffffffull;  // (distance bits, original index): +inf and the largest index -- above every candidate, below every NaN distance (never taken)
   // Seed: between two LM transitions the pose moves by millimetres and nearly every point keeps its neighbour. The point this row found LAST
   // time is a candidate like any other -- its key under the NEW pose is an upper bound from the start, and the walk below visits only what
@@ -1452,9 +1464,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
   };
   // Boxes are visited NEAREST FIRST at both levels. In index order the walk sweeps whatever passes the bound of the moment: measured on the
   // bundled pair, 44 tiles per query pass the bound the first tile leaves (90th percentile: 156) where 5 pass the final one -- a query inside
-  // a 2 m tile box is often far from every point of it. A bound travels as its float bits (non-negative floats order like unsigned integers;
-  // a NaN bound -- a non-finite query -- lies above +inf and is never a candidate) with the box number in its low bits, so that a row
-  // minimum is an arg-min; the truncated mantissa bits only ever LOWER a bound (a box may be visited needlessly, never skipped wrongly).
+  // a 2 m tile box is often far from every point of it. A bound travels as its float bits (non-negative floats order like unsigned integers)
+  // with the box number in its low bits, so that a row minimum is an arg-min; the truncated mantissa bits only ever LOWER a bound (a box
+  // may be visited needlessly, never skipped wrongly). A finite query so far away that every squared distance overflows (1e30) still gets
+  // +inf bounds, none above the initial `best`: it sweeps the whole target and ends with no correspondence.
   const auto best_bits = [&]() __attribute__((always_inline)) { return (unsigned)(best >> 32); };
   // one super tile: its 64 tile boxes, four per lane (eight loads, one round trip), then tiles in ascending bound order until the
   // nearest remaining one lies beyond the row's minimum
@@ -1469,7 +1482,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
     }
     while (true) {
       const unsigned m = row_min_u32(min(min(key[0], key[1]), min(key[2], key[3])));
-      if ((m & ~63u) > best_bits()) break;  // (also the end of the list: ~0u; and a NaN bound: above +inf)
+      if ((m & ~63u) > best_bits()) break;  // (also the end of the list: ~0u)
       const int tl = (int)(m & 63u);
       sweep((sup << 6) + tl);
 #pragma unroll
@@ -1506,7 +1519,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
       const unsigned m = chunk_min();
       if (m < bk) { bk = m; s_first = cb + (int)(m & 255u); }
     }
-    s_first = min(s_first, nsuper - 1);  // (a non-finite query: every bound is NaN or the list is empty -- any super tile will do)
+    s_first = min(s_first, nsuper - 1);  // (stays inside the list whatever the bounds were)
   }
   process_super(s_first);
   // ---- then every other super tile that can still matter, nearest first within a chunk ----
