@@ -84,6 +84,12 @@ def load():
                 continue
             fn.argtypes = argtypes
             fn.restype = C.c_int
+        for name, argtypes in DESKEW_ARGTYPES.items():
+            fn = getattr(L, name, None)
+            if fn is None:  # (an older build of the ABI, as above)
+                continue
+            fn.argtypes = argtypes
+            fn.restype = C.c_int
         _LIB = L
     return _LIB
 
@@ -109,6 +115,16 @@ def _outlier_argtypes():
 
 
 OUTLIER_ARGTYPES = _outlier_argtypes()
+
+
+def _deskew_argtypes():
+    """fvh_voxelgrid_deskew[_strided|_device], as the header declares them"""
+    h, p, i, d = C.c_void_p, C.c_void_p, C.c_int, C.c_double
+    tail = [p, i, p, p, i, d, p]  # times, time_stride, knot_times, knot_poses, K, t_ref, out_n
+    return {"fvh_voxelgrid_deskew": [h, p, i] + tail, "fvh_voxelgrid_deskew_strided": [h, p, i, i] + tail, "fvh_voxelgrid_deskew_device": [h, p, i, i] + tail}
+
+
+DESKEW_ARGTYPES = _deskew_argtypes()
 
 
 def declared_symbols():
@@ -886,7 +902,7 @@ class VoxelGrid:
         self._check(self._lib.fvh_voxelgrid_profile_reset(self._h), "profile_reset")
 
     def profile_get(self, cls="downsample"):
-        """(total ms, launches) of one profile class of the filter's engine: "downsample", "sort", "knn", "outlier_count", "outlier_score", "compact" """
+        """(total ms, launches) of one profile class of the filter's engine: "downsample", "sort", "knn", "outlier_count", "outlier_score", "compact", "deskew" """
         ms, n = C.c_double(0), C.c_int(0)
         if cls == "downsample":
             self._check(self._lib.fvh_voxelgrid_profile_get(self._h, C.byref(ms), C.byref(n)), "profile_get")
@@ -937,6 +953,54 @@ class VoxelGrid:
     def remove_radius_outliers_device(self, d_ptr, n, radius=0.8, min_neighbors=2, stride=3):
         """The pointer may be this handle's own device_points(): stages chain on one handle."""
         return self._outlier_device("remove_radius_outliers", d_ptr, n, stride, float(radius), int(min_neighbors))
+
+    # ---- motion compensation of a sweep (fvh_voxelgrid_deskew): every point moved into the sensor frame of t_ref along the piecewise
+    # constant-twist trajectory through the knot poses; n points out, in input order. Run it FIRST in a chain: crop and voxel filter
+    # change the indexing the times refer to. ----
+    @staticmethod
+    def _knots(knot_times, knot_poses, t_ref):
+        tau = np.ascontiguousarray(knot_times, dtype=np.float64).reshape(-1)
+        T = np.asarray(knot_poses, dtype=np.float64).reshape(-1, 4, 4)
+        if len(T) != len(tau):
+            raise ValueError("deskew: %d knot times but %d knot poses" % (len(tau), len(T)))
+        T = np.ascontiguousarray(T.transpose(0, 2, 1))  # (K, 4, 4) row-major indexing -> the ABI's column-major matrices
+        if t_ref is None:
+            if len(tau) == 0:
+                raise ValueError("deskew: no knots")
+            t_ref = tau[-1]
+        return tau, T, float(t_ref)
+
+    def deskew(self, xyz, times, knot_times, knot_poses, t_ref=None, stride=3, time_stride=1):
+        """Host arrays in, (n, 3) float32 out. times: one float32 per point (time_stride 1), or None with stride 4 and time_stride 4:
+        xyzt rows, the time in the 4th float. knot_poses: (K, 4, 4), sensor-at-that-instant -> one fixed frame. t_ref None: knot_times[-1].
+        A point with a non-finite coordinate or time comes out as NaNs (crop_range drops it)."""
+        a = _f32(np.asarray(xyz).reshape(-1, stride))
+        tau, T, t_ref = self._knots(knot_times, knot_poses, t_ref)
+        n = C.c_int(0)
+        if times is None:
+            if stride != 4:
+                raise ValueError("deskew: times=None needs xyzt rows (stride 4)")
+            tp = C.c_void_p(a.__array_interface__["data"][0] + 12)
+        else:
+            t = _f32(times).reshape(-1)
+            if len(t) < (len(a) - 1) * int(time_stride) + 1 and len(a):
+                raise ValueError("deskew: %d times for %d points at time_stride %d" % (len(t), len(a), time_stride))
+            tp = _p(t)
+        if stride == 3:
+            rc = self._lib.fvh_voxelgrid_deskew(self._h, _p(a), len(a), tp, int(time_stride), _p(tau), _p(T), len(tau), t_ref, C.byref(n))
+        else:
+            rc = self._lib.fvh_voxelgrid_deskew_strided(self._h, _p(a), len(a), int(stride), tp, int(time_stride), _p(tau), _p(T), len(tau), t_ref, C.byref(n))
+        self._check(rc, "fvh_voxelgrid_deskew")
+        return self.get_points(n.value)
+
+    def deskew_device(self, d_xyz, n, d_times, knot_times, knot_poses, t_ref=None, stride=3, time_stride=1):
+        """Device pointers in (the knots stay host arrays); (device pointer to packed xyz, count) as filter_device returns them.
+        d_xyz may be this handle's own device_points()."""
+        tau, T, t_ref = self._knots(knot_times, knot_poses, t_ref)
+        m = C.c_int(0)
+        self._check(self._lib.fvh_voxelgrid_deskew_device(self._h, C.c_void_p(d_xyz), int(n), int(stride), C.c_void_p(d_times), int(time_stride), _p(tau), _p(T), len(tau), t_ref,
+                                                          C.byref(m)), "fvh_voxelgrid_deskew_device")
+        return self.device_points()
 
     def device_points(self):
         """(device pointer to the packed xyz of the last output, count)"""

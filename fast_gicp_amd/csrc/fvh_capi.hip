@@ -26,6 +26,7 @@
 #include "kernels_cov.hpp"
 #include "kernels_downsample.hpp"
 #include "kernels_outlier.hpp"
+#include "kernels_deskew.hpp"
 #include "kernels_peer.hpp"
 #include "kernels_sort.hpp"
 #include "kernels_voxelmap.hpp"
@@ -450,6 +451,7 @@ inline void pose_to_rowmajor12f(const double* T16, float* T12) {  // what the se
 #include "host_gicp.inc.hpp"
 #include "host_downsample.inc.hpp"
 #include "host_outlier.inc.hpp"
+#include "host_deskew.inc.hpp"
 
 }  // namespace
 
@@ -649,12 +651,13 @@ struct fvh_voxelgrid {
   Engine e;
   DownsampleDev d;
   OutlierDev o;  // side outputs of crop_range / remove_*_outliers (host_outlier.inc.hpp)
+  DeskewDev k;   // segment records and times of fvh_voxelgrid_deskew (host_deskew.inc.hpp)
   bool in_flight() const { return false; }  // (a filter has no pipeline: CHECK_HANDLE never refuses on it)
   static constexpr const char* prefix = "fvh_voxelgrid";
   static constexpr bool gang_kernels = false;          // a filter never launches a persistent / cooperative kernel
   static constexpr bool side_stream_first = false;     // (it has no side stream of its own)
   int created() { return FVH_OK; }
-  void release_all() { d.release(); o.release(); }
+  void release_all() { d.release(); o.release(); k.release(); }
 };
 
 // CHECK_HANDLE_SOURCE_CHAIN: the calls that only touch the SOURCE cloud -- they may run beside a target-map build on the side
@@ -1855,6 +1858,14 @@ int fvh_voxelgrid_remove_radius_outliers_device(fvh_voxelgrid* h, const float* d
 #undef FVH_OUTLIER_CALL
 int fvh_voxelgrid_get_kept_indices(fvh_voxelgrid* h, int* idx) { CHECK_HANDLE(h); return outlier_get_kept(&h->e, h->d, h->o, idx); }
 int fvh_voxelgrid_get_scores(fvh_voxelgrid* h, float* scores, double* threshold) { CHECK_HANDLE(h); return outlier_get_scores(&h->e, h->o, scores, threshold); }
+
+// ---- motion compensation of a sweep on the filter handle (host_deskew.inc.hpp, kernels_deskew.hpp) ----
+#define FVH_DESKEW_CALL(xyz, stride, on_device, times) \
+  CHECK_HANDLE(h); FilterStream fs(&h->e); if (fs.rc) return fs.rc; return deskew(&h->e, h->d, h->o, h->k, xyz, n, stride, on_device, times, time_stride, knot_times, knot_poses, K, t_ref, out_n)
+int fvh_voxelgrid_deskew(fvh_voxelgrid* h, const float* xyz, int n, const float* times, int time_stride, const double* knot_times, const double* knot_poses, int K, double t_ref, int* out_n) { FVH_DESKEW_CALL(xyz, 3, false, times); }
+int fvh_voxelgrid_deskew_strided(fvh_voxelgrid* h, const float* xyz, int n, int stride, const float* times, int time_stride, const double* knot_times, const double* knot_poses, int K, double t_ref, int* out_n) { FVH_DESKEW_CALL(xyz, stride, false, times); }
+int fvh_voxelgrid_deskew_device(fvh_voxelgrid* h, const float* d_xyz, int n, int stride, const float* d_times, int time_stride, const double* knot_times, const double* knot_poses, int K, double t_ref, int* out_n) { FVH_DESKEW_CALL(d_xyz, stride, true, d_times); }
+#undef FVH_DESKEW_CALL
 int fvh_voxelgrid_profile_get_class(fvh_voxelgrid* h, const char* kernel_class, double* total_ms, int* launches) { CHECK_HANDLE(h); return profile_get(&h->e, kernel_class, total_ms, launches); }
 
 }  // extern "C"

@@ -167,6 +167,30 @@ static py::object remove_outliers_device(const Points& points, const std::string
   return filtered_result(vg, rc, n, return_indices, stat ? "fvh_voxelgrid_remove_statistical_outliers" : "fvh_voxelgrid_remove_radius_outliers");
 }
 
+// motion compensation of a sweep on the device (fvh_voxelgrid_deskew): every point into the sensor frame of t_ref along the trajectory
+// through the knot poses ((K, 4, 4), sensor-at-that-instant -> one fixed frame); (n, 3) out, input order
+static py::array_t<double> deskew_device(const Points& points, const py::array_t<double, py::array::c_style | py::array::forcecast>& times,
+                                         const py::array_t<double, py::array::c_style | py::array::forcecast>& knot_times, const Mat4& knot_poses, const py::object& t_ref, int device) {
+  auto cloud = numpy2cloud(points);
+  const std::vector<float> xyz = detail::pack_xyz(*cloud);
+  if (times.ndim() != 1 || (size_t)times.shape(0) != cloud->size()) throw std::invalid_argument("times must be an (N,) array, one per point");
+  if (knot_times.ndim() != 1) throw std::invalid_argument("knot_times must be a (K,) array");
+  if (knot_poses.ndim() != 3 || knot_poses.shape(0) != knot_times.shape(0) || knot_poses.shape(1) != 4 || knot_poses.shape(2) != 4) throw std::invalid_argument("knot_poses must be a (K, 4, 4) array");
+  const int K = (int)knot_times.shape(0);
+  if (K < 1) throw std::invalid_argument("no knots");
+  std::vector<float> t(cloud->size());
+  for (size_t i = 0; i < t.size(); i++) t[i] = (float)times.data()[i];
+  std::vector<double> poses((size_t)16 * K);  // column-major, as the ABI takes them
+  auto r = knot_poses.unchecked<3>();
+  for (int k = 0; k < K; k++) for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) poses[(size_t)16 * k + j * 4 + i] = r(k, i, j);
+  const double ref = t_ref.is_none() ? knot_times.data()[K - 1] : t_ref.cast<double>();
+  fvh_voxelgrid* vg = nullptr;
+  detail::check(fvh_voxelgrid_create(device, &vg), "fvh_voxelgrid_create", "cannot create the HIP engine (no GPU? there is no CPU fallback)");
+  int n = 0;
+  const int rc = fvh_voxelgrid_deskew(vg, xyz.data(), (int)cloud->size(), t.data(), 1, knot_times.data(), poses.data(), K, ref, &n);
+  return filtered_result(vg, rc, n, false, "fvh_voxelgrid_deskew").cast<py::array_t<double>>();
+}
+
 // align_points, main.cpp:64-150. "VGICP" (the CPU FastVGICP in the reference, main.cpp:102-108) runs on the same GPU engine in
 // its fp64 arithmetic WITH k_correspondences honoured (class FastVGICP of registration.hpp; "VGICP_CUDA" ignores it like the
 // reference's FastVGICPCuda: k = 20); "GICP" (nearest-point correspondences, no voxels) runs on the device too.
@@ -300,6 +324,8 @@ PYBIND11_MODULE(pygicp, m) {
   m.def("remove_outliers_device", &remove_outliers_device, "statistical (mean_k, stddev_mul) or radius (radius, min_neighbors) outlier removal on the GPU; kept points in input order",
         py::arg("points"), py::arg("method") = "STATISTICAL", py::arg("mean_k") = 20, py::arg("stddev_mul") = 1.0, py::arg("radius") = 0.8, py::arg("min_neighbors") = 2,
         py::arg("return_indices") = false, py::arg("device") = 0);
+  m.def("deskew_device", &deskew_device, "motion-compensate a sweep on the GPU: points (n, 3) with one time each, moved along the trajectory through the knot poses into the sensor frame of t_ref",
+        py::arg("points"), py::arg("times"), py::arg("knot_times"), py::arg("knot_poses"), py::arg("t_ref") = py::none(), py::arg("device") = 0);
   m.def("align_points", &align_points, "align two point sets", py::arg("target"), py::arg("source"), py::arg("method") = "VGICP_CUDA", py::arg("downsample_resolution") = -1.0,
         py::arg("k_correspondences") = 15, py::arg("max_correspondence_distance") = std::numeric_limits<double>::max(), py::arg("voxel_resolution") = 1.0,
         py::arg("num_threads") = 0, py::arg("neighbor_search_method") = "DIRECT1", py::arg("neighbor_search_radius") = 1.5, py::arg("initial_guess") = identity4());

@@ -598,7 +598,7 @@ int fvh_voxelgrid_device_points(fvh_voxelgrid* h, const float** d_xyz, int* n);
 int fvh_voxelgrid_profile_enable(fvh_voxelgrid* h, int on);
 int fvh_voxelgrid_profile_reset(fvh_voxelgrid* h);
 int fvh_voxelgrid_profile_get(fvh_voxelgrid* h, double* total_ms, int* launches);
-int fvh_voxelgrid_profile_get_class(fvh_voxelgrid* h, const char* kernel_class, double* total_ms, int* launches); /* any class of the filter's engine: "downsample", "sort", "knn", "outlier_count", "outlier_score", "compact" */
+int fvh_voxelgrid_profile_get_class(fvh_voxelgrid* h, const char* kernel_class, double* total_ms, int* launches); /* any class of the filter's engine: "downsample", "sort", "knn", "outlier_count", "outlier_score", "compact", "deskew" */
 
 /* ---- range crop, statistical and radius outlier removal (no counterpart in the reference's cores: the stages a LiDAR front end runs
  * around the voxel filter -- the origin / range filter of src/align.cpp:127-133, pcl::StatisticalOutlierRemoval,
@@ -639,6 +639,33 @@ int fvh_voxelgrid_remove_radius_outliers_strided(fvh_voxelgrid* h, const float* 
 int fvh_voxelgrid_remove_radius_outliers_device(fvh_voxelgrid* h, const float* d_xyz, int n, int stride_floats, double radius, int min_neighbors, int* out_n);
 int fvh_voxelgrid_get_kept_indices(fvh_voxelgrid* h, int* idx /* out_n ints, host */);
 int fvh_voxelgrid_get_scores(fvh_voxelgrid* h, float* scores /* n floats (the INPUT size), host, may be NULL */, double* threshold /* may be NULL */);
+
+/* ---- motion compensation ("deskew") of one sweep (no counterpart in the reference: the KITTI odometry scans it runs on are untwisted by
+ * the dataset; a live driver delivers points taken over ~0.1 s of vehicle motion) ----
+ * Input: n points (float32 xyz), one float32 time per point t_i = times[i * time_stride] (a separate array: time_stride 1; xyzt rows:
+ * times = xyz + 3, time_stride 4), K knots (2 <= K <= 64) with times tau[0] < ... < tau[K-1] (fp64, finite) and poses T[0..K-1]
+ * (knot_poses: K consecutive 4x4 double COLUMN-MAJOR matrices, sensor-at-that-instant -> one fixed frame), and a reference time t_ref
+ * (finite fp64). A knot pose must be finite, as fvh_*_map_insert_source asks of its pose, and -- a logarithm is taken of it -- a rigid
+ * motion: last row (0, 0, 0, 1) to 1e-9, |R^T R - I| <= 1e-6 entrywise, det R > 0.
+ * Trajectory: xi_j = log(T[j]^-1 * T[j+1]) (SE(3) logarithm, rotation part omega_j, translation part v_j; rotation-first exponential
+ * exp(omega, v) = {exp(omega), V(omega) v}), computed once on the host in fp64. For a time x: j(x) = the largest j with tau[j] <= x,
+ * clamped to [0, K-2]; s = (x - tau[j]) / (tau[j+1] - tau[j]); T(x) = T[j] * exp(s * xi_j). s outside [0, 1] on the end segments
+ * EXTRAPOLATES at that segment's constant twist (drivers overshoot the sweep by a few points).
+ * Output: p'_i = float32( T(t_ref)^-1 * T((double)t_i) * (double)p_i ), everything before the final cast in fp64; out_n = n, input order.
+ * The output is the handle's output state exactly as after a crop (packed xyz and {x, y, z, 0}): fvh_voxelgrid_get_points,
+ * _device_points, fvh_ndt_{set_source,set_target,prepare_source}_cloud_from_voxelgrid and a following crop_range_device / filter_device on
+ * the handle's own output pointer work on it unchanged. fvh_voxelgrid_get_kept_indices / _get_scores answer FVH_ERR_BAD_STATE after it.
+ * The input xyz may be the handle's own fvh_voxelgrid_device_points() (it is copied before the output is written).
+ * A point whose time or any coordinate is not finite comes out as three NaNs; it is not refused: crop_range is the stage that drops
+ * non-finite points, and deskew -> crop_range is the intended chain (deskew FIRST: crop and voxel filter change the indexing of the times).
+ * Refused with FVH_ERR_INVALID_ARGUMENT and out_n = 0: K outside [2, 64]; knot times not finite or not strictly increasing; a non-rigid
+ * knot pose; a segment whose relative rotation angle exceeds pi - 1e-6 (the logarithm is not unique there); non-finite t_ref; null
+ * pointers with n > 0 (null knot arrays at any n); stride not 3 or 4; time_stride < 1. n == 0: out_n = 0, FVH_OK.
+ * _device: d_xyz and d_times are device memory; the knot arrays are always host memory. All three forms run on the stream the handle
+ * currently works on (sharing as for the other filters) and synchronise it before returning. Profile class: "deskew". */
+int fvh_voxelgrid_deskew(fvh_voxelgrid* h, const float* xyz, int n, const float* times, int time_stride, const double* knot_times, const double* knot_poses, int K, double t_ref, int* out_n);
+int fvh_voxelgrid_deskew_strided(fvh_voxelgrid* h, const float* xyz, int n, int stride_floats, const float* times, int time_stride, const double* knot_times, const double* knot_poses, int K, double t_ref, int* out_n);
+int fvh_voxelgrid_deskew_device(fvh_voxelgrid* h, const float* d_xyz, int n, int stride_floats, const float* d_times, int time_stride, const double* knot_times, const double* knot_poses, int K, double t_ref, int* out_n);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,205 @@
+"""Motion compensation without a GPU: the numpy twin (tests/deskew_ref.py) against its own definition -- a series matrix exponential, the
+closed form through numpy's inverse, a second fp64 formulation -- the public surface (header, exported symbols, ctypes argtypes, the
+Python layers) and the new kernel's resources."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import deskew_ref as R
+from tests import util
+
+
+@pytest.fixture(scope="module")
+def cloud():
+    from fast_gicp_amd import preprocess
+    p = np.ascontiguousarray(preprocess.bundled_pair(util.DATA)[1][:4099])
+    assert p.shape == (4099, 3) and p.dtype == np.float32
+    return p
+
+
+def _expm(X):
+    """matrix exponential by scaling and squaring of the Taylor series: shares nothing with the twin's closed forms"""
+    k = max(0, int(np.ceil(np.log2(max(np.abs(X).sum(axis=1).max(), 1e-300)))) + 4)
+    A = X / 2.0 ** k
+    E, term = np.eye(len(X)), np.eye(len(X))
+    for i in range(1, 30):
+        term = term @ A / i
+        E = E + term
+    for _ in range(k):
+        E = E @ E
+    return E
+
+
+def _twist_matrix(w, v):
+    X = np.zeros((4, 4))
+    X[:3, :3], X[:3, 3] = R.hat(w), v
+    return X
+
+
+TWISTS = [([0.0, 0.0, 0.0], [0.3, -1.0, 0.2]), ([1e-12, 0.0, 0.0], [1.0, 2.0, -3.0]), ([3e-11, -2e-11, 1e-11], [0.5, 0.5, 0.5]), ([0.01, -0.02, 0.03], [1.5, 0.1, -0.2]),
+          ([0.5, 0.4, -0.3], [1.0, -2.0, 0.5]), ([1.8, 0.0, 2.4], [0.2, 0.3, 0.4]), ([0.0, -3.0, 0.0], [1.0, 1.0, 1.0]), ([1.9, 1.9, -1.6], [0.0, 0.0, 2.0])]
+
+
+def test_exponential_and_logarithm_against_a_series_exponential():
+    for w, v in TWISTS:
+        w, v = np.array(w), np.array(v)
+        E = R.se3_exp(w, v)
+        assert np.abs(E - _expm(_twist_matrix(w, v))).max() <= 2e-14, (w, v)
+        assert np.abs(E[:3, :3].T @ E[:3, :3] - np.eye(3)).max() <= 1e-15 * 8
+        w2, v2 = R.se3_log(E)
+        assert np.abs(w2 - w).max() <= 1e-14 and np.abs(v2 - v).max() <= 1e-14, (w, v, w2, v2)
+    assert np.array_equal(R.se3_exp(np.zeros(3), np.zeros(3)), np.eye(4))
+    w0, v0 = R.se3_log(np.eye(4))
+    assert not w0.any() and not v0.any()
+
+
+def test_identity_motion_returns_the_input_bits(cloud):
+    t = R.azimuth_times(cloud)
+    for K in (2, 3, 64):
+        tau, T = R.identity_trajectory(K)
+        for t_ref in (None, 0.0, 0.05, -1.0, 7.0):
+            out64, out32 = R.deskew(cloud, t, tau, T, t_ref)
+            assert np.array_equal(out32.view(np.uint32), cloud.view(np.uint32)), (K, t_ref)
+            assert np.array_equal(out64, cloud.astype(np.float64))
+
+
+def test_trajectory_meets_its_knots_and_is_continuous_across_them():
+    for K, seed in ((2, 1), (3, 2), (40, 3), (64, 4)):
+        tau, T = R.random_trajectory(K, seed)
+        wv = R.twists(T)
+        span = np.abs(np.linalg.norm(T[-1][:3, 3] - T[0][:3, 3]))
+        assert 0.5 < span < 3.0, span
+        for j in range(K):
+            assert np.abs(R.pose_at(tau, T, tau[j], wv) - T[j]).max() <= 1e-14, (K, j)
+        for j in range(1, K - 1):  # both sides of an inner knot: within the distance travelled in 1e-12 s (30 m/s, 1 rad/s with a 60 m lever)
+            eps = 1e-12
+            lo, hi = R.pose_at(tau, T, tau[j] - eps, wv), R.pose_at(tau, T, tau[j] + eps, wv)
+            assert R.segment(tau, tau[j] - eps) == j - 1 and R.segment(tau, tau[j] + eps) == j and R.segment(tau, tau[j]) == j
+            assert np.abs(lo - T[j]).max() <= 1e-10 and np.abs(hi - T[j]).max() <= 1e-10 and np.abs(hi - lo).max() <= 1e-10, (K, j)
+
+
+def test_reference_time_at_the_end_knots_equals_the_closed_form(cloud):
+    """t_ref on the first / last knot: p' = T[k]^-1 T(t) p with numpy's general inverse and one 4x4 product chain per point"""
+    sub = cloud[::41]
+    t = R.azimuth_times(sub)
+    for K, seed in ((2, 5), (3, 6), (40, 7)):
+        tau, T = R.random_trajectory(K, seed)
+        wv = R.twists(T)
+        M = R.scale(sub, T)
+        for k in (0, K - 1):
+            out64, _ = R.deskew(sub, t, tau, T, tau[k])
+            left = np.linalg.inv(T[k])
+            want = np.array([(left @ R.pose_at(tau, T, float(x), wv) @ np.append(p.astype(np.float64), 1.0))[:3] for p, x in zip(sub, t)])
+            assert np.abs(out64 - want).max() <= 1e-12 * M, (K, k, np.abs(out64 - want).max())
+        assert np.array_equal(R.deskew(sub, t, tau, T, None)[0], R.deskew(sub, t, tau, T, tau[-1])[0])
+
+
+def test_extrapolation_is_the_end_segments_constant_twist():
+    for K, seed in ((2, 8), (3, 9), (40, 10)):
+        tau, T = R.random_trajectory(K, seed)
+        w, v = R.twists(T)
+        for d in (1e-4, 0.003, 0.05):
+            s = d / (tau[-1] - tau[-2])
+            want = T[-1] @ _expm(s * _twist_matrix(w[-1], v[-1]))
+            assert np.abs(R.pose_at(tau, T, tau[-1] + d, (w, v)) - want).max() <= 1e-13, (K, d)
+            s = -d / (tau[1] - tau[0])
+            want = T[0] @ _expm(s * _twist_matrix(w[0], v[0]))
+            assert np.abs(R.pose_at(tau, T, tau[0] - d, (w, v)) - want).max() <= 1e-13, (K, d)
+    assert list(R.segment(tau, np.array([-1.0, tau[0], tau[1], tau[-2], tau[-1], 9.0]))) == [0, 0, 1, K - 2, K - 2, K - 2]
+
+
+def test_deskew_undoes_skew(cloud):
+    t = R.azimuth_times(cloud)
+    assert t.dtype == np.float32 and t.min() >= 0 and t.max() <= np.float32(R.SWEEP)
+    for K, seed, t_ref in ((2, 11, None), (3, 12, 0.0), (40, 13, 0.05), (40, 13, None)):
+        tau, T = R.random_trajectory(K, seed)
+        bent64 = R.skew(cloud, t, tau, T, t_ref)
+        moved = np.abs(bent64 - cloud).max()
+        assert 0.3 < moved < 10.0, moved  # the sweep is bent by about the distance travelled
+        back64, _ = R.deskew(bent64.astype(np.float32), t, tau, T, t_ref)
+        M = R.scale(cloud, T)
+        # the skew's float32 cast carried through a rotation (<= sqrt(3) / 2 ulp) and this comparison's own fp64 noise
+        assert np.abs(back64 - cloud).max() <= np.sqrt(3.0) / 2.0 * np.spacing(np.float32(M)) + 1e-12 * M, (K, np.abs(back64 - cloud).max())
+        exact = R._moved(bent64, t.astype(np.float64), tau, T, *R.twists(T), R.rigid_inv(R.pose_at(tau, T, tau[-1] if t_ref is None else t_ref)))
+        assert np.abs(exact - cloud).max() <= 1e-12 * M
+
+
+def test_two_fp64_formulations_agree_far_inside_the_gpu_tolerance(cloud):
+    """The 1e-12 M term of the GPU test's tolerance is fp64 evaluation-order noise: Rodrigues in cross products (the twin, the kernel)
+    against half-angle quaternion + V matrix + numpy's inverse stay orders below it, and round to the same float32."""
+    t = R.azimuth_times(cloud)
+    for K, seed in ((2, 14), (3, 15), (40, 16)):
+        tau, T = R.random_trajectory(K, seed)
+        a, a32 = R.deskew(cloud, t, tau, T)
+        b = R.deskew_quat(cloud, t, tau, T)
+        M = R.scale(cloud, T)
+        print("K=%d M=%.1f max |rodrigues - quaternion| = %.2e, float32 casts differing: %d of %d" % (K, M, np.abs(a - b).max(), (a32 != b.astype(np.float32)).sum(), a32.size))
+        assert np.abs(a - b).max() <= 1e-14 * M
+        assert (a32 != b.astype(np.float32)).sum() * 1000 <= a32.size
+        assert np.all(np.abs(b - a) <= R.tolerance(a, cloud, T))
+
+
+def test_non_finite_rows_come_out_as_nans_and_leave_the_others_alone(cloud):
+    p, t = cloud[:300].copy(), R.azimuth_times(cloud[:300]).copy()
+    tau, T = R.random_trajectory(3, 17)
+    clean = R.deskew(p, t, tau, T)[1]
+    p[0, 1], p[63, 0], t[64], p[299, 2], t[299] = np.nan, np.inf, -np.inf, -np.inf, np.nan
+    out = R.deskew(p, t, tau, T)[1]
+    bad = np.zeros(300, bool)
+    bad[[0, 63, 64, 299]] = True
+    assert np.isnan(out[bad]).all() and np.array_equal(out[~bad].view(np.uint32), clean[~bad].view(np.uint32))
+
+
+# ---- the public surface ----
+NEW = ["fvh_voxelgrid_deskew", "fvh_voxelgrid_deskew_strided", "fvh_voxelgrid_deskew_device"]
+
+
+def test_header_library_and_upper_layers_expose_deskew():
+    from fast_gicp_amd import build, capi
+    declared = capi.declared_symbols()
+    lib = build.build_lib()
+    have = set(l.split()[-1] for l in subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True).stdout.splitlines() if l.split())
+    hdr = re.sub(r"/\*.*?\*/", "", open(build.HEADER).read(), flags=re.S)
+    ctype = {"int": C.c_int, "double": C.c_double}
+    L = capi.load()
+    assert sorted(capi.DESKEW_ARGTYPES) == sorted(NEW)
+    for name in NEW:
+        assert name in declared and name in have, name
+        m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, hdr)
+        assert m, name
+        want = [C.c_void_p if "*" in arg else ctype[arg.split()[0]] for arg in (a.strip() for a in m.group(1).split(","))]
+        assert capi.DESKEW_ARGTYPES[name] == want, (name, m.group(1))
+        assert list(getattr(L, name).argtypes) == want and getattr(L, name).restype is C.c_int
+    for meth in ("deskew", "deskew_device"):
+        assert callable(getattr(capi.VoxelGrid, meth, None)), meth
+    assert '"deskew"' in open(build.HEADER).read().split("fvh_voxelgrid_profile_get_class", 1)[1].split("\n", 1)[0]
+    csrc = os.path.join(util.ROOT, "fast_gicp_amd", "csrc")
+    src, host, capi_src = (open(os.path.join(csrc, f)).read() for f in ("kernels_deskew.hpp", "host_deskew.inc.hpp", "fvh_capi.hip"))
+    assert re.search(r"__global__[^;{]*\bdeskew_points_kernel\b", src) and re.search(r"\bdeskew_points_kernel<<<", host)
+    assert host.index("upload_cloud(") < host.index("d.out.ensure(")  # the input is widened before the output state is touched
+    assert capi_src.index('#include "host_outlier.inc.hpp"') < capi_src.index('#include "host_deskew.inc.hpp"')
+    for f in ("kernels_deskew.hpp", "host_deskew.inc.hpp"):
+        assert any(s.endswith(os.sep + f) for s in build.SOURCES), f
+    pyg = open(os.path.join(util.ROOT, "fast_gicp_amd", "python", "pygicp.cpp")).read()
+    assert 'm.def("deskew_device"' in pyg
+
+
+def test_the_one_new_kernel_fits_its_budget():
+    """one point per lane, launch-bound: all that is asked of the kernel is no spill, no scratch, and the 63 segment records in LDS"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(util.ROOT, "tools", "kernel_resources.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    res = mod.kernel_resources()
+    hit = {k: v for k, v in res.items() if "deskew" in k}
+    assert len(hit) == 1, sorted(hit)
+    (name, v), = hit.items()
+    print(name, v)
+    assert v["vgpr_spill"] == 0 and v["sgpr_spill"] == 0 and v["scratch"] == 0 and 63 * 160 <= v["lds"] <= 16384, v
+    # the names existing tests select kernels by do not occur in it
+    assert not any(s in name.split("(")[0] for s in ("knn_tiled1_kernel", "nn1_rows_kernel", "cov_rbf1_kernel", "cov_from_neighbors_kernel", "vm_accumulate_kernel", "sort_coop_kernel",
+                                                      "cost_kernel", "outlier", "crop_flag"))
