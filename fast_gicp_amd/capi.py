@@ -274,6 +274,26 @@ class _IncrementalMap:
         write_map_file(path, self.map_export())
 
 
+class _PosedMap:
+    """A live map added under a rigid pose, and re-anchored in place (include/fast_vgicp_hip.h: fvh_{vgicp,ndt}_posed_merge_from /
+    _transform_map): mixed into VGICPMapCore and NDTMapCore, the handle classes for scan-to-map work."""
+
+    def map_merge_from_posed(self, other, T):
+        """ADD the live map of `other`, seen from pose T (4x4, other's frame -> this map's frame, rigid), into this one on the device: every
+        voxel's sums are transformed in closed form and go to the voxel of their own mean (fvh_*_posed_merge_from).
+        -> rows skipped because their mean left the key range"""
+        skipped, t = C.c_int(0), _colmajor16(T)
+        self._call("posed_merge_from", other.h, _p(t), C.byref(skipped))
+        return skipped.value
+
+    def map_transform(self, T):
+        """Re-anchor the live map by the rigid pose T in place (fvh_*_transform_map): what map_begin on a fresh handle +
+        map_merge_from_posed(this, T) would hold; insert count, num_points and ages stay. -> rows skipped"""
+        skipped, t = C.c_int(0), _colmajor16(T)
+        self._call("transform_map", _p(t), C.byref(skipped))
+        return skipped.value
+
+
 class _MapTarget:
     """The live incremental map as the handle's target cloud (include/fast_vgicp_hip.h: fvh_{vgicp,ndt}_target_from_map, _get_target_points):
     mixed into VGICPMapCore and NDTMapCore, the handle classes for scan-to-map work."""
@@ -805,7 +825,7 @@ class VGICPCore(_Core, _IncrementalMap):
         return n.value
 
 
-class VGICPMapCore(VGICPCore, _MapTarget):
+class VGICPMapCore(VGICPCore, _MapTarget, _PosedMap):
     """A VGICP handle for scan-to-map work: VGICPCore (which has the map_* calls) + target_from_map / get_target_points, on the same C handle
     type -- as NDTMapCore is to NDTCore."""
 
@@ -1114,7 +1134,7 @@ class NDTCore(_Core):
         return coords, num, means, covs
 
 
-class NDTMapCore(NDTCore, _IncrementalMap, _MapTarget):
+class NDTMapCore(NDTCore, _IncrementalMap, _MapTarget, _PosedMap):
     """An NDT handle with the calls of its incremental target map (include/fast_vgicp_hip.h: fvh_ndt_map_* / fvh_ndt_voxelmap_*): map_begin,
     map_insert_source, map_prune, map_info, map_export, map_import, map_merge_from, map_save come from _IncrementalMap as on VGICPCore; NDT
     voxels take points only. Everything else is NDTCore's, on the same C handle type."""
@@ -1127,6 +1147,11 @@ class NDTMapCore(NDTCore, _IncrementalMap, _MapTarget):
         else:
             a = _f32(xyz)
             self._call("map_insert_cloud", _p(a), len(a), 3, _p(t), 0)
+
+    def debug_skipped_points(self):
+        n = C.c_int(0)
+        self._call("debug_get_skipped_points", C.byref(n))
+        return n.value
 
     def map_load(self, path):
         """Add the file's map (mode VOXEL_NDT_SUMS) into the live map; a handle with no live map takes the file's resolution and starts one sized for it."""

@@ -846,21 +846,46 @@ int voxelmap_import(H* h, int n, const int* coords3, const double* sums10, const
   if (H::foreign_snapshot && mode != incmap_snapshot_mode(h->target_map())) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, H::foreign_snapshot);
   return incmap_import(&h->e, h->target_map(), n, coords3, sums10, ages, resolution, mode, num_inserts, num_points);
 }
+// what merge_from and merge_from_posed ask of the pair of handles, then the other handle's stream settled and the fence events made.
+// `itself`: what to say when other == h; posed: T16 is the posed call's pose (checked after the handles, before the other stream is touched)
+int rigid_pose(Engine* e, const double* T16, const char* who) {  // the rule fvh_voxelgrid_deskew applies to a knot pose (host_deskew.inc.hpp: deskew_rigid)
+  if (!T16) return e->fail(FVH_ERR_INVALID_ARGUMENT, std::string(who) + ": null pose");
+  if (!deskew_rigid(T16)) return e->fail(FVH_ERR_INVALID_ARGUMENT, std::string(who) + ": the pose is not a finite rigid motion (last row (0, 0, 0, 1), |R^T R - I| <= 1e-6, det R > 0)");
+  return FVH_OK;
+}
 template <class H>
-int voxelmap_merge_from(H* h, H* other) {
-  { const int rc = h->map_refusal("voxelmap_merge_from"); if (rc) return rc; }
-  if (!other) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_merge_from: null other handle");
-  if (other == h) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_merge_from: a map cannot be merged into itself");
-  if (other->e.device != h->e.device) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, "voxelmap_merge_from: the two handles are on different devices");
-  if (const char* kind = other->not_a_merge_source()) return h->e.fail(FVH_ERR_UNSUPPORTED, std::string("voxelmap_merge_from: the other handle is a ") + kind + " handle");
-  if (other->in_flight()) return h->e.fail(FVH_ERR_BAD_STATE, std::string("voxelmap_merge_from: an align_async is in flight on the other handle: call ") + H::prefix + "_align_wait first");
-  { const int rc = map_live(h, "voxelmap_merge_from"); if (rc) return rc; }
-  if (!other->incremental()) return h->e.fail(FVH_ERR_BAD_STATE, std::string("voxelmap_merge_from: the other handle has no live incremental map (") + H::prefix + "_map_begin)");
+int merge_pair(H* h, H* other, const std::string& who, const std::string& itself, bool posed = false, const double* T16 = nullptr) {
+  { const int rc = h->map_refusal(who.c_str()); if (rc) return rc; }
+  if (!other) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, who + ": null other handle");
+  if (other == h) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, who + itself);
+  if (other->e.device != h->e.device) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, who + ": the two handles are on different devices");
+  if (const char* kind = other->not_a_merge_source()) return h->e.fail(FVH_ERR_UNSUPPORTED, who + ": the other handle is a " + kind + " handle");
+  if (other->in_flight()) return h->e.fail(FVH_ERR_BAD_STATE, who + ": an align_async is in flight on the other handle: call " + H::prefix + "_align_wait first");
+  { const int rc = map_live(h, who.c_str()); if (rc) return rc; }
+  if (!other->incremental()) return h->e.fail(FVH_ERR_BAD_STATE, who + ": the other handle has no live incremental map (" + H::prefix + "_map_begin)");
+  if (posed) { const int rc = rigid_pose(&h->e, T16, who.c_str()); if (rc) return rc; }
   // every refusal that needs no HIP call has been given: only now is the other handle's stream touched
-  { const int rc = other->e.settle(); if (rc) return h->e.fail(rc, "voxelmap_merge_from: the other handle: " + other->e.err); }
+  { const int rc = other->e.settle(); if (rc) return h->e.fail(rc, who + ": the other handle: " + other->e.err); }
   for (hipEvent_t& ev : h->merge_ev) if (!ev) HIP_OR_FAIL(&h->e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
   other->e.quiet = false;  // (its stream now holds a wait)
+  return FVH_OK;
+}
+template <class H>
+int voxelmap_merge_from(H* h, H* other) {
+  { const int rc = merge_pair(h, other, "voxelmap_merge_from", ": a map cannot be merged into itself"); if (rc) return rc; }
   return incmap_merge_from(&h->e, h->target_map(), other->target_map(), other->e.stream, h->merge_ev[0], h->merge_ev[1]);
+}
+// ---- a map added under a rigid pose; the live map re-anchored (host_incmap.inc.hpp: "added under a rigid pose") ----
+template <class H>
+int voxelmap_merge_from_posed(H* h, H* other, const double* T16, int* rows_skipped) {
+  { const int rc = merge_pair(h, other, "posed_merge_from", std::string(": a map cannot be merged into itself (to move a map in place: ") + H::prefix + "_transform_map)", true, T16); if (rc) return rc; }
+  return incmap_merge_from_posed(&h->e, h->target_map(), other->target_map(), other->e.stream, h->merge_ev[0], h->merge_ev[1], T16, rows_skipped);
+}
+template <class H>
+int map_transform(H* h, const double* T16, int* rows_skipped) {
+  { const int rc = map_call(h, "transform_map"); if (rc) return rc; }
+  { const int rc = rigid_pose(&h->e, T16, "transform_map"); if (rc) return rc; }
+  return incmap_transform(&h->e, h->target_map(), T16, rows_skipped);
 }
 // ---- the live incremental map as the handle's target cloud (host_incmap.inc.hpp: incmap_to_cloud) ----
 template <class H>
@@ -905,6 +930,8 @@ int fvh_vgicp_map_get_info(fvh_vgicp* h, int* incremental, int* num_voxels, int*
 int fvh_vgicp_voxelmap_export(fvh_vgicp* h, int* num_voxels, double* resolution, int* mode, int* num_inserts, long long* num_points, int* coords3, double* sums10, unsigned* ages) { CHECK_HANDLE(h); return shared::voxelmap_export(h, num_voxels, resolution, mode, num_inserts, num_points, coords3, sums10, ages); }
 int fvh_vgicp_voxelmap_import(fvh_vgicp* h, int n, const int* coords3, const double* sums10, const unsigned* ages, double resolution, int mode, int num_inserts, long long num_points) { CHECK_HANDLE(h); return shared::voxelmap_import(h, n, coords3, sums10, ages, resolution, mode, num_inserts, num_points); }
 int fvh_vgicp_voxelmap_merge_from(fvh_vgicp* h, fvh_vgicp* other) { CHECK_HANDLE(h); return shared::voxelmap_merge_from(h, other); }
+int fvh_vgicp_posed_merge_from(fvh_vgicp* h, fvh_vgicp* other, const double* T16, int* rows_skipped) { CHECK_HANDLE(h); return shared::voxelmap_merge_from_posed(h, other, T16, rows_skipped); }
+int fvh_vgicp_transform_map(fvh_vgicp* h, const double* T16, int* rows_skipped) { CHECK_HANDLE(h); return shared::map_transform(h, T16, rows_skipped); }
 int fvh_vgicp_target_from_map(fvh_vgicp* h, int min_points, int* num_points_out) { CHECK_HANDLE(h); return shared::target_from_map(h, min_points, num_points_out); }
 int fvh_vgicp_get_target_points(fvh_vgicp* h, float* xyz3) { CHECK_HANDLE(h); return shared::get_points_host(&h->e, h->target, xyz3, "get_target_points"); }
 int fvh_vgicp_set_voxel_accumulation_mode(fvh_vgicp* h, int mode) {
@@ -1574,6 +1601,8 @@ int fvh_ndt_map_get_info(fvh_ndt* h, int* incremental, int* num_voxels, int* cap
 int fvh_ndt_voxelmap_export(fvh_ndt* h, int* num_voxels, double* resolution, int* mode, int* num_inserts, long long* num_points, int* coords3, double* sums10, unsigned* ages) { CHECK_HANDLE(h); return shared::voxelmap_export(h, num_voxels, resolution, mode, num_inserts, num_points, coords3, sums10, ages); }
 int fvh_ndt_voxelmap_import(fvh_ndt* h, int n, const int* coords3, const double* sums10, const unsigned* ages, double resolution, int mode, int num_inserts, long long num_points) { CHECK_HANDLE(h); return shared::voxelmap_import(h, n, coords3, sums10, ages, resolution, mode, num_inserts, num_points); }
 int fvh_ndt_voxelmap_merge_from(fvh_ndt* h, fvh_ndt* other) { CHECK_HANDLE(h); return shared::voxelmap_merge_from(h, other); }
+int fvh_ndt_posed_merge_from(fvh_ndt* h, fvh_ndt* other, const double* T16, int* rows_skipped) { CHECK_HANDLE(h); return shared::voxelmap_merge_from_posed(h, other, T16, rows_skipped); }
+int fvh_ndt_transform_map(fvh_ndt* h, const double* T16, int* rows_skipped) { CHECK_HANDLE(h); return shared::map_transform(h, T16, rows_skipped); }
 int fvh_ndt_target_from_map(fvh_ndt* h, int min_points, int* num_points_out) { CHECK_HANDLE(h); return shared::target_from_map(h, min_points, num_points_out); }
 int fvh_ndt_get_num_target_points(const fvh_ndt* h, int* n) { return shared::get_num_target_points(h, n); }
 int fvh_ndt_get_target_points(fvh_ndt* h, float* xyz3) { CHECK_HANDLE(h); return shared::get_points_host(&h->e, h->target, xyz3, "get_target_points"); }
@@ -1703,6 +1732,14 @@ int fvh_ndt_adopt_prepared_source(fvh_ndt* h) {
   return h->pipe.adopt(&h->e, h->source, h->source_vm, "fvh_ndt_prepare_source_device");
 }
 int fvh_ndt_debug_set_voxel_hint(fvh_ndt* h, int which, int num_voxels) { CHECK_HANDLE(h); (which ? h->target_vm : h->source_vm).nv_hint = num_voxels; return FVH_OK; }
+int fvh_ndt_debug_get_skipped_points(fvh_ndt* h, int* n) {  // as fvh_vgicp_debug_get_skipped_points, of the target map
+  CHECK_HANDLE(h);
+  if (!n) return FVH_ERR_INVALID_ARGUMENT;
+  if (!h->target_vm.valid) return h->e.fail(FVH_ERR_BAD_STATE, "voxel map not built");
+  HIP_OR_FAIL(&h->e, hipMemcpyAsync(n, h->target_vm.counters_cur() + 2, sizeof(int), hipMemcpyDeviceToHost, h->e.stream));
+  HIP_OR_FAIL(&h->e, hipStreamSynchronize(h->e.stream));
+  return FVH_OK;
+}
 int fvh_ndt_debug_get_table_capacity(fvh_ndt* h, int which, int* capacity) { CHECK_HANDLE(h); if (!capacity) return FVH_ERR_INVALID_ARGUMENT; *capacity = (int)(which ? h->target_vm : h->source_vm).capacity; return FVH_OK; }
 int fvh_ndt_set_lm_trace(fvh_ndt* h, int on) { CHECK_HANDLE(h); return shared::set_lm_trace(h, on); }
 int fvh_ndt_get_lm_trace(fvh_ndt* h, int* n, double* rows6) { CHECK_HANDLE(h); return shared::get_lm_trace(&h->e, n, rows6); }

@@ -378,6 +378,94 @@ int incmap_merge_from(Engine* e, VoxelMapDev& vm, VoxelMapDev& from, hipStream_t
   return rc;
 }
 
+// ---- a live map added under a rigid pose (fvh_*_posed_merge_from / fvh_*_transform_map; kernels_voxelmap.hpp: "added under a
+// rigid pose"). The callers have validated T16 (deskew_rigid) before anything is queued.
+
+// the rows of `src` (buffers of side src_side, counter set src_side) under T into side `to` of `vm`: kernel + the insert's refresh.
+// ctl[0] (dirty count) and ctl[1] (rows skipped) are zeroed in front; `grid` as incmap_add_rows passes it, or null when the bitmap is rebuilt afterwards
+int incmap_posed_launch(Engine* e, VoxelMapDev& vm, int to, const VoxelMapDev& src, int src_side, int n_rows, const double* T16, bool live_bitmap, const char* prof_class) {
+  HIP_OR_FAIL(e, vm.inc.dirty.ensure(sizeof(unsigned) * (size_t)n_rows));
+  HIP_OR_FAIL(e, hipMemsetAsync(vm.inc.ctl.p, 0, 2 * sizeof(int), e->stream));
+  const PoseD T = pose_from_colmajor16(T16);
+  unsigned long long* keys = vm.keys[to].as<unsigned long long>();
+  double* sums = vm.inc.sums[to].as<double>();
+  unsigned* stamps = vm.inc.stamps[to].as<unsigned>();
+  int* counters = vm.counters.as<int>() + 16 * to;
+  int* ctl = vm.inc.ctl.as<int>();
+  unsigned* dirty = vm.inc.dirty.as<unsigned>();
+  VmGrid* grid = live_bitmap ? vm.grid.as<VmGrid>() : nullptr;
+  unsigned long long* bitmap = live_bitmap ? vm.bitmap.as<unsigned long long>() : nullptr;
+  const int blocks = (n_rows + VM_SNAP_THREADS - 1) / VM_SNAP_THREADS;
+  {
+    ProfScope ps(e, prof_class);
+    incmap_by_mode(vm, [&](auto m) {
+      constexpr int M = decltype(m)::value;
+      vm_import_posed_kernel<M><<<blocks, VM_SNAP_THREADS, 0, e->stream>>>(src.keys[src_side].as<unsigned long long>(), src.inc.sums[src_side].as<double>(), src.inc.stamps[src_side].as<unsigned>(),
+                                                                           src.occupied.as<int>(), src.counters.as<int>() + 16 * src_side, n_rows, src.inc.epoch, T, vm.res, keys,
+                                                                           vm.capacity - 1, sums, stamps, vm.inc.epoch, dirty, ctl, counters + 1);
+      vm_refresh_kernel<M><<<(n_rows + 255) / 256, 256, 0, e->stream>>>(dirty, ctl, keys, sums, vm.table.as<uint4>(), counters, vm.occupied.as<int>(), grid, bitmap);
+    });
+  }
+  HIP_OR_FAIL(e, hipGetLastError());
+  return FVH_OK;
+}
+
+int incmap_read_rows_skipped(Engine* e, VoxelMapDev& vm, int* rows_skipped) {
+  if (!rows_skipped) return FVH_OK;
+  HIP_OR_FAIL(e, hipMemcpyAsync(rows_skipped, vm.inc.ctl.as<int>() + 1, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIP_OR_FAIL(e, hipStreamSynchronize(e->stream));
+  return FVH_OK;
+}
+
+// `from` seen from pose T added into `vm`: incmap_merge_from's fences, capacity and bookkeeping around the posed kernel
+int incmap_merge_from_posed(Engine* e, VoxelMapDev& vm, VoxelMapDev& from, hipStream_t from_stream, hipEvent_t ev_before, hipEvent_t ev_after, const double* T16, int* rows_skipped) {
+  if (!(from.res == vm.res)) return e->fail(FVH_ERR_INVALID_ARGUMENT, "posed_merge_from: the two maps differ in resolution");
+  if (from.inc.mode != vm.inc.mode) return e->fail(FVH_ERR_INVALID_ARGUMENT, "posed_merge_from: the two maps differ in accumulation mode");
+  HIP_OR_FAIL(e, hipEventRecord(ev_before, from_stream));
+  HIP_OR_FAIL(e, hipStreamWaitEvent(e->stream, ev_before, 0));
+  long long n_bound = std::min<long long>(from.inc.voxel_bound, (long long)from.capacity);  // (the host keeps the load factor <= 0.5: capacity bounds the count too)
+  if (vm.inc.voxel_bound + n_bound > INCMAP_MAX_VOXELS || 2 * (vm.inc.voxel_bound + n_bound) > (long long)vm.capacity) {
+    int cnt[3];
+    HIP_OR_FAIL(e, hipMemcpyAsync(cnt, from.counters_cur(), 3 * sizeof(int), hipMemcpyDeviceToHost, e->stream));  // (e's stream: ordered after from_stream by the event)
+    HIP_OR_FAIL(e, hipStreamSynchronize(e->stream));
+    from.inc.voxel_bound = n_bound = cnt[0];
+  }
+  { int rc = incmap_secure(e, vm, n_bound, "posed_merge_from"); if (rc) return rc; }
+  vm.inc.epoch = std::max(vm.inc.epoch, from.inc.epoch);
+  vm.inc.num_points += from.inc.num_points;
+  vm.host_valid = false;
+  vm.has_canon = false;
+  e->has_corr = false;
+  if (rows_skipped) *rows_skipped = 0;
+  if (n_bound == 0) return FVH_OK;  // (nothing was queued on our stream that reads `from`)
+  int rc = incmap_posed_launch(e, vm, vm.cur, from, from.cur, (int)n_bound, T16, vm.has_bitmap, "map_merge_posed");
+  if (rc) return rc;
+  vm.inc.voxel_bound += n_bound;
+  HIP_OR_FAIL(e, hipEventRecord(ev_after, e->stream));
+  HIP_OR_FAIL(e, hipStreamWaitEvent(from_stream, ev_after, 0));
+  if (!vm.has_bitmap) rc = incmap_bitmap(e, vm);  // (as an insert: a map that has grown into bitmap territory gets its bitmap here)
+  return rc ? rc : incmap_read_rows_skipped(e, vm, rows_skipped);
+}
+
+// the live map re-anchored in place: one pass from the current key / sums / stamp buffers into the other set at the same capacity (the
+// voxel count cannot grow), which ADDS -- rows may meet in one voxel --, then the refresh and the bitmap as after a rehash. Insert count,
+// num_points and every row's age stay: a row's stamp goes over as it is (age = epoch - stamp on both sides).
+int incmap_transform(Engine* e, VoxelMapDev& vm, const double* T16, int* rows_skipped) {
+  const int from = vm.cur, to = vm.cur ^ 1;
+  const int n_bound = (int)std::min<long long>(vm.inc.voxel_bound, (long long)vm.capacity);
+  { int rc = incmap_prepare_side(e, vm, to, vm.capacity); if (rc) return rc; }
+  vm_rehash_begin_kernel<<<1, 64, 0, e->stream>>>(vm.counters_cur(), vm.counters.as<int>() + 16 * to, vm.inc.ctl.as<int>());
+  HIP_OR_FAIL(e, hipGetLastError());
+  if (rows_skipped) *rows_skipped = 0;
+  if (n_bound > 0) { int rc = incmap_posed_launch(e, vm, to, vm, from, n_bound, T16, false, "transform_map"); if (rc) return rc; }
+  vm.cur = to;
+  vm.host_valid = false;
+  vm.has_canon = false;
+  e->has_corr = false;  // stored correspondences are bucket indices of the old table
+  { int rc = incmap_bitmap(e, vm); if (rc) return rc; }
+  return n_bound > 0 ? incmap_read_rows_skipped(e, vm, rows_skipped) : (int)FVH_OK;
+}
+
 // ---- the live map as a point target (fvh_vgicp_target_from_map / fvh_ndt_target_from_map; kernels_voxelmap.hpp: "point target") ---------
 // Cloud `c` becomes one point per voxel with >= min_points points -- the record's float mean, with_cov: + the record's covariance -- rows in
 // ascending packed-key order (the row order of incmap_export). The map is only read. Everything is queued on the main stream with scratch of

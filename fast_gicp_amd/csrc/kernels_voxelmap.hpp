@@ -845,6 +845,129 @@ __global__ __launch_bounds__(VM_SNAP_THREADS) void vm_export_kernel(const unsign
   }
 }
 
+// ---- a live map added under a rigid pose (fvh_*_posed_merge_from / fvh_*_transform_map: host_incmap.inc.hpp) ------------
+// The voxel sums transform in closed form under x -> R x + t (n = the count, sp / b the first three sums, the six others a symmetric matrix):
+//   MODE 0 additive       : sp' = R sp + n t             SC' = R SC R^T
+//   MODE 2 multiplicative : A'  = R A R^T                b'  = R b + A' t
+//   MODE 1 NDT, u = R sp  : sp' = u + n t                S'  = R S R^T + u t^T + t u^T + n t t^T
+// all in fp64, each expression in the order tests/posedmerge_ref.py restates. A row goes to the voxel of the float32 mean its transformed
+// sums have ON THEIR OWN -- the record arithmetic, taken from inc_write_record<MODE> / inc_ndt_record_head themselves by handing them a
+// four-quad record in registers -- binned as vm_insert_kernel bins a point. This re-bins voxel Gaussians, not points: several rows may
+// meet in one voxel (their sums add), and a row whose mean leaves the key range is skipped and counted (rows in ctl[1], its points in
+// dropped[1], where an insert counts skipped points).
+// Rows are the compact list of a live map read in place, as vm_import_kernel<true> reads one: another handle's map (merge), or this map's
+// own current buffers on their way into the other set (transform: keys are no longer unique afterwards, so the pass ADDS where
+// vm_rehash_kernel moves). Shaped like vm_import_kernel for the same reason: the workgroup's 256 x 10 sums come into LDS (20 KB) with ten
+// neighbouring lanes per row, one thread per row transforms its row out of LDS and back (80-byte rows: a half wave's 8-byte reads fall
+// two to a bank pair), and the adds leave in the coalesced second phase.
+template <int MODE>
+__device__ __forceinline__ void vm_posed_sums(const PoseD& T, const double* a, double* o) {
+  const double* R = T.r;
+  const double* t = T.t;
+  const double n = a[9];
+  const double S[3][3] = {{a[3], a[4], a[5]}, {a[4], a[6], a[7]}, {a[5], a[7], a[8]}};
+  double u[3], M[3][3], Q[3][3];  // R sp, R S, R S R^T
+#pragma unroll
+  for (int r = 0; r < 3; r++) {
+    u[r] = R[3 * r] * a[0] + R[3 * r + 1] * a[1] + R[3 * r + 2] * a[2];
+#pragma unroll
+    for (int c = 0; c < 3; c++) M[r][c] = R[3 * r] * S[0][c] + R[3 * r + 1] * S[1][c] + R[3 * r + 2] * S[2][c];
+  }
+#pragma unroll
+  for (int r = 0; r < 3; r++)
+#pragma unroll
+    for (int c = r; c < 3; c++) Q[r][c] = M[r][0] * R[3 * c] + M[r][1] * R[3 * c + 1] + M[r][2] * R[3 * c + 2];
+  Q[1][0] = Q[0][1]; Q[2][0] = Q[0][2]; Q[2][1] = Q[1][2];
+  if (MODE == 2) {
+#pragma unroll
+    for (int r = 0; r < 3; r++) o[r] = u[r] + Q[r][0] * t[0] + Q[r][1] * t[1] + Q[r][2] * t[2];
+  } else {
+#pragma unroll
+    for (int r = 0; r < 3; r++) o[r] = u[r] + n * t[r];
+  }
+  if (MODE == 1) {
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+      for (int c = r; c < 3; c++) Q[r][c] = Q[r][c] + u[r] * t[c] + t[r] * u[c] + (n * t[r]) * t[c];
+  }
+  o[3] = Q[0][0]; o[4] = Q[0][1]; o[5] = Q[0][2]; o[6] = Q[1][1]; o[7] = Q[1][2]; o[8] = Q[2][2];
+  o[9] = n;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(VM_SNAP_THREADS) void vm_import_posed_kernel(const unsigned long long* __restrict__ src_keys, const double* __restrict__ src_sums, const unsigned* __restrict__ src_stamps,
+                                                                          const int* __restrict__ src_occupied, const int* __restrict__ src_counters, int n_rows, unsigned src_epoch, PoseD T,
+                                                                          double res, unsigned long long* __restrict__ table_keys, unsigned mask, double* __restrict__ sums,
+                                                                          unsigned* __restrict__ stamps, unsigned epoch, unsigned* __restrict__ dirty, int* __restrict__ ctl,
+                                                                          int* __restrict__ dropped) {
+  __shared__ double s_val[VM_SNAP_THREADS * VM_ACC_STRIDE];
+  __shared__ unsigned s_dst[VM_SNAP_THREADS], s_src[VM_SNAP_THREADS];
+  __shared__ int s_cnt, s_base;
+  const int tid = threadIdx.x;
+  if (tid == 0) s_cnt = 0;
+  const int n = min(src_counters[0], n_rows);  // (n_rows: what the host sized `dirty` and the grid for)
+  const int base = blockIdx.x * VM_SNAP_THREADS;
+  const int i = base + tid;
+  unsigned age = 0u;
+  if (i < n) {
+    const unsigned sb = (unsigned)src_occupied[i];
+    age = src_epoch - src_stamps[sb];
+    s_src[tid] = sb;
+  }
+  __syncthreads();
+  const int rows = min(VM_SNAP_THREADS, n - base);
+  for (int e = tid; e < rows * VM_ACC_STRIDE; e += VM_SNAP_THREADS) {
+    const int v = e / VM_ACC_STRIDE, j = e - v * VM_ACC_STRIDE;
+    s_val[e] = src_sums[(size_t)s_src[v] * VM_ACC_STRIDE + j];
+  }
+  __syncthreads();
+  unsigned b = 0xFFFFFFFFu, entry = 0u;
+  int local = -1;
+  if (i < n) {
+    double a[VM_ACC_STRIDE], o[VM_ACC_STRIDE];
+#pragma unroll
+    for (int j = 0; j < VM_ACC_STRIDE; j++) a[j] = s_val[tid * VM_ACC_STRIDE + j];
+    vm_posed_sums<MODE>(T, a, o);
+    float4 rec[4];  // the record the transformed sums would get, in registers: only its mean (quad 1, which the record functions store as a float4) is used
+    if constexpr (MODE == 1) {
+      Sym3<double> Craw;
+      double wn;
+      inc_ndt_record_head(0ull, o, reinterpret_cast<uint4*>(rec), 0u, Craw, wn);
+    } else {
+      inc_write_record<MODE>(0ull, o, reinterpret_cast<uint4*>(rec), 0u);
+    }
+    const float mx = rec[1].x, my = rec[1].y, mz = rec[1].z;
+    const double fx = floor((double)mx / res - 0.5), fy = floor((double)my / res - 0.5), fz = floor((double)mz / res - 0.5);
+    if (!voxel_index_ok(fx, fy, fz)) {
+      atomicAdd(ctl + 1, 1);
+      atomicAdd(dropped + 1, (int)a[9]);
+    } else {
+      b = inc_claim(table_keys, mask, pack_key((int)fx, (int)fy, (int)fz));
+      if (b != 0xFFFFFFFFu) {
+        const unsigned was = atomicMax(stamps + b, epoch - age);
+        entry = b | (was == 0u ? VM_INC_NEW : 0u);
+        local = atomicAdd(&s_cnt, 1);
+#pragma unroll
+        for (int j = 0; j < VM_ACC_STRIDE; j++) s_val[tid * VM_ACC_STRIDE + j] = o[j];
+      } else {
+        atomicAdd(dropped, 1);  // (cannot happen: the host secures a load factor <= 0.5 before the launch)
+      }
+    }
+  }
+  s_dst[tid] = b;
+  __syncthreads();
+  if (tid == 0) s_base = s_cnt ? atomicAdd(ctl, s_cnt) : 0;
+  for (int e = tid; e < rows * VM_ACC_STRIDE; e += VM_SNAP_THREADS) {
+    const int v = e / VM_ACC_STRIDE;
+    const unsigned db = s_dst[v];
+    if (db == 0xFFFFFFFFu) continue;
+    atomicAdd(&sums[(size_t)db * VM_ACC_STRIDE + (e - v * VM_ACC_STRIDE)], s_val[e]);
+  }
+  __syncthreads();
+  if (local >= 0) dirty[s_base + local] = entry;
+}
+
 // ---- the live incremental map as a point target (fvh_vgicp_target_from_map / fvh_ndt_target_from_map: host_incmap.inc.hpp) --------
 // One point per voxel (the record's float mean; VGICP: + the record's covariance), rows in ascending packed-key order, written where a
 // target cloud lives -- so the exact 1-NN search, the fitness score and the FastGICP cost run on the map unchanged. Three steps:

@@ -76,6 +76,13 @@ static Matrix4f numpy2mat4(const Mat4& m) {
   for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) M(i, j) = (float)r(i, j);
   return M;
 }
+static fast_gicp::Isometry3d numpy2iso(const Mat4& m) {  // a pose kept in double (the upper three rows: a rigid pose's last row is (0, 0, 0, 1))
+  if (m.ndim() != 2 || m.shape(0) != 4 || m.shape(1) != 4) throw std::invalid_argument("pose must be a (4, 4) array");
+  fast_gicp::Matrix4d M;
+  auto r = m.unchecked<2>();
+  for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) M(i, j) = r(i, j);
+  return fast_gicp::Isometry3d::from(M);
+}
 static std::vector<Matrix4f> numpy2mat4s(const Mat4& m) {  // (K, 4, 4) -> K poses
   if (m.ndim() != 3 || m.shape(1) != 4 || m.shape(2) != 4) throw std::invalid_argument("poses must be a (K, 4, 4) array");
   std::vector<Matrix4f> out((size_t)m.shape(0));
@@ -310,6 +317,10 @@ static void def_incremental_target(PyClass& c) {
         v.importTargetMap(m);
       }, py::arg("snapshot"))
       .def("merge_target_from", [](Reg& v, Reg& other) { v.mergeTargetFrom(other); }, py::arg("other"))
+      // a map built in another frame added under the rigid pose T (other's frame -> this map's), and the live map re-anchored in place
+      // (fvh_*_posed_merge_from / fvh_*_transform_map). -> rows skipped because their mean left the key range
+      .def("merge_target_from_posed", [](Reg& v, Reg& other, const Mat4& T) { return v.mergeTargetFromPosed(other, numpy2iso(T)); }, py::arg("other"), py::arg("T"))
+      .def("transform_target_map", [](Reg& v, const Mat4& T) { return v.transformTargetMap(numpy2iso(T)); }, py::arg("T"))
       .def("save_target_map", [](Reg& v, const std::string& path) { v.saveTargetMap(path); }, py::arg("path"))
       .def("load_target_map", [](Reg& v, const std::string& path) { v.loadTargetMap(path); }, py::arg("path"));
 }

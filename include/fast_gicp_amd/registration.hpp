@@ -626,6 +626,8 @@ struct MapCalls<fvh_vgicp> {
   static int export_rows(fvh_vgicp* h, int* n, double* res, int* mode, int* inserts, long long* points, int* coords, double* sums, unsigned* ages) { return fvh_vgicp_voxelmap_export(h, n, res, mode, inserts, points, coords, sums, ages); }
   static int import_rows(fvh_vgicp* h, int n, const int* coords, const double* sums, const unsigned* ages, double res, int mode, int inserts, long long points) { return fvh_vgicp_voxelmap_import(h, n, coords, sums, ages, res, mode, inserts, points); }
   static int merge_from(fvh_vgicp* h, fvh_vgicp* other) { return fvh_vgicp_voxelmap_merge_from(h, other); }
+  static int merge_from_posed(fvh_vgicp* h, fvh_vgicp* other, const double* T16, int* rows_skipped) { return fvh_vgicp_posed_merge_from(h, other, T16, rows_skipped); }
+  static int transform(fvh_vgicp* h, const double* T16, int* rows_skipped) { return fvh_vgicp_transform_map(h, T16, rows_skipped); }
   static int target_from_map(fvh_vgicp* h, int min_points, int* num_points) { return fvh_vgicp_target_from_map(h, min_points, num_points); }
 };
 template <>
@@ -636,6 +638,8 @@ struct MapCalls<fvh_ndt> {
   static int export_rows(fvh_ndt* h, int* n, double* res, int* mode, int* inserts, long long* points, int* coords, double* sums, unsigned* ages) { return fvh_ndt_voxelmap_export(h, n, res, mode, inserts, points, coords, sums, ages); }
   static int import_rows(fvh_ndt* h, int n, const int* coords, const double* sums, const unsigned* ages, double res, int mode, int inserts, long long points) { return fvh_ndt_voxelmap_import(h, n, coords, sums, ages, res, mode, inserts, points); }
   static int merge_from(fvh_ndt* h, fvh_ndt* other) { return fvh_ndt_voxelmap_merge_from(h, other); }
+  static int merge_from_posed(fvh_ndt* h, fvh_ndt* other, const double* T16, int* rows_skipped) { return fvh_ndt_posed_merge_from(h, other, T16, rows_skipped); }
+  static int transform(fvh_ndt* h, const double* T16, int* rows_skipped) { return fvh_ndt_transform_map(h, T16, rows_skipped); }
   static int target_from_map(fvh_ndt* h, int min_points, int* num_points) { return fvh_ndt_target_from_map(h, min_points, num_points); }
 };
 }  // namespace detail
@@ -743,6 +747,24 @@ protected:
     call(Map::import_rows(core_, (int)n, n ? m.coords.data() : nullptr, n ? m.sums.data() : nullptr, n ? m.ages.data() : nullptr, m.resolution, m.mode, m.num_inserts, m.num_points), "voxelmap_import");
   }
   void merge_target_from(DeviceRegistration& other) { call(Map::merge_from(core_, other.core_), "voxelmap_merge_from"); }  // (the classes' mergeTargetFrom takes their own type)
+  /// `other`'s live map, seen from pose T (other's frame -> this map's frame, rigid), added into this one on the device: every voxel's sums are
+  /// transformed in closed form and go to the voxel of their own mean (C ABI: fvh_*_posed_merge_from). Returns the rows skipped because
+  /// their mean left the key range. (the classes' mergeTargetFromPosed takes their own type)
+  int merge_target_from_posed(DeviceRegistration& other, const Isometry3d& T) {
+    double T16[16];
+    int skipped = 0;
+    T.to_colmajor16(T16);
+    call(Map::merge_from_posed(core_, other.core_, T16, &skipped), "posed_merge_from");
+    return skipped;
+  }
+  /// re-anchors the live incremental target by the rigid pose T in place (fvh_*_transform_map); insert count, point count and ages stay
+  int transformTargetMap(const Isometry3d& T) {
+    double T16[16];
+    int skipped = 0;
+    T.to_colmajor16(T16);
+    call(Map::transform(core_, T16, &skipped), "transform_map");
+    return skipped;
+  }
   void saveTargetMap(const std::string& path) { detail::write_map_file(path, exportTargetMap()); }
   bool has_device_target() const override { return incremental_target_; }
   bool incremental_target_ = false;  // beginIncrementalTarget .. setInputTarget
@@ -973,6 +995,8 @@ public:
   using Base::importTargetMap;
   /// adds the live incremental target of `other` (same device, resolution and mode) into this one, device to device; `other` is unchanged
   void mergeTargetFrom(FastVGICPCuda& other) { this->merge_target_from(other); }
+  int mergeTargetFromPosed(FastVGICPCuda& other, const Isometry3d& T) { return this->merge_target_from_posed(other, T); }
+  using Base::transformTargetMap;
   using Base::saveTargetMap;
   /// adds the file's map into the incremental target; an object without one takes the file's resolution and voxel mode and starts one sized for it
   void loadTargetMap(const std::string& path) {
@@ -1226,6 +1250,8 @@ public:
   using Base::exportTargetMap;
   using Base::importTargetMap;
   void mergeTargetFrom(NDTCuda& other) { this->merge_target_from(other); }
+  int mergeTargetFromPosed(NDTCuda& other, const Isometry3d& T) { return this->merge_target_from_posed(other, T); }
+  using Base::transformTargetMap;
   using Base::saveTargetMap;
   /// adds the file's map into the incremental target; an object without one takes the file's resolution and starts one sized for it
   void loadTargetMap(const std::string& path) {

@@ -297,6 +297,39 @@ int fvh_vgicp_map_get_info(fvh_vgicp* h, int* incremental, int* num_voxels, int*
 int fvh_vgicp_voxelmap_export(fvh_vgicp* h, int* num_voxels, double* resolution, int* mode, int* num_inserts, long long* num_points, int* coords3, double* sums10, unsigned* ages);
 int fvh_vgicp_voxelmap_import(fvh_vgicp* h, int n, const int* coords3, const double* sums10, const unsigned* ages, double resolution, int mode, int num_inserts, long long num_points);
 int fvh_vgicp_voxelmap_merge_from(fvh_vgicp* h, fvh_vgicp* other);
+/* new: a map built in ANOTHER frame added into this one (submaps fused after pose-graph optimisation, a second session registered against
+ * the first), and the live map re-anchored in place (a vehicle-centred map that moves, a loop-closure correction) -- on the device, one pass.
+ * T16: 4x4 double, column-major, mapping `other`'s frame into h's; finite and rigid by the rule fvh_voxelgrid_deskew applies to a knot
+ * pose (last row (0,0,0,1) to 1e-9, |R^T R - I| <= 1e-6 entrywise, det R > 0).
+ *   posed_merge_from: every row {key, s[0..9], age} of `other`'s live map is transformed in fp64 (R, t from T16; n = s[9]; the six stored
+ *            entries of a symmetric result are its upper triangle xx xy xz yy yz zz):
+ *              additive (snapshot mode 0)        sp' = R sp + n t;   SC' = R SC R^T;                                          n' = n
+ *              multiplicative (mode 2)           A'  = R A R^T;      b'  = R b + A' t;                                        n' = n
+ *              NDT sums (mode 3), u = R sp       sp' = u + n t;      S'  = R S R^T + u t^T + t u^T + n t t^T;                 n' = n
+ *            and added into the voxel of ITS OWN float32 mean: m' = the mean the voxel record arithmetic gives the transformed sums alone
+ *            (additive / NDT: (float)(sp' * (1 / n)); multiplicative: (float)(A'^-1 b')), coord = floor((double)m' / resolution - 0.5) per
+ *            axis, exactly as an inserted point is binned. The voxel is created if absent; several rows may land in one voxel and their
+ *            sums add; stamp = max(own, new insert count - age) as _merge_from. A row whose coord leaves |c| < 2^20 - 4096 is skipped:
+ *            counted in *rows_skipped (may be NULL; non-NULL costs one int read back and a stream synchronisation) and its point count added
+ *            to the skipped-point counter (fvh_vgicp_debug_get_skipped_points). Bookkeeping as _merge_from: insert count max(own, other's),
+ *            num_points += other's (skipped rows included), capacity secured before the launch (num_dropped stays 0), stored
+ *            correspondences cleared, the occupancy bitmap follows the insert rule, both streams ordered around the read, `other` unchanged.
+ *   transform_map: re-anchors h's live map by T16 in place; the result is what fvh_vgicp_map_begin on a fresh handle followed by
+ *            posed_merge_from(fresh, h, T16) would hold. Insert count, num_points, every row's age, resolution and mode stay; the table is
+ *            rewritten into its other buffer set (a pass proportional to the map, like a rehash) and the bitmap rebuilt; stored
+ *            correspondences are cleared. A target cloud made earlier by fvh_vgicp_target_from_map is a snapshot and stays as it was.
+ * This re-bins voxel GAUSSIANS, not points: a voxel of `other` goes where its mean goes. The result is therefore not the map of the
+ * re-inserted points, voxels may fuse (never split), and merge(T) followed by merge(T^-1) is not the identity. Conserved exactly in the
+ * algebra above: counts, first moments (sum p' = R sum p + n t) and covariance sums. Numerically each output sum is within a few dozen
+ * 2^-53 of the same formulas evaluated with |R|, |t|, |sums| (tests/posedmerge_ref.py). For NDT the covariance recomputed from S' is
+ * analytically R C R^T, but S' holds n |m'|^2-sized terms that cancel in it: its absolute fp64 error grows with n |m'|^2 2^-53, as for
+ * any NDT voxel far from the origin.
+ * Refusals (the handle, its map and `other` stay as they were; host input is validated before anything is queued): NULL other or T16, a
+ * non-finite or non-rigid T16, other == h (use transform_map), resolution (bit-equal double) or mode different, handles on different
+ * devices (FVH_ERR_INVALID_ARGUMENT); no live incremental map on either handle, an align_async in flight on either handle
+ * (FVH_ERR_BAD_STATE); multi-GPU handles, FVH_COMPUTE_CUDA_COMPAT, more than 2^28 voxels (FVH_ERR_UNSUPPORTED). */
+int fvh_vgicp_posed_merge_from(fvh_vgicp* h, fvh_vgicp* other, const double* T16, int* rows_skipped);
+int fvh_vgicp_transform_map(fvh_vgicp* h, const double* T16, int* rows_skipped);
 /* new: the live incremental map as the handle's TARGET CLOUD -- what fvh_vgicp_fitness_score, fvh_vgicp_gicp_* (FastGICP), find_target_neighbors
  * and debug_get_spatial_order(which = 1) need and a map does not have. Made on the device (select, radix sort by key, gather), nothing
  * crosses PCIe but one 32-byte readback.
@@ -517,6 +550,9 @@ int fvh_ndt_map_get_info(fvh_ndt* h, int* incremental, int* num_voxels, int* cap
 int fvh_ndt_voxelmap_export(fvh_ndt* h, int* num_voxels, double* resolution, int* mode, int* num_inserts, long long* num_points, int* coords3, double* sums10, unsigned* ages);
 int fvh_ndt_voxelmap_import(fvh_ndt* h, int n, const int* coords3, const double* sums10, const unsigned* ages, double resolution, int mode, int num_inserts, long long num_points);
 int fvh_ndt_voxelmap_merge_from(fvh_ndt* h, fvh_ndt* other);
+/* as fvh_vgicp_posed_merge_from / fvh_vgicp_transform_map, argument for argument, with the NDT row of their table of sums */
+int fvh_ndt_posed_merge_from(fvh_ndt* h, fvh_ndt* other, const double* T16, int* rows_skipped);
+int fvh_ndt_transform_map(fvh_ndt* h, const double* T16, int* rows_skipped);
 /* new: the live incremental NDT map as the handle's target cloud, as fvh_vgicp_target_from_map / _get_target_points above: one point per
  * voxel with >= min_points points (the float mean fvh_ndt_get_voxels(h, 1, ...) returns, bit for bit), rows in ascending packed-key order,
  * a snapshot. POINTS ONLY (an NDT handle keeps no target covariances). The map stays the target map and stays live: the call does NOT mark
@@ -539,6 +575,7 @@ int fvh_ndt_fitness_score(fvh_ndt* h, const double* T16, double max_range, doubl
 int fvh_ndt_debug_set_voxel_hint(fvh_ndt* h, int which, int num_voxels);
 /* testing hook (as fvh_vgicp_debug_get_table_capacity): buckets of the current source (which = 0) / target (1) voxel table */
 int fvh_ndt_debug_get_table_capacity(fvh_ndt* h, int which, int* capacity);
+int fvh_ndt_debug_get_skipped_points(fvh_ndt* h, int* n);  /* as fvh_vgicp_debug_get_skipped_points, of the target map: points (and the points of posed-merge rows) that belong to no voxel */
 int fvh_ndt_set_lm_trace(fvh_ndt* h, int on);
 int fvh_ndt_get_lm_trace(fvh_ndt* h, int* num_rows, double* rows6);
 int fvh_ndt_get_num_voxels(fvh_ndt* h, int which /* 0 source, 1 target */, int* num_voxels);
