@@ -220,6 +220,22 @@ def read_map_file(path):
                 coords=coords, sums=sums, ages=ages)
 
 
+def clear_rays_check(min_range, max_range, end_margin, min_misses, origin=None):
+    """The refusals of fvh_*_clear_rays_* that need no handle, given before the call (FvhError): the library gives the same ones, and
+    those that need the map (max_range beyond 4096 voxels) or the cloud. Needs no GPU."""
+    import math
+    if origin is not None and not (np.size(origin) == 3 and np.all(np.isfinite(np.asarray(origin, np.float64)))):
+        raise FvhError("map_clear_rays: origin must be 3 finite values")
+    if not min_range >= 0.0:
+        raise FvhError("map_clear_rays: min_range must be >= 0")
+    if not math.isfinite(max_range) or max_range < min_range:
+        raise FvhError("map_clear_rays: max_range must be finite and >= min_range")
+    if not math.isfinite(end_margin) or end_margin < 0.0:
+        raise FvhError("map_clear_rays: end_margin must be finite and >= 0")
+    if int(min_misses) < 1:
+        raise FvhError("map_clear_rays: min_misses must be >= 1")
+
+
 class _IncrementalMap:
     """The incremental target map of a handle class whose C prefix has map_* / voxelmap_* calls (mixed into VGICPCore and NDTMapCore)."""
 
@@ -292,6 +308,30 @@ class _PosedMap:
         skipped, t = C.c_int(0), _colmajor16(T)
         self._call("transform_map", _p(t), C.byref(skipped))
         return skipped.value
+
+
+class _RayClearing:
+    """Free-space carving on the live incremental map (include/fast_vgicp_hip.h: fvh_{vgicp,ndt}_clear_rays_source / _cloud): mixed into
+    VGICPMapCore and NDTMapCore, the handle classes for scan-to-map work."""
+
+    def map_clear_rays(self, T=None, xyz=None, origin=None, min_range=0.0, max_range=100.0, end_margin=0.0, min_misses=1, device_ptr=None, n=None, stride=3):
+        """Free-space carving (fvh_*_clear_rays_source / _cloud): drop the voxels that at least min_misses rays of this call cross and none
+        ends in. The rays run from `origin` (scan frame, None: (0, 0, 0)) to the current source points (xyz and device_ptr None), to the
+        host points xyz (m, 3), or to n device points at device_ptr (stride 3 or 4 floats), all at pose T (4x4, default identity); rays outside
+        [min_range, max_range] metres are skipped and a walk stops end_margin metres in front of its endpoint. -> (voxels removed, rays used)"""
+        clear_rays_check(min_range, max_range, end_margin, min_misses, origin)
+        t = _IDENTITY16 if T is None else _colmajor16(T)
+        o = None if origin is None else np.ascontiguousarray(origin, np.float64).reshape(3)
+        removed, used = C.c_int(0), C.c_int(0)
+        tail = (_p(t), None if o is None else _p(o), C.c_double(min_range), C.c_double(max_range), C.c_double(end_margin), int(min_misses), C.byref(removed), C.byref(used))
+        if device_ptr is not None:
+            self._call("clear_rays_cloud", C.c_void_p(device_ptr), int(n), int(stride), 1, *tail)
+        elif xyz is not None:
+            a = _f32(xyz).reshape(-1, 3)
+            self._call("clear_rays_cloud", _p(a) if len(a) else None, len(a), 3, 0, *tail)
+        else:
+            self._call("clear_rays_source", *tail)
+        return removed.value, used.value
 
 
 class _MapTarget:
@@ -825,7 +865,7 @@ class VGICPCore(_Core, _IncrementalMap):
         return n.value
 
 
-class VGICPMapCore(VGICPCore, _MapTarget, _PosedMap):
+class VGICPMapCore(VGICPCore, _MapTarget, _PosedMap, _RayClearing):
     """A VGICP handle for scan-to-map work: VGICPCore (which has the map_* calls) + target_from_map / get_target_points, on the same C handle
     type -- as NDTMapCore is to NDTCore."""
 
@@ -1134,7 +1174,7 @@ class NDTCore(_Core):
         return coords, num, means, covs
 
 
-class NDTMapCore(NDTCore, _IncrementalMap, _MapTarget, _PosedMap):
+class NDTMapCore(NDTCore, _IncrementalMap, _MapTarget, _PosedMap, _RayClearing):
     """An NDT handle with the calls of its incremental target map (include/fast_vgicp_hip.h: fvh_ndt_map_* / fvh_ndt_voxelmap_*): map_begin,
     map_insert_source, map_prune, map_info, map_export, map_import, map_merge_from, map_save come from _IncrementalMap as on VGICPCore; NDT
     voxels take points only. Everything else is NDTCore's, on the same C handle type."""

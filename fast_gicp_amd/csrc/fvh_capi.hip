@@ -820,6 +820,23 @@ int map_prune(H* h, const double* center3, double radius, int max_age, int* num_
   { const int rc = map_call(h, "map_prune"); if (rc) return rc; }
   return incmap_prune(&h->e, h->target_map(), center3, radius, max_age, num_removed);
 }
+// free space cleared along the rays origin3 -> point, both at pose T16. from_source: the rays end at the handle's source points (walked in
+// their Morton order when there is one, as map_insert_source walks them); else at xyz (n, stride_floats, on_device), staged in insert_cloud
+template <class H>
+int map_clear_rays(H* h, bool from_source, const float* xyz, int n, int stride_floats, int on_device, const double* T16, const double* origin3, double min_range, double max_range, double end_margin,
+                   int min_misses, int* num_removed, int* rays_used) {
+  const char* who = from_source ? "clear_rays_source" : "clear_rays_cloud";
+  { const int rc = map_call(h, who); if (rc) return rc; }
+  if (from_source && !h->source.has_pts) return h->e.fail(FVH_ERR_BAD_STATE, std::string(who) + ": the source cloud is not set");
+  { const int rc = incmap_clear_rays_check(&h->e, h->target_map(), T16, origin3, min_range, max_range, end_margin, min_misses, who); if (rc) return rc; }
+  if (from_source) return incmap_clear_rays(&h->e, h->target_map(), h->source, coherent_order(h->source, h->e.params.coherent_min_points), T16, origin3, min_range, max_range, end_margin, min_misses, num_removed, rays_used);
+  if (n < 0) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, std::string(who) + ": n < 0");
+  if (n > 0 && !xyz) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, std::string(who) + ": null points with n > 0");
+  if (stride_floats != 3 && stride_floats != 4) return h->e.fail(FVH_ERR_INVALID_ARGUMENT, std::string(who) + ": stride must be 3 or 4 floats");
+  cloud_replaced(h->insert_cloud);
+  { const int rc = upload_cloud(&h->e, h->insert_cloud, xyz, n, stride_floats, on_device != 0, false); if (rc) return rc; }
+  return incmap_clear_rays(&h->e, h->target_map(), h->insert_cloud, nullptr, T16, origin3, min_range, max_range, end_margin, min_misses, num_removed, rays_used);
+}
 template <class H>
 int map_get_info(H* h, int* incremental, int* num_voxels, int* capacity, int* num_inserts, long long* num_points, int* num_dropped) {
   VoxelMapDev& vm = h->target_map();
@@ -926,6 +943,8 @@ int fvh_vgicp_map_begin(fvh_vgicp* h, int expected_voxels) { CHECK_HANDLE(h); re
 int fvh_vgicp_map_insert_source(fvh_vgicp* h, const double* T16) { CHECK_HANDLE(h); return shared::map_insert_source(h, T16); }
 int fvh_vgicp_map_insert_cloud(fvh_vgicp* h, const float* xyz, int n, int stride_floats, const double* covs9, const double* T16, int on_device) { CHECK_HANDLE(h); return shared::map_insert_cloud(h, xyz, n, stride_floats, covs9, T16, on_device); }
 int fvh_vgicp_map_prune(fvh_vgicp* h, const double* center3, double radius, int max_age, int* num_removed) { CHECK_HANDLE(h); return shared::map_prune(h, center3, radius, max_age, num_removed); }
+int fvh_vgicp_clear_rays_source(fvh_vgicp* h, const double* T16, const double* origin3, double min_range, double max_range, double end_margin, int min_misses, int* num_removed, int* rays_used) { CHECK_HANDLE(h); return shared::map_clear_rays(h, true, nullptr, 0, 3, 0, T16, origin3, min_range, max_range, end_margin, min_misses, num_removed, rays_used); }
+int fvh_vgicp_clear_rays_cloud(fvh_vgicp* h, const float* xyz, int n, int stride_floats, int on_device, const double* T16, const double* origin3, double min_range, double max_range, double end_margin, int min_misses, int* num_removed, int* rays_used) { CHECK_HANDLE(h); return shared::map_clear_rays(h, false, xyz, n, stride_floats, on_device, T16, origin3, min_range, max_range, end_margin, min_misses, num_removed, rays_used); }
 int fvh_vgicp_map_get_info(fvh_vgicp* h, int* incremental, int* num_voxels, int* capacity, int* num_inserts, long long* num_points, int* num_dropped) { CHECK_HANDLE(h); return shared::map_get_info(h, incremental, num_voxels, capacity, num_inserts, num_points, num_dropped); }
 int fvh_vgicp_voxelmap_export(fvh_vgicp* h, int* num_voxels, double* resolution, int* mode, int* num_inserts, long long* num_points, int* coords3, double* sums10, unsigned* ages) { CHECK_HANDLE(h); return shared::voxelmap_export(h, num_voxels, resolution, mode, num_inserts, num_points, coords3, sums10, ages); }
 int fvh_vgicp_voxelmap_import(fvh_vgicp* h, int n, const int* coords3, const double* sums10, const unsigned* ages, double resolution, int mode, int num_inserts, long long num_points) { CHECK_HANDLE(h); return shared::voxelmap_import(h, n, coords3, sums10, ages, resolution, mode, num_inserts, num_points); }
@@ -1597,6 +1616,8 @@ int fvh_ndt_map_begin(fvh_ndt* h, int expected_voxels) { CHECK_HANDLE(h); return
 int fvh_ndt_map_insert_source(fvh_ndt* h, const double* T16) { CHECK_HANDLE(h); return shared::map_insert_source(h, T16); }
 int fvh_ndt_map_insert_cloud(fvh_ndt* h, const float* xyz, int n, int stride_floats, const double* T16, int on_device) { CHECK_HANDLE(h); return shared::map_insert_cloud(h, xyz, n, stride_floats, nullptr, T16, on_device); }
 int fvh_ndt_map_prune(fvh_ndt* h, const double* center3, double radius, int max_age, int* num_removed) { CHECK_HANDLE(h); return shared::map_prune(h, center3, radius, max_age, num_removed); }
+int fvh_ndt_clear_rays_source(fvh_ndt* h, const double* T16, const double* origin3, double min_range, double max_range, double end_margin, int min_misses, int* num_removed, int* rays_used) { CHECK_HANDLE(h); return shared::map_clear_rays(h, true, nullptr, 0, 3, 0, T16, origin3, min_range, max_range, end_margin, min_misses, num_removed, rays_used); }
+int fvh_ndt_clear_rays_cloud(fvh_ndt* h, const float* xyz, int n, int stride_floats, int on_device, const double* T16, const double* origin3, double min_range, double max_range, double end_margin, int min_misses, int* num_removed, int* rays_used) { CHECK_HANDLE(h); return shared::map_clear_rays(h, false, xyz, n, stride_floats, on_device, T16, origin3, min_range, max_range, end_margin, min_misses, num_removed, rays_used); }
 int fvh_ndt_map_get_info(fvh_ndt* h, int* incremental, int* num_voxels, int* capacity, int* num_inserts, long long* num_points, int* num_dropped) { CHECK_HANDLE(h); return shared::map_get_info(h, incremental, num_voxels, capacity, num_inserts, num_points, num_dropped); }
 int fvh_ndt_voxelmap_export(fvh_ndt* h, int* num_voxels, double* resolution, int* mode, int* num_inserts, long long* num_points, int* coords3, double* sums10, unsigned* ages) { CHECK_HANDLE(h); return shared::voxelmap_export(h, num_voxels, resolution, mode, num_inserts, num_points, coords3, sums10, ages); }
 int fvh_ndt_voxelmap_import(fvh_ndt* h, int n, const int* coords3, const double* sums10, const unsigned* ages, double resolution, int mode, int num_inserts, long long num_points) { CHECK_HANDLE(h); return shared::voxelmap_import(h, n, coords3, sums10, ages, resolution, mode, num_inserts, num_points); }

@@ -205,6 +205,76 @@ int incmap_prune(Engine* e, VoxelMapDev& vm, const double* center3, double radiu
   return FVH_OK;
 }
 
+// ---- free space cleared along the rays of a posed scan (fvh_*_clear_rays_*; kernels_voxelmap.hpp: "free space cleared") -------------
+// o' = (float)(R o + t): ((r0 x + r1 y) + r2 z) + t per axis in fp64 with no product contracted into a sum, rounded once
+inline float clear_rays_origin_axis(const double* r3, const double* o, double t) {
+#pragma clang fp contract(off)
+  return (float)(((r3[0] * o[0] + r3[1] * o[1]) + r3[2] * o[2]) + t);
+}
+// what the host refuses before anything is queued (the cloud's own arguments -- n, xyz, stride -- are the caller's)
+int incmap_clear_rays_check(Engine* e, const VoxelMapDev& vm, const double* T16, const double* origin3, double min_range, double max_range, double end_margin, int min_misses, const char* who) {
+  const std::string w(who);
+  if (!T16) return e->fail(FVH_ERR_INVALID_ARGUMENT, w + ": null pose");
+  for (int i = 0; i < 16; i++)
+    if (!std::isfinite(T16[i])) return e->fail(FVH_ERR_INVALID_ARGUMENT, w + ": the pose is not finite");
+  if (origin3 && !(std::isfinite(origin3[0]) && std::isfinite(origin3[1]) && std::isfinite(origin3[2]))) return e->fail(FVH_ERR_INVALID_ARGUMENT, w + ": the origin is not finite");
+  if (!(min_range >= 0.0)) return e->fail(FVH_ERR_INVALID_ARGUMENT, w + ": min_range must be >= 0");
+  if (!std::isfinite(max_range) || max_range < min_range) return e->fail(FVH_ERR_INVALID_ARGUMENT, w + ": max_range must be finite and >= min_range");
+  if (max_range / vm.res > 4096.0) return e->fail(FVH_ERR_INVALID_ARGUMENT, w + ": max_range is more than 4096 voxels (a lane would walk more than 12,291 cells)");
+  if (!std::isfinite(end_margin) || end_margin < 0.0) return e->fail(FVH_ERR_INVALID_ARGUMENT, w + ": end_margin must be finite and >= 0");
+  if (min_misses < 1) return e->fail(FVH_ERR_INVALID_ARGUMENT, w + ": min_misses must be >= 1");
+  return FVH_OK;
+}
+
+// the rays origin3 -> point of cloud `c` (points only), both at pose T16: mark, sweep, one readback, and -- only if a voxel was condemned -- the
+// rehash at the same capacity. Arguments checked by incmap_clear_rays_check.
+int incmap_clear_rays(Engine* e, VoxelMapDev& vm, const CloudDev& c, const int* order, const double* T16, const double* origin3, double min_range, double max_range, double end_margin,
+                      int min_misses, int* num_removed, int* rays_used) {
+  if (num_removed) *num_removed = 0;
+  if (rays_used) *rays_used = 0;
+  const int n = c.n;
+  if (n == 0) return FVH_OK;
+  VmRays ry;
+  ry.T = pose_from_colmajor16(T16);
+  const double zero3[3] = {0.0, 0.0, 0.0};
+  for (int a = 0; a < 3; a++) ry.origin[a] = clear_rays_origin_axis(ry.T.r + 3 * a, origin3 ? origin3 : zero3, ry.T.t[a]);
+  ry.res = vm.res; ry.min_range = min_range; ry.max_range = max_range; ry.end_margin = end_margin;
+  // The sweep marks a condemned bucket by writing its stamp, and only the rehash removes it: nothing between the two may fail. The buffers
+  // the rehash moves the map into are therefore secured here, before anything is written (same capacity: table and list are large enough).
+  const int to = vm.cur ^ 1;
+  HIP_OR_FAIL(e, vm.keys[to].ensure((size_t)vm.capacity * 8));
+  HIP_OR_FAIL(e, vm.inc.sums[to].ensure((size_t)vm.capacity * VM_ACC_STRIDE * sizeof(double)));
+  HIP_OR_FAIL(e, vm.inc.stamps[to].ensure((size_t)vm.capacity * sizeof(unsigned)));
+  HIP_OR_FAIL(e, vm.inc.ray_marks.ensure((size_t)vm.capacity * sizeof(unsigned)));
+  HIP_OR_FAIL(e, hipMemsetAsync(vm.inc.ray_marks.p, 0, (size_t)vm.capacity * sizeof(unsigned), e->stream));
+  HIP_OR_FAIL(e, hipMemsetAsync(vm.inc.ctl.p, 0, 4 * sizeof(int), e->stream));
+  const int n_bound = (int)std::min<long long>(vm.inc.voxel_bound, (long long)vm.capacity);  // (the host keeps the load factor <= 0.5: capacity bounds the count too)
+  {
+    ProfScope ps(e, "map_raymark");
+    vm_raymark_kernel<<<(n + 255) / 256, 256, 0, e->stream>>>(c.pts.as<float4>(), n, order, ry, vm.keys_cur(), vm.capacity - 1, vm.inc.ray_marks.as<unsigned>(),
+                                                              vm.has_bitmap ? vm.grid.as<VmGrid>() : nullptr, vm.has_bitmap ? vm.bitmap.as<unsigned long long>() : nullptr, vm.inc.ctl.as<int>());
+  }
+  if (n_bound > 0) {
+    ProfScope ps(e, "map_raysweep");
+    vm_raysweep_kernel<<<(n_bound + 255) / 256, 256, 0, e->stream>>>(vm.occupied.as<int>(), vm.counters_cur(), n_bound, vm.inc.ray_marks.as<unsigned>(), (unsigned)min_misses,
+                                                                     vm.inc.stamps[vm.cur].as<unsigned>(), vm.inc.ctl.as<int>());
+  }
+  HIP_OR_FAIL(e, hipGetLastError());
+  int cnt[3], ctl[4];
+  { int rc = incmap_read_counts(e, vm, cnt, ctl); if (rc) return rc; }
+  vm.inc.voxel_bound = cnt[0];
+  if (rays_used) *rays_used = ctl[1];
+  const int removed = ctl[3];
+  if (removed > 0) {
+    VmPrune p = incmap_no_prune(vm);
+    p.max_age = vm.inc.epoch;  // epoch - stamp >= epoch: exactly the buckets whose stamp the sweep set to 0
+    { int rc = incmap_rehash(e, vm, vm.capacity, p); if (rc) return rc; }
+    vm.inc.voxel_bound = cnt[0] - removed;
+  }
+  if (num_removed) *num_removed = removed;
+  return FVH_OK;
+}
+
 // ---- snapshots of the live map (fvh_vgicp_voxelmap_export / _import / _merge_from; kernels_voxelmap.hpp: "snapshots") ------------------
 // A snapshot is the header {resolution, mode, num_inserts = epoch, num_points, num_voxels} and per voxel {coords[3], sums[10], age}, rows
 // in ascending packed-key order. Rows ADD into a live map of the same grid: import (host rows) and merge_from (another handle's map, read

@@ -135,10 +135,11 @@ struct VoxelMapDev {
     // the map as a point target (fvh_*_target_from_map): selected {keys | buckets}, the sort's (key word, row) pairs x 2 and histograms, the
     // rows on their way into the target cloud, VmTargetCtl. Its own: the Engine-wide sort scratch may belong to a preparation on the second stream
     DevBuf tm_sel, tm_keys, tm_idx, tm_hist, tm_rows, tm_ctl;
+    DevBuf ray_marks;           // fvh_*_clear_rays_*: the per-call miss counters and hit bits, one u32 per bucket (kernels_voxelmap.hpp: vm_raymark_kernel)
     unsigned epoch = 0;         // inserts so far: the stamp of the last one
     long long num_points = 0;   // points offered to the map since map_begin (skipped ones included)
     long long voxel_bound = 0;  // host-side upper bound of the voxel count (exact after a readback)
-    void release() { sums[0].release(); sums[1].release(); stamps[0].release(); stamps[1].release(); dirty.release(); ctl.release(); xfer.release(); tm_sel.release(); tm_keys.release(); tm_idx.release(); tm_hist.release(); tm_rows.release(); tm_ctl.release(); live = false; }
+    void release() { sums[0].release(); sums[1].release(); stamps[0].release(); stamps[1].release(); dirty.release(); ctl.release(); xfer.release(); tm_sel.release(); tm_keys.release(); tm_idx.release(); tm_hist.release(); tm_rows.release(); tm_ctl.release(); ray_marks.release(); live = false; }
   } inc;
   unsigned clean_cap = 0;  // keys[cur ^ 1], counter set cur ^ 1 and acc are clean (EMPTY / 0) over this capacity; 0 = unknown
   int* counters_cur() const { return counters.as<int>() + 16 * cur; }

@@ -1076,4 +1076,132 @@ __global__ __launch_bounds__(256) void vm_target_gather_kernel(const float4* __r
   }
 }
 
+// ---- free space cleared along the rays of a posed scan (fvh_*_clear_rays_*: host_incmap.inc.hpp, incmap_clear_rays) -----------
+// The ray from the sensor origin to a measured point proves the voxels it crosses empty. Two kernels and the existing rehash:
+//   marks : capacity x u32 parallel to the buckets, zeroed per call: bits 0..30 count the rays of THIS call that crossed the voxel (an
+//           integer: the order of the adds does not matter), bit 31 says a ray of this call ended in it.
+//   vm_raymark  one ray per lane: the endpoint's voxel gets bit 31, an Amanatides-Woo walk in fp64 (the contract, operation by operation,
+//               is in include/fast_vgicp_hip.h; tests/clearrays_ref.py restates it) adds 1 to every crossed voxel that exists. The map is
+//               only read: a probe by hash_slot and linear probing to the key or an empty slot.
+//   vm_raysweep one thread per entry of the compact list: a voxel with >= min_misses crossings and no hit is condemned -- its stamp
+//               becomes 0, the value of a bucket nothing ever touched, which no live voxel holds -- and counted in ctl[3].
+// vm_rehash_kernel with max_age = epoch then drops exactly the buckets whose stamp is 0 (epoch - stamp >= epoch); it is launched only
+// when ctl[3] > 0, so a call that removes nothing writes nothing to the map.
+// ctl here: {-, rays used, (the rehash's removed count), voxels condemned}
+constexpr unsigned VM_RAY_HIT = 0x80000000u;
+constexpr int VM_RAY_MAX_STEPS = 3 * 4097;  // what max_range <= 4096 voxels (the host's rule) allows |dc_x| + |dc_y| + |dc_z| to be
+
+struct VmRays {
+  PoseD T;          // scan frame -> map frame
+  float origin[3];  // o' = (float)(R o + t), formed by the host
+  double res, min_range, max_range, end_margin;
+};
+
+__device__ __forceinline__ double ray_range_nofma(double dx, double dy, double dz) {
+#pragma clang fp contract(off)
+  return __dsqrt_rn((dx * dx + dy * dy) + dz * dz);
+}
+
+// read-only lookup: the bucket of `key`, 0xFFFFFFFF when the map has no such voxel
+__device__ __forceinline__ unsigned vm_find_bucket(const unsigned long long* __restrict__ keys, unsigned mask, unsigned long long key) {
+  unsigned slot = hash_slot(key, mask);
+  for (unsigned it = 0; it <= mask; it++) {
+    const unsigned long long k = keys[slot];
+    if (k == key) return slot;
+    if (k == FVH_EMPTY_KEY) break;
+    slot = (slot + 1) & mask;
+  }
+  return 0xFFFFFFFFu;
+}
+// ... of cell (cx, cy, cz). A live bitmap answers for the cells that do not exist (every voxel of the map lies inside its box while it is
+// enabled: vm_refresh_kernel), so the result is the same with and without it.
+__device__ __forceinline__ unsigned ray_cell_bucket(int cx, int cy, int cz, const unsigned long long* __restrict__ keys, unsigned mask, bool use_grid, const VmGrid& g,
+                                                    const unsigned long long* __restrict__ bitmap) {
+  if (!coord_in_range(cx, cy, cz)) return 0xFFFFFFFFu;
+  if (use_grid) {
+    unsigned long long word;
+    unsigned bit;
+    if (!vm_grid_locate(g, (unsigned)(cx + FVH_COORD_BIAS), (unsigned)(cy + FVH_COORD_BIAS), (unsigned)(cz + FVH_COORD_BIAS), word, bit)) return 0xFFFFFFFFu;
+    if (!((bitmap[word] >> bit) & 1ull)) return 0xFFFFFFFFu;
+  }
+  return vm_find_bucket(keys, mask, pack_key(cx, cy, cz));
+}
+
+// One ray per lane; trip counts diverge inside a wave, which is why the host hands the source's Morton order in when it has one
+// (neighbouring lanes then walk rays of similar length through neighbouring cells). p' is formed by the expression vm_insert_kernel bins.
+__global__ __launch_bounds__(256) void vm_raymark_kernel(const float4* __restrict__ pts, int n, const int* __restrict__ order, VmRays ry, const unsigned long long* __restrict__ keys,
+                                                         unsigned mask, unsigned* __restrict__ marks, const VmGrid* __restrict__ grid, const unsigned long long* __restrict__ bitmap,
+                                                         int* __restrict__ ctl) {
+  __shared__ int s_used;
+  if (threadIdx.x == 0) s_used = 0;
+  __syncthreads();
+  const bool use_grid = grid != nullptr && grid->enabled != 0;
+  VmGrid g = {};
+  if (use_grid) g = *grid;
+  const int i0 = blockIdx.x * 256 + threadIdx.x;
+  if (i0 < n) {
+    const int i = order ? order[i0] : i0;
+    const float4 p = pts[i];
+    const PoseD& T = ry.T;
+    const double res = ry.res;
+    const double x = p.x, y = p.y, z = p.z;
+    const float px = (float)(T.r[0] * x + T.r[1] * y + T.r[2] * z + T.t[0]);
+    const float py = (float)(T.r[3] * x + T.r[4] * y + T.r[5] * z + T.t[1]);
+    const float pz = (float)(T.r[6] * x + T.r[7] * y + T.r[8] * z + T.t[2]);
+    const double ax = (double)ry.origin[0] / res - 0.5, ay = (double)ry.origin[1] / res - 0.5, az = (double)ry.origin[2] / res - 0.5;
+    const double bx = (double)px / res - 0.5, by = (double)py / res - 0.5, bz = (double)pz / res - 0.5;
+    const double fax = floor(ax), fay = floor(ay), faz = floor(az), fbx = floor(bx), fby = floor(by), fbz = floor(bz);
+    const double r = ray_range_nofma((double)px - (double)ry.origin[0], (double)py - (double)ry.origin[1], (double)pz - (double)ry.origin[2]);
+    const bool finite_in = isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
+    if (finite_in && !(r == 0.0) && !(r < ry.min_range) && !(r > ry.max_range) && voxel_index_ok(fax, fay, faz) && voxel_index_ok(fbx, fby, fbz)) {
+      atomicAdd(&s_used, 1);
+      int cx = (int)fax, cy = (int)fay, cz = (int)faz;
+      const int ex = (int)fbx, ey = (int)fby, ez = (int)fbz;
+      const unsigned hb = ray_cell_bucket(ex, ey, ez, keys, mask, use_grid, g, bitmap);
+      if (hb != 0xFFFFFFFFu) atomicOr(marks + hb, VM_RAY_HIT);
+      const double dx = bx - ax, dy = by - ay, dz = bz - az;
+      const int sx = dx > 0.0 ? 1 : (dx < 0.0 ? -1 : 0), sy = dy > 0.0 ? 1 : (dy < 0.0 ? -1 : 0), sz = dz > 0.0 ? 1 : (dz < 0.0 ? -1 : 0);
+      const double tdx = 1.0 / fabs(dx), tdy = 1.0 / fabs(dy), tdz = 1.0 / fabs(dz);
+      const double inf = __longlong_as_double(0x7FF0000000000000ll);
+      double tmx = dx > 0.0 ? ((double)(cx + 1) - ax) / dx : (dx < 0.0 ? (ax - (double)cx) / (-dx) : inf);
+      double tmy = dy > 0.0 ? ((double)(cy + 1) - ay) / dy : (dy < 0.0 ? (ay - (double)cy) / (-dy) : inf);
+      double tmz = dz > 0.0 ? ((double)(cz + 1) - az) / dz : (dz < 0.0 ? (az - (double)cz) / (-dz) : inf);
+      const double t_end = 1.0 - ry.end_margin / r;
+      const int nsteps = min(abs(ex - cx) + abs(ey - cy) + abs(ez - cz), VM_RAY_MAX_STEPS);
+      double t_in = 0.0;
+#pragma unroll 1
+      for (int step = 0; t_in < t_end; step++) {
+        const unsigned b = ray_cell_bucket(cx, cy, cz, keys, mask, use_grid, g, bitmap);
+        if (b != 0xFFFFFFFFu) atomicAdd(marks + b, 1u);  // (result unused: a no-return atomic)
+        if (step == nsteps) break;
+        if (tmx <= tmy && tmx <= tmz) { t_in = tmx; cx += sx; tmx += tdx; }       // ties: x before y before z
+        else if (tmy <= tmz) { t_in = tmy; cy += sy; tmy += tdy; }
+        else { t_in = tmz; cz += sz; tmz += tdz; }
+      }
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && s_used) atomicAdd(ctl + 1, s_used);
+}
+
+// n_bound: the voxel count the host sized the grid for (its bound; the count itself is read here)
+__global__ __launch_bounds__(256) void vm_raysweep_kernel(const int* __restrict__ occupied, const int* __restrict__ counters, int n_bound, const unsigned* __restrict__ marks,
+                                                          unsigned min_misses, unsigned* __restrict__ stamps, int* __restrict__ ctl) {
+  __shared__ int s_cnt;
+  if (threadIdx.x == 0) s_cnt = 0;
+  __syncthreads();
+  const int n = min(counters[0], n_bound);
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) {
+    const unsigned b = (unsigned)occupied[i];
+    const unsigned m = marks[b];
+    if (!(m & VM_RAY_HIT) && m >= min_misses) {  // (no hit bit: m is the count)
+      stamps[b] = 0u;
+      atomicAdd(&s_cnt, 1);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && s_cnt) atomicAdd(ctl + 3, s_cnt);
+}
+
 }  // namespace fvh

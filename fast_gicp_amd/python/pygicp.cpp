@@ -280,6 +280,19 @@ static void def_incremental_target(PyClass& c) {
         if (c.size() != 3) throw std::invalid_argument("prune_target: center must have 3 elements");
         return v.pruneTarget(c.data(), radius, max_age);
       }, py::arg("center") = py::none(), py::arg("radius") = 0.0, py::arg("max_age") = 0)
+      // free-space carving (fvh_*_clear_rays_source): the voxels that >= min_misses rays origin -> source point at `pose` cross and none ends
+      // in are dropped; call it before insert_source_into_target(pose). -> (voxels removed, rays used)
+      .def("clear_target_rays", [](Reg& v, const Mat4& pose, const py::object& origin, double min_range, double max_range, double end_margin, int min_misses) {
+        fast_gicp::RayClearing r;
+        if (origin.is_none()) {
+          r = v.clearTargetAlongRays(numpy2mat4(pose), nullptr, min_range, max_range, end_margin, min_misses);
+        } else {
+          const auto o = origin.cast<py::array_t<double, py::array::c_style | py::array::forcecast>>();
+          if (o.size() != 3) throw std::invalid_argument("clear_target_rays: origin must have 3 elements");
+          r = v.clearTargetAlongRays(numpy2mat4(pose), o.data(), min_range, max_range, end_margin, min_misses);
+        }
+        return py::make_tuple(r.removed, r.rays_used);
+      }, py::arg("pose"), py::arg("origin") = py::none(), py::arg("min_range") = 0.0, py::arg("max_range") = 100.0, py::arg("end_margin") = 0.0, py::arg("min_misses") = 1)
       // the map as the handle's target cloud too (one point per voxel with >= min_points points; a snapshot): get_fitness_score() and
       // align_best() then work in this mode. -> number of points
       .def("target_cloud_from_map", [](Reg& v, int min_points) { return v.targetCloudFromMap(min_points); }, py::arg("min_points") = 1)

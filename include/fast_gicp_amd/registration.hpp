@@ -547,6 +547,9 @@ protected:
   Matrix6d final_hessian_;
 };
 
+/// what clearTargetAlongRays() reports: voxels removed, rays that were walked (not skipped)
+struct RayClearing { int removed = 0, rays_used = 0; };
+
 /// A snapshot of an incremental target map (FastVGICPCuda / NDTCuda exportTargetMap / importTargetMap; C ABI: fvh_vgicp_voxelmap_export /
 /// _import, fvh_ndt_voxelmap_export / _import): per voxel coords[3], the device's ten fp64 sums and an age, rows in ascending packed-key
 /// order (z-major, then y, then x).
@@ -623,6 +626,7 @@ struct MapCalls<fvh_vgicp> {
   static int begin(fvh_vgicp* h, int expected_voxels) { return fvh_vgicp_map_begin(h, expected_voxels); }
   static int insert_source(fvh_vgicp* h, const double* T16) { return fvh_vgicp_map_insert_source(h, T16); }
   static int prune(fvh_vgicp* h, const double* c3, double radius, int max_age, int* removed) { return fvh_vgicp_map_prune(h, c3, radius, max_age, removed); }
+  static int clear_rays_source(fvh_vgicp* h, const double* T16, const double* origin3, double min_range, double max_range, double end_margin, int min_misses, int* removed, int* rays_used) { return fvh_vgicp_clear_rays_source(h, T16, origin3, min_range, max_range, end_margin, min_misses, removed, rays_used); }
   static int export_rows(fvh_vgicp* h, int* n, double* res, int* mode, int* inserts, long long* points, int* coords, double* sums, unsigned* ages) { return fvh_vgicp_voxelmap_export(h, n, res, mode, inserts, points, coords, sums, ages); }
   static int import_rows(fvh_vgicp* h, int n, const int* coords, const double* sums, const unsigned* ages, double res, int mode, int inserts, long long points) { return fvh_vgicp_voxelmap_import(h, n, coords, sums, ages, res, mode, inserts, points); }
   static int merge_from(fvh_vgicp* h, fvh_vgicp* other) { return fvh_vgicp_voxelmap_merge_from(h, other); }
@@ -635,6 +639,7 @@ struct MapCalls<fvh_ndt> {
   static int begin(fvh_ndt* h, int expected_voxels) { return fvh_ndt_map_begin(h, expected_voxels); }
   static int insert_source(fvh_ndt* h, const double* T16) { return fvh_ndt_map_insert_source(h, T16); }
   static int prune(fvh_ndt* h, const double* c3, double radius, int max_age, int* removed) { return fvh_ndt_map_prune(h, c3, radius, max_age, removed); }
+  static int clear_rays_source(fvh_ndt* h, const double* T16, const double* origin3, double min_range, double max_range, double end_margin, int min_misses, int* removed, int* rays_used) { return fvh_ndt_clear_rays_source(h, T16, origin3, min_range, max_range, end_margin, min_misses, removed, rays_used); }
   static int export_rows(fvh_ndt* h, int* n, double* res, int* mode, int* inserts, long long* points, int* coords, double* sums, unsigned* ages) { return fvh_ndt_voxelmap_export(h, n, res, mode, inserts, points, coords, sums, ages); }
   static int import_rows(fvh_ndt* h, int n, const int* coords, const double* sums, const unsigned* ages, double res, int mode, int inserts, long long points) { return fvh_ndt_voxelmap_import(h, n, coords, sums, ages, res, mode, inserts, points); }
   static int merge_from(fvh_ndt* h, fvh_ndt* other) { return fvh_ndt_voxelmap_merge_from(h, other); }
@@ -722,6 +727,18 @@ protected:
     int removed = 0;
     call(Map::prune(core_, center3, radius, max_age, &removed), "map_prune");
     return removed;
+  }
+  /// Free-space carving (fvh_*_clear_rays_source): drops the voxels that at least min_misses rays of this call cross and none ends in. The
+  /// rays run from origin3 (scan frame; null: the origin) to the current source points, all at pose T -- the pose insertSourceIntoTarget(T)
+  /// would add the scan at: call this first, then insert. Rays outside [min_range, max_range] metres are skipped and a walk stops end_margin
+  /// metres in front of its endpoint; end_margin (a voxel or two) and min_misses > 1 keep grazing rays from eroding the ground.
+  RayClearing clearTargetAlongRays(const Matrix4f& T, const double* origin3 = nullptr, double min_range = 0.0, double max_range = 100.0, double end_margin = 0.0, int min_misses = 1) {
+    if (!this->input_) throw std::invalid_argument("clearTargetAlongRays: source cloud not set");
+    double T16[16];
+    Isometry3d::from(T).to_colmajor16(T16);
+    RayClearing out;
+    call(Map::clear_rays_source(core_, T16, origin3, min_range, max_range, end_margin, min_misses, &out.removed, &out.rays_used), "clear_rays_source");
+    return out;
   }
   bool hasIncrementalTarget() const { return incremental_target_; }
   /// The live map becomes the handle's target CLOUD as well: one point per voxel with >= min_points points (the voxel's mean; VGICP: + its
@@ -984,6 +1001,7 @@ public:
   using Base::beginIncrementalTarget;
   using Base::insertSourceIntoTarget;
   using Base::pruneTarget;
+  using Base::clearTargetAlongRays;
   using Base::hasIncrementalTarget;
   using Base::targetCloudFromMap;
 
@@ -1245,6 +1263,7 @@ public:
   using Base::beginIncrementalTarget;
   using Base::insertSourceIntoTarget;
   using Base::pruneTarget;
+  using Base::clearTargetAlongRays;
   using Base::hasIncrementalTarget;
   using Base::targetCloudFromMap;
   using Base::exportTargetMap;

@@ -275,6 +275,46 @@ int fvh_vgicp_map_insert_source(fvh_vgicp* h, const double* T16);
 int fvh_vgicp_map_insert_cloud(fvh_vgicp* h, const float* xyz, int n, int stride_floats, const double* covs9, const double* T16, int on_device);
 int fvh_vgicp_map_prune(fvh_vgicp* h, const double* center3, double radius, int max_age, int* num_removed);
 int fvh_vgicp_map_get_info(fvh_vgicp* h, int* incremental, int* num_voxels, int* capacity, int* num_inserts, long long* num_points, int* num_dropped);
+/* new: FREE-SPACE CARVING. The ray from the sensor to a measured point proves the voxels it crosses empty: a voxel written by a car, a
+ * pedestrian or an opening door is removed by the next scan that sees through it, instead of staying until map_prune's distance or age rule
+ * also takes the static structure around it. On the device: one 3D grid walk per ray, a sweep, and -- only if something goes -- the rehash
+ * map_prune drives. The intended loop is align, clear_rays_source(T), map_insert_source(T).
+ *   _source   the rays end at the handle's current source points (no covariances needed), walked in the source's Morton order when it has one.
+ *   _cloud    ... at xyz: n points on the host or the device (on_device), stride_floats 3 or 4, as fvh_vgicp_map_insert_cloud takes them.
+ *   T16       4x4 double column-major, scan frame -> map frame (R, t); origin3 the sensor origin in the SCAN frame, NULL = (0, 0, 0).
+ *   min_range, max_range   metres; rays shorter / longer are skipped.  end_margin: metres in front of the endpoint the walk stops at.
+ *   min_misses             a voxel goes when at least this many rays of THIS call crossed it and none ended in it.
+ * end_margin and min_misses are the knobs against grazing rays eroding the ground: a ray that runs along a surface crosses the voxels of that
+ * surface just before it ends; end_margin (a voxel or two) keeps the walk out of them, min_misses > 1 asks for several witnesses.
+ * The contract (res = the map's resolution; voxel c covers grid coordinates [c, c + 1) per axis; the grid coordinate of a metric value x is
+ * x / res - 0.5 in fp64, the expression an insert bins with):
+ *   origin    o' = (float)(R o + t) per axis: ((r0 x + r1 y) + r2 z) + t in fp64, no product contracted into a sum, rounded once.
+ *   endpoint  p'_i = (float)(R p_i + t): the bits an insert of the same point at the same pose bins, so a ray ends in the voxel the insert
+ *             would put its point in.
+ *   range     d_m = (double)p' - (double)o' per axis; r = sqrt((dx*dx + dy*dy) + dz*dz) in fp64, no product contracted into a sum.
+ *   skipped   (not counted in *rays_used) when a coordinate of p_i is non-finite, r == 0, r < min_range, r > max_range, or the cell of o' or
+ *             of p' is outside |c| < 2^20 - 4096.
+ *   hit       with b the grid coordinate of p': the voxel floor(b) of every used ray is protected for this call if it exists.
+ *   walk      (Amanatides-Woo, fp64) a = the grid coordinate of o', d = b - a, c = floor(a); per axis s = sign(d), tDelta = 1.0 / fabs(d),
+ *             tMax = ((double)(c + 1) - a) / d for d > 0, (a - (double)c) / (-d) for d < 0, +inf for d == 0; t_end = 1.0 - end_margin / r;
+ *             N = |dc_x| + |dc_y| + |dc_z| with dc = floor(b) - floor(a). t_in = 0; repeat: stop unless t_in < t_end; the current cell is
+ *             CROSSED; stop if N steps have been taken; take the axis of the smallest tMax (ties: x before y before z): t_in = tMax[axis],
+ *             c[axis] += s[axis], tMax[axis] += tDelta[axis]. One axis per step: at most N + 1 cells, never past the endpoint's cell.
+ *   miss      every crossed cell that exists in the map gets its per-call counter incremented (an integer: order does not matter).
+ *   removal   after all rays a voxel is removed iff misses >= min_misses and it is not protected. Survivors keep their full sums, their ages
+ *             and their records, bit for bit.
+ * Insert count and num_points are unchanged. When something was removed the table is rewritten by the rehash at the same capacity, the
+ * bitmap rebuilt, stored correspondences cleared. When NOTHING was removed the map is not touched: no rehash, an export before and after is
+ * byte-equal, stored correspondences are kept. *num_removed and *rays_used may be NULL; the call synchronises once to read its counts, as
+ * map_prune does. The miss counters live for one call: nothing is added to the snapshot format (a hit / miss count kept across calls
+ * is a different feature).
+ * Refusals (the handle and its map stay as they were; host input is validated before anything is queued): no live incremental map, an
+ * align_async in flight, _source without a source cloud (FVH_ERR_BAD_STATE); a NULL or non-finite T16, a non-finite origin3, min_range < 0
+ * or NaN, max_range not finite or < min_range or > 4096 * res (one lane then walks at most 3 * 4097 = 12,291 cells), end_margin < 0 or
+ * not finite, min_misses < 1, n < 0, NULL xyz with n > 0, a stride other than 3 or 4 (FVH_ERR_INVALID_ARGUMENT); multi-GPU handles
+ * (communicator, peers, tile, map sharding) and FVH_COMPUTE_CUDA_COMPAT (FVH_ERR_UNSUPPORTED). n == 0: FVH_OK, nothing removed. */
+int fvh_vgicp_clear_rays_source(fvh_vgicp* h, const double* T16, const double* origin3, double min_range, double max_range, double end_margin, int min_misses, int* num_removed, int* rays_used);
+int fvh_vgicp_clear_rays_cloud(fvh_vgicp* h, const float* xyz, int n, int stride_floats, int on_device, const double* T16, const double* origin3, double min_range, double max_range, double end_margin, int min_misses, int* num_removed, int* rays_used);
 /* Snapshots of the live incremental map: write it out, bring it back, add another map to it.
  * A snapshot is a header -- resolution, mode (0 additive, 2 multiplicative), num_inserts (the map's insert count), num_points, num_voxels --
  * and per voxel coords[3] (int32), sums[10] (fp64: {sum p | sum C^-1 p (3), sum C | sum C^-1 (6), count}, the device's own sums) and an age
@@ -547,6 +587,9 @@ int fvh_ndt_map_insert_source(fvh_ndt* h, const double* T16);
 int fvh_ndt_map_insert_cloud(fvh_ndt* h, const float* xyz, int n, int stride_floats, const double* T16, int on_device);
 int fvh_ndt_map_prune(fvh_ndt* h, const double* center3, double radius, int max_age, int* num_removed);
 int fvh_ndt_map_get_info(fvh_ndt* h, int* incremental, int* num_voxels, int* capacity, int* num_inserts, long long* num_points, int* num_dropped);
+/* free-space carving, as fvh_vgicp_clear_rays_source / _cloud above, argument for argument and under the same contract */
+int fvh_ndt_clear_rays_source(fvh_ndt* h, const double* T16, const double* origin3, double min_range, double max_range, double end_margin, int min_misses, int* num_removed, int* rays_used);
+int fvh_ndt_clear_rays_cloud(fvh_ndt* h, const float* xyz, int n, int stride_floats, int on_device, const double* T16, const double* origin3, double min_range, double max_range, double end_margin, int min_misses, int* num_removed, int* rays_used);
 int fvh_ndt_voxelmap_export(fvh_ndt* h, int* num_voxels, double* resolution, int* mode, int* num_inserts, long long* num_points, int* coords3, double* sums10, unsigned* ages);
 int fvh_ndt_voxelmap_import(fvh_ndt* h, int n, const int* coords3, const double* sums10, const unsigned* ages, double resolution, int mode, int num_inserts, long long num_points);
 int fvh_ndt_voxelmap_merge_from(fvh_ndt* h, fvh_ndt* other);
