@@ -48,6 +48,12 @@ def default_engine_params():
     return p
 
 
+class MapScore(C.Structure):
+    """fvh_map_score (include/fast_vgicp_hip.h): what fvh_*_score_source / _score_cloud report"""
+    _fields_ = [("n_points", C.c_int), ("n_used", C.c_int), ("n_in_voxel", C.c_int), ("n_near", C.c_int), ("n_explained", C.c_int),
+                ("sum_best_m2", C.c_double), ("sum_score_max", C.c_double), ("sum_score_all", C.c_double)]
+
+
 class FvhError(RuntimeError):
     pass
 
@@ -332,6 +338,50 @@ class _RayClearing:
         else:
             self._call("clear_rays_source", *tail)
         return removed.value, used.value
+
+
+class _MapScoring:
+    """A posed scan scored against the handle's target voxel map, batch or incremental (include/fast_vgicp_hip.h: fvh_{vgicp,ndt}_score_source /
+    _score_cloud): mixed into VGICPMapCore and NDTMapCore, the handle classes for scan-to-map work."""
+
+    def map_score(self, T=None, xyz=None, device_ptr=None, n=None, stride=3, neighbors=DIRECT7, min_points=1, max_m2=float("inf"), score_scale=1.0, per_point=False):
+        """How well the map explains a scan at pose T (4x4, default identity): the current source points (xyz and device_ptr None), the host points
+        xyz (m, 3), or n device points at device_ptr (stride 3 or 4 floats). Around every point the voxels of `neighbors` (DIRECT1 / DIRECT7 /
+        DIRECT27) with >= min_points points are looked up; a point is explained when its best squared Mahalanobis distance is finite and <= max_m2; scores
+        are exp(-0.5 * score_scale * m2). Read-only on the handle. -> dict of the struct's fields plus overlap = n_in_voxel / n_used, nvtl =
+        sum_score_max / n_near, tp = sum_score_all / n_used (NaN on a zero denominator); per_point adds found, best (int32) and best_m2
+        (float64), one row per point in input order (skipped points: -1, -1, NaN)."""
+        t = _IDENTITY16 if T is None else _colmajor16(T)
+        out = MapScore()
+        head = (_p(t), int(neighbors), int(min_points), C.c_double(max_m2), C.c_double(score_scale), C.byref(out))
+        if device_ptr is not None:
+            m = int(n)
+        elif xyz is not None:
+            a = _f32(xyz).reshape(-1, 3)
+            m = len(a)
+        else:  # the rows a source score writes are the source cloud's
+            cnt = C.c_int(0)
+            if per_point:
+                self._call("get_num_source_points", C.byref(cnt))
+            m = cnt.value
+        found = np.empty(m, np.int32) if per_point else None
+        best = np.empty(m, np.int32) if per_point else None
+        best_m2 = np.empty(m, np.float64) if per_point else None
+        rows = tuple(_p(v) if per_point and m else None for v in (found, best, best_m2))
+        if device_ptr is not None:
+            self._call("score_cloud", C.c_void_p(device_ptr), m, int(stride), 1, *head, *rows)
+        elif xyz is not None:
+            self._call("score_cloud", _p(a) if m else None, m, 3, 0, *head, *rows)
+        else:
+            self._call("score_source", *head, *rows)
+        r = {name: getattr(out, name) for name, _ in MapScore._fields_}
+        nan = float("nan")
+        r["overlap"] = r["n_in_voxel"] / r["n_used"] if r["n_used"] else nan
+        r["nvtl"] = r["sum_score_max"] / r["n_near"] if r["n_near"] else nan
+        r["tp"] = r["sum_score_all"] / r["n_used"] if r["n_used"] else nan
+        if per_point:
+            r["found"], r["best"], r["best_m2"] = found, best, best_m2
+        return r
 
 
 class _MapTarget:
@@ -865,7 +915,7 @@ class VGICPCore(_Core, _IncrementalMap):
         return n.value
 
 
-class VGICPMapCore(VGICPCore, _MapTarget, _PosedMap, _RayClearing):
+class VGICPMapCore(VGICPCore, _MapTarget, _PosedMap, _RayClearing, _MapScoring):
     """A VGICP handle for scan-to-map work: VGICPCore (which has the map_* calls) + target_from_map / get_target_points, on the same C handle
     type -- as NDTMapCore is to NDTCore."""
 
@@ -1174,7 +1224,7 @@ class NDTCore(_Core):
         return coords, num, means, covs
 
 
-class NDTMapCore(NDTCore, _IncrementalMap, _MapTarget, _PosedMap, _RayClearing):
+class NDTMapCore(NDTCore, _IncrementalMap, _MapTarget, _PosedMap, _RayClearing, _MapScoring):
     """An NDT handle with the calls of its incremental target map (include/fast_vgicp_hip.h: fvh_ndt_map_* / fvh_ndt_voxelmap_*): map_begin,
     map_insert_source, map_prune, map_info, map_export, map_import, map_merge_from, map_save come from _IncrementalMap as on VGICPCore; NDT
     voxels take points only. Everything else is NDTCore's, on the same C handle type."""

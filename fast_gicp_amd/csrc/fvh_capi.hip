@@ -30,6 +30,7 @@
 #include "kernels_peer.hpp"
 #include "kernels_sort.hpp"
 #include "kernels_voxelmap.hpp"
+#include "kernels_mapscore.hpp"
 
 using namespace fvh;
 
@@ -519,6 +520,7 @@ struct fvh_vgicp {
     return FVH_OK;
   }
   const char* not_a_merge_source() const { return e.sharded() || shard_map || e.precision == FVH_COMPUTE_CUDA_COMPAT ? "multi-GPU / sharded / FVH_COMPUTE_CUDA_COMPAT" : nullptr; }
+  bool multi_gpu() const { return e.sharded() || shard_map; }  // communicator, peers, tile, map sharding: the live map may be one rank's shard
   int map_begin_mode() const { return voxel_mode == 2 ? 2 : 0; }  // (ADDITIVE_WEIGHTED: the additive voxel type)
   void before_map_begin() { live_map_stale = false; }
   void after_map_begin() {}
@@ -616,6 +618,7 @@ struct fvh_ndt {
     return FVH_OK;
   }
   const char* not_a_merge_source() const { return e.sharded() || e.precision == FVH_COMPUTE_CUDA_COMPAT ? "multi-GPU / FVH_COMPUTE_CUDA_COMPAT" : nullptr; }
+  bool multi_gpu() const { return e.sharded(); }
   int map_begin_mode() const { return 1; }
   void before_map_begin() {}
   void after_map_begin() { target_newer = false; }
@@ -837,6 +840,49 @@ int map_clear_rays(H* h, bool from_source, const float* xyz, int n, int stride_f
   { const int rc = upload_cloud(&h->e, h->insert_cloud, xyz, n, stride_floats, on_device != 0, false); if (rc) return rc; }
   return incmap_clear_rays(&h->e, h->target_map(), h->insert_cloud, nullptr, T16, origin3, min_range, max_range, end_margin, min_misses, num_removed, rays_used);
 }
+// a posed scan scored against the CURRENT target voxel map (batch or incremental), per point. from_source: the handle's source points, walked in
+// their Morton order when there is one; else xyz (n, stride_floats, on_device) -- host points are staged in the map's own buffer, device
+// points are read where they are. Read-only on the handle; a batch map whose hint-sized table had overflowed is rebuilt first, as align does.
+template <class H>
+int map_score(H* h, bool from_source, const float* xyz, int n, int stride_floats, int on_device, const double* T16, int neighbors, int min_points, double max_m2, double score_scale,
+              fvh_map_score* out, int* found, int* best, double* best_m2) {
+  const char* who = from_source ? "score_source" : "score_cloud";
+  Engine* e = &h->e;
+  if (h->multi_gpu()) return e->fail(FVH_ERR_UNSUPPORTED, std::string(who) + ": not on a multi-GPU handle (communicator / peers / tile / map sharding)");
+  VoxelMapDev& vm = h->target_map();
+  if (!vm.valid || vm.capacity == 0) return e->fail(FVH_ERR_BAD_STATE, std::string(who) + ": no target voxel map (create_target_voxelmap or " + H::prefix + "_map_begin)");
+  if (from_source && !h->source.has_pts) return e->fail(FVH_ERR_BAD_STATE, std::string(who) + ": the source cloud is not set");
+  { const int rc = map_score_check(e, T16, neighbors, max_m2, score_scale, out, who); if (rc) return rc; }
+  const float* d_xyz = nullptr;
+  const int* order = nullptr;
+  int stride = 4;
+  if (from_source) {
+    n = h->source.n;
+    d_xyz = h->source.pts.template as<float>();
+    order = coherent_order(h->source, e->params.coherent_min_points);
+  } else {
+    if (n < 0) return e->fail(FVH_ERR_INVALID_ARGUMENT, std::string(who) + ": n < 0");
+    if (n > 0 && !xyz) return e->fail(FVH_ERR_INVALID_ARGUMENT, std::string(who) + ": null points with n > 0");
+    if (stride_floats != 3 && stride_floats != 4) return e->fail(FVH_ERR_INVALID_ARGUMENT, std::string(who) + ": stride must be 3 or 4 floats");
+    stride = stride_floats;
+    d_xyz = xyz;
+    if (!on_device && n > 0) {
+      const size_t bytes = sizeof(float) * (size_t)stride * (size_t)n;
+      HIP_OR_FAIL(e, vm.score_xyz.ensure(bytes));
+      HIP_OR_FAIL(e, hipMemcpyAsync(vm.score_xyz.p, xyz, bytes, hipMemcpyHostToDevice, e->stream));
+      d_xyz = vm.score_xyz.template as<float>();
+    }
+  }
+  for (int attempt = 0;; attempt++) {
+    bool overflowed = false;
+    { const int rc = map_score_run(e, h->target_map(), d_xyz, stride, n, order, T16, neighbors, min_points, max_m2, score_scale, out, found, best, best_m2, &overflowed); if (rc) return rc; }
+    if (!overflowed) break;
+    if (attempt == 1) return e->fail(FVH_ERR_BAD_STATE, std::string(who) + ": voxel map overflow persists after safe rebuild");
+    { const int rc = h->rebuild_safe()(); if (rc) return rc; }
+  }
+  out->n_points = n;
+  return FVH_OK;
+}
 template <class H>
 int map_get_info(H* h, int* incremental, int* num_voxels, int* capacity, int* num_inserts, long long* num_points, int* num_dropped) {
   VoxelMapDev& vm = h->target_map();
@@ -945,6 +991,8 @@ int fvh_vgicp_map_insert_cloud(fvh_vgicp* h, const float* xyz, int n, int stride
 int fvh_vgicp_map_prune(fvh_vgicp* h, const double* center3, double radius, int max_age, int* num_removed) { CHECK_HANDLE(h); return shared::map_prune(h, center3, radius, max_age, num_removed); }
 int fvh_vgicp_clear_rays_source(fvh_vgicp* h, const double* T16, const double* origin3, double min_range, double max_range, double end_margin, int min_misses, int* num_removed, int* rays_used) { CHECK_HANDLE(h); return shared::map_clear_rays(h, true, nullptr, 0, 3, 0, T16, origin3, min_range, max_range, end_margin, min_misses, num_removed, rays_used); }
 int fvh_vgicp_clear_rays_cloud(fvh_vgicp* h, const float* xyz, int n, int stride_floats, int on_device, const double* T16, const double* origin3, double min_range, double max_range, double end_margin, int min_misses, int* num_removed, int* rays_used) { CHECK_HANDLE(h); return shared::map_clear_rays(h, false, xyz, n, stride_floats, on_device, T16, origin3, min_range, max_range, end_margin, min_misses, num_removed, rays_used); }
+int fvh_vgicp_score_source(fvh_vgicp* h, const double* T16, int neighbors, int min_points, double max_m2, double score_scale, fvh_map_score* out, int* found, int* best, double* best_m2) { CHECK_HANDLE(h); return shared::map_score(h, true, nullptr, 0, 4, 1, T16, neighbors, min_points, max_m2, score_scale, out, found, best, best_m2); }
+int fvh_vgicp_score_cloud(fvh_vgicp* h, const float* xyz, int n, int stride_floats, int on_device, const double* T16, int neighbors, int min_points, double max_m2, double score_scale, fvh_map_score* out, int* found, int* best, double* best_m2) { CHECK_HANDLE(h); return shared::map_score(h, false, xyz, n, stride_floats, on_device, T16, neighbors, min_points, max_m2, score_scale, out, found, best, best_m2); }
 int fvh_vgicp_map_get_info(fvh_vgicp* h, int* incremental, int* num_voxels, int* capacity, int* num_inserts, long long* num_points, int* num_dropped) { CHECK_HANDLE(h); return shared::map_get_info(h, incremental, num_voxels, capacity, num_inserts, num_points, num_dropped); }
 int fvh_vgicp_voxelmap_export(fvh_vgicp* h, int* num_voxels, double* resolution, int* mode, int* num_inserts, long long* num_points, int* coords3, double* sums10, unsigned* ages) { CHECK_HANDLE(h); return shared::voxelmap_export(h, num_voxels, resolution, mode, num_inserts, num_points, coords3, sums10, ages); }
 int fvh_vgicp_voxelmap_import(fvh_vgicp* h, int n, const int* coords3, const double* sums10, const unsigned* ages, double resolution, int mode, int num_inserts, long long num_points) { CHECK_HANDLE(h); return shared::voxelmap_import(h, n, coords3, sums10, ages, resolution, mode, num_inserts, num_points); }
@@ -1618,6 +1666,8 @@ int fvh_ndt_map_insert_cloud(fvh_ndt* h, const float* xyz, int n, int stride_flo
 int fvh_ndt_map_prune(fvh_ndt* h, const double* center3, double radius, int max_age, int* num_removed) { CHECK_HANDLE(h); return shared::map_prune(h, center3, radius, max_age, num_removed); }
 int fvh_ndt_clear_rays_source(fvh_ndt* h, const double* T16, const double* origin3, double min_range, double max_range, double end_margin, int min_misses, int* num_removed, int* rays_used) { CHECK_HANDLE(h); return shared::map_clear_rays(h, true, nullptr, 0, 3, 0, T16, origin3, min_range, max_range, end_margin, min_misses, num_removed, rays_used); }
 int fvh_ndt_clear_rays_cloud(fvh_ndt* h, const float* xyz, int n, int stride_floats, int on_device, const double* T16, const double* origin3, double min_range, double max_range, double end_margin, int min_misses, int* num_removed, int* rays_used) { CHECK_HANDLE(h); return shared::map_clear_rays(h, false, xyz, n, stride_floats, on_device, T16, origin3, min_range, max_range, end_margin, min_misses, num_removed, rays_used); }
+int fvh_ndt_score_source(fvh_ndt* h, const double* T16, int neighbors, int min_points, double max_m2, double score_scale, fvh_map_score* out, int* found, int* best, double* best_m2) { CHECK_HANDLE(h); return shared::map_score(h, true, nullptr, 0, 4, 1, T16, neighbors, min_points, max_m2, score_scale, out, found, best, best_m2); }
+int fvh_ndt_score_cloud(fvh_ndt* h, const float* xyz, int n, int stride_floats, int on_device, const double* T16, int neighbors, int min_points, double max_m2, double score_scale, fvh_map_score* out, int* found, int* best, double* best_m2) { CHECK_HANDLE(h); return shared::map_score(h, false, xyz, n, stride_floats, on_device, T16, neighbors, min_points, max_m2, score_scale, out, found, best, best_m2); }
 int fvh_ndt_map_get_info(fvh_ndt* h, int* incremental, int* num_voxels, int* capacity, int* num_inserts, long long* num_points, int* num_dropped) { CHECK_HANDLE(h); return shared::map_get_info(h, incremental, num_voxels, capacity, num_inserts, num_points, num_dropped); }
 int fvh_ndt_voxelmap_export(fvh_ndt* h, int* num_voxels, double* resolution, int* mode, int* num_inserts, long long* num_points, int* coords3, double* sums10, unsigned* ages) { CHECK_HANDLE(h); return shared::voxelmap_export(h, num_voxels, resolution, mode, num_inserts, num_points, coords3, sums10, ages); }
 int fvh_ndt_voxelmap_import(fvh_ndt* h, int n, const int* coords3, const double* sums10, const unsigned* ages, double resolution, int mode, int num_inserts, long long num_points) { CHECK_HANDLE(h); return shared::voxelmap_import(h, n, coords3, sums10, ages, resolution, mode, num_inserts, num_points); }
@@ -1625,6 +1675,7 @@ int fvh_ndt_voxelmap_merge_from(fvh_ndt* h, fvh_ndt* other) { CHECK_HANDLE(h); r
 int fvh_ndt_posed_merge_from(fvh_ndt* h, fvh_ndt* other, const double* T16, int* rows_skipped) { CHECK_HANDLE(h); return shared::voxelmap_merge_from_posed(h, other, T16, rows_skipped); }
 int fvh_ndt_transform_map(fvh_ndt* h, const double* T16, int* rows_skipped) { CHECK_HANDLE(h); return shared::map_transform(h, T16, rows_skipped); }
 int fvh_ndt_target_from_map(fvh_ndt* h, int min_points, int* num_points_out) { CHECK_HANDLE(h); return shared::target_from_map(h, min_points, num_points_out); }
+int fvh_ndt_get_num_source_points(const fvh_ndt* h, int* n) { if (!h || !n) return FVH_ERR_INVALID_ARGUMENT; *n = h->source.has_pts ? h->source.n : 0; return FVH_OK; }
 int fvh_ndt_get_num_target_points(const fvh_ndt* h, int* n) { return shared::get_num_target_points(h, n); }
 int fvh_ndt_get_target_points(fvh_ndt* h, float* xyz3) { CHECK_HANDLE(h); return shared::get_points_host(&h->e, h->target, xyz3, "get_target_points"); }
 static int ndt_ready(fvh_ndt* h) {

@@ -275,6 +275,73 @@ int incmap_clear_rays(Engine* e, VoxelMapDev& vm, const CloudDev& c, const int* 
   return FVH_OK;
 }
 
+// ---- a posed scan scored against the target voxel map, per point (fvh_*_score_source / _score_cloud; kernels_mapscore.hpp) -----------------
+static_assert(sizeof(fvh_map_score) == sizeof(VmScoreOut) && offsetof(fvh_map_score, n_explained) == offsetof(VmScoreOut, n_explained) &&
+              offsetof(fvh_map_score, sum_best_m2) == offsetof(VmScoreOut, sum_best_m2) && offsetof(fvh_map_score, sum_score_all) == offsetof(VmScoreOut, sum_score_all),
+              "VmScoreOut is the device image of fvh_map_score");
+// what the host refuses before anything is queued (the cloud's own arguments -- n, xyz, stride -- are the caller's)
+int map_score_check(Engine* e, const double* T16, int neighbors, double max_m2, double score_scale, const fvh_map_score* out, const char* who) {
+  const std::string w(who);
+  if (!T16) return e->fail(FVH_ERR_INVALID_ARGUMENT, w + ": null pose");
+  for (int i = 0; i < 16; i++)
+    if (!std::isfinite(T16[i])) return e->fail(FVH_ERR_INVALID_ARGUMENT, w + ": the pose is not finite");
+  if (!out) return e->fail(FVH_ERR_INVALID_ARGUMENT, w + ": null result");
+  if (neighbors != FVH_DIRECT1 && neighbors != FVH_DIRECT7 && neighbors != FVH_DIRECT27) return e->fail(FVH_ERR_INVALID_ARGUMENT, w + ": neighbors must be FVH_DIRECT1, FVH_DIRECT7 or FVH_DIRECT27");
+  if (!(max_m2 >= 0.0)) return e->fail(FVH_ERR_INVALID_ARGUMENT, w + ": max_m2 must be >= 0");
+  if (!std::isfinite(score_scale) || !(score_scale > 0.0)) return e->fail(FVH_ERR_INVALID_ARGUMENT, w + ": score_scale must be finite and > 0");
+  return FVH_OK;
+}
+
+// n points at d_xyz (device, `stride` floats apart; `order`: the walk order or null) at pose T16 against `vm`: the score kernel, the two-level
+// fixed-order sum, ONE readback of the struct (+ the per-point rows that were asked for). Nothing of the engine or the map is written; the
+// scratch is the map's own. Arguments checked by map_score_check. *overflowed: the map's table had dropped points (a hint-sized batch build):
+// `out` is then not valid, the caller rebuilds the map and calls again.
+int map_score_run(Engine* e, VoxelMapDev& vm, const float* d_xyz, int stride, int n, const int* order, const double* T16, int neighbors, int min_points, double max_m2, double score_scale,
+              fvh_map_score* out, int* found, int* best, double* best_m2, bool* overflowed) {
+  *overflowed = false;
+  std::memset(out, 0, sizeof(*out));
+  if (n == 0) return FVH_OK;
+  const int nb = (n + VM_SCORE_CHUNK - 1) / VM_SCORE_CHUNK;
+  // {VmScoreOut (64 B) | 3 nb chunk sums | 3 n terms | n best m2 | n found | n best}
+  const size_t off_chunk = 64, off_terms = off_chunk + sizeof(double) * 3 * (size_t)nb, off_m2 = off_terms + sizeof(double) * 3 * (size_t)n, off_found = off_m2 + sizeof(double) * (size_t)n,
+               off_best = off_found + sizeof(int) * (size_t)n;
+  HIP_OR_FAIL(e, vm.score_buf.ensure(off_best + sizeof(int) * (size_t)n));
+  char* base = vm.score_buf.as<char>();
+  VmScoreOut* d_out = reinterpret_cast<VmScoreOut*>(base);
+  double* d_chunk = reinterpret_cast<double*>(base + off_chunk);
+  double* d_terms = reinterpret_cast<double*>(base + off_terms);
+  double* d_m2 = best_m2 ? reinterpret_cast<double*>(base + off_m2) : nullptr;
+  int* d_found = found ? reinterpret_cast<int*>(base + off_found) : nullptr;
+  int* d_best = best ? reinterpret_cast<int*>(base + off_best) : nullptr;
+  HIP_OR_FAIL(e, hipMemsetAsync(d_out, 0, sizeof(VmScoreOut), e->stream));
+  VmScore sp;
+  sp.T = pose_from_colmajor16(T16);
+  sp.res = vm.res; sp.max_m2 = max_m2; sp.score_scale = score_scale; sp.min_points = min_points;
+  const VmGrid* grid = vm.has_bitmap ? vm.grid.as<VmGrid>() : nullptr;
+  const unsigned long long* bitmap = vm.has_bitmap ? vm.bitmap.as<unsigned long long>() : nullptr;
+  {
+    ProfScope ps(e, "map_score");
+    auto launch = [&](auto noff) {
+      vm_score_kernel<decltype(noff)::value><<<(n + 255) / 256, 256, 0, e->stream>>>(d_xyz, stride, n, order, sp, vm.keys_cur(), vm.capacity - 1, vm.table.as<uint4>(), grid, bitmap, vm.counters_cur(),
+                                                                                    d_terms, d_found, d_best, d_m2, d_out);
+    };
+    if (neighbors == FVH_DIRECT1) launch(std::integral_constant<int, 1>{});
+    else if (neighbors == FVH_DIRECT7) launch(std::integral_constant<int, 7>{});
+    else launch(std::integral_constant<int, 27>{});
+    // chunk sums, then their sum: one chunk goes straight into the struct (how many levels run depends on n alone)
+    vm_score_sum_kernel<3><<<nb, 1024, 0, e->stream>>>(d_terms, n, VM_SCORE_CHUNK, nb == 1 ? &d_out->sum_best_m2 : d_chunk);
+    if (nb > 1) vm_score_sum_kernel<3><<<1, 1024, 0, e->stream>>>(d_chunk, nb, 0x7FFFFFFF, &d_out->sum_best_m2);
+  }
+  HIP_OR_FAIL(e, hipGetLastError());
+  HIP_OR_FAIL(e, hipMemcpyAsync(out, d_out, sizeof(*out), hipMemcpyDeviceToHost, e->stream));
+  if (found) HIP_OR_FAIL(e, hipMemcpyAsync(found, d_found, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, e->stream));
+  if (best) HIP_OR_FAIL(e, hipMemcpyAsync(best, d_best, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, e->stream));
+  if (best_m2) HIP_OR_FAIL(e, hipMemcpyAsync(best_m2, d_m2, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, e->stream));
+  HIP_OR_FAIL(e, hipStreamSynchronize(e->stream));
+  if (out->n_points < 0) { *overflowed = true; std::memset(out, 0, sizeof(*out)); }
+  return FVH_OK;
+}
+
 // ---- snapshots of the live map (fvh_vgicp_voxelmap_export / _import / _merge_from; kernels_voxelmap.hpp: "snapshots") ------------------
 // A snapshot is the header {resolution, mode, num_inserts = epoch, num_points, num_voxels} and per voxel {coords[3], sums[10], age}, rows
 // in ascending packed-key order. Rows ADD into a live map of the same grid: import (host rows) and merge_from (another handle's map, read

@@ -293,6 +293,22 @@ static void def_incremental_target(PyClass& c) {
         }
         return py::make_tuple(r.removed, r.rays_used);
       }, py::arg("pose"), py::arg("origin") = py::none(), py::arg("min_range") = 0.0, py::arg("max_range") = 100.0, py::arg("end_margin") = 0.0, py::arg("min_misses") = 1)
+      // how well the target voxel map (batch or incremental) explains the source at `pose` (fvh_*_score_source; read-only): -> dict of the
+      // counts and sums, overlap / nvtl / tp, and with per_point the arrays found, best (int32) and best_m2 (float64), one row per source point
+      .def("score_target", [](Reg& v, const Mat4& pose, int neighbors, int min_points, double max_m2, double score_scale, bool per_point) {
+        const fast_gicp::MapScore s = v.scoreTarget(numpy2mat4(pose), (fast_gicp::NeighborSearchMethod)neighbors, min_points, max_m2, score_scale, per_point);
+        py::dict d;
+        d["n_points"] = s.n_points; d["n_used"] = s.n_used; d["n_in_voxel"] = s.n_in_voxel; d["n_near"] = s.n_near; d["n_explained"] = s.n_explained;
+        d["sum_best_m2"] = s.sum_best_m2; d["sum_score_max"] = s.sum_score_max; d["sum_score_all"] = s.sum_score_all;
+        d["overlap"] = s.overlap(); d["nvtl"] = s.nvtl(); d["tp"] = s.tp();
+        if (per_point) {
+          d["found"] = py::array_t<int>((py::ssize_t)s.found.size(), s.found.data());
+          d["best"] = py::array_t<int>((py::ssize_t)s.best.size(), s.best.data());
+          d["best_m2"] = py::array_t<double>((py::ssize_t)s.best_m2.size(), s.best_m2.data());
+        }
+        return d;
+      }, py::arg("pose"), py::arg("neighbors") = 1 /* DIRECT7 */, py::arg("min_points") = 1, py::arg("max_m2") = std::numeric_limits<double>::infinity(), py::arg("score_scale") = 1.0,
+         py::arg("per_point") = false)
       // the map as the handle's target cloud too (one point per voxel with >= min_points points; a snapshot): get_fitness_score() and
       // align_best() then work in this mode. -> number of points
       .def("target_cloud_from_map", [](Reg& v, int min_points) { return v.targetCloudFromMap(min_points); }, py::arg("min_points") = 1)

@@ -550,6 +550,17 @@ protected:
 /// what clearTargetAlongRays() reports: voxels removed, rays that were walked (not skipped)
 struct RayClearing { int removed = 0, rays_used = 0; };
 
+/// what scoreTarget() reports (C ABI: fvh_map_score + the per-point rows): how well the target voxel map explains the source at a pose
+struct MapScore {
+  int n_points = 0, n_used = 0, n_in_voxel = 0, n_near = 0, n_explained = 0;
+  double sum_best_m2 = 0.0, sum_score_max = 0.0, sum_score_all = 0.0;
+  std::vector<int> found, best;   // with per_point: one row per source point, in input order (skipped points: -1, -1, NaN)
+  std::vector<double> best_m2;
+  double overlap() const { return n_used ? (double)n_in_voxel / n_used : std::numeric_limits<double>::quiet_NaN(); }   // share of points inside occupied voxels
+  double nvtl() const { return n_near ? sum_score_max / n_near : std::numeric_limits<double>::quiet_NaN(); }           // nearest voxel transformation likelihood
+  double tp() const { return n_used ? sum_score_all / n_used : std::numeric_limits<double>::quiet_NaN(); }             // transform probability
+};
+
 /// A snapshot of an incremental target map (FastVGICPCuda / NDTCuda exportTargetMap / importTargetMap; C ABI: fvh_vgicp_voxelmap_export /
 /// _import, fvh_ndt_voxelmap_export / _import): per voxel coords[3], the device's ten fp64 sums and an age, rows in ascending packed-key
 /// order (z-major, then y, then x).
@@ -617,7 +628,7 @@ inline constexpr DeviceCalls<fvh_ndt> kNdtCalls{
     {fvh_ndt_align, "align"}, {fvh_ndt_align_multi, "align_multi"}, {fvh_ndt_fitness_score, "fitness_score"},
     {fvh_ndt_set_lm_trace, "set_lm_trace"}, {fvh_ndt_get_lm_trace, "get_lm_trace"},
     {fvh_ndt_align_async, "align_async"}, {fvh_ndt_align_wait, "align_wait"}};
-/// The incremental target map and its snapshots (FastVGICPCuda, NDTCuda). Not part of the tables above: these are inline functions of a
+/// The incremental target map, its snapshots and the map score (FastVGICPCuda, NDTCuda; the score: FastVGICP too). Not part of the tables above: these are inline functions of a
 /// class template, so a program refers to a handle type's map calls only if it uses them
 template <typename Handle>
 struct MapCalls;
@@ -633,6 +644,8 @@ struct MapCalls<fvh_vgicp> {
   static int merge_from_posed(fvh_vgicp* h, fvh_vgicp* other, const double* T16, int* rows_skipped) { return fvh_vgicp_posed_merge_from(h, other, T16, rows_skipped); }
   static int transform(fvh_vgicp* h, const double* T16, int* rows_skipped) { return fvh_vgicp_transform_map(h, T16, rows_skipped); }
   static int target_from_map(fvh_vgicp* h, int min_points, int* num_points) { return fvh_vgicp_target_from_map(h, min_points, num_points); }
+  static int num_source_points(fvh_vgicp* h, int* n) { return fvh_vgicp_get_num_source_points(h, n); }
+  static int score_source(fvh_vgicp* h, const double* T16, int neighbors, int min_points, double max_m2, double score_scale, fvh_map_score* out, int* found, int* best, double* best_m2) { return fvh_vgicp_score_source(h, T16, neighbors, min_points, max_m2, score_scale, out, found, best, best_m2); }
 };
 template <>
 struct MapCalls<fvh_ndt> {
@@ -646,6 +659,8 @@ struct MapCalls<fvh_ndt> {
   static int merge_from_posed(fvh_ndt* h, fvh_ndt* other, const double* T16, int* rows_skipped) { return fvh_ndt_posed_merge_from(h, other, T16, rows_skipped); }
   static int transform(fvh_ndt* h, const double* T16, int* rows_skipped) { return fvh_ndt_transform_map(h, T16, rows_skipped); }
   static int target_from_map(fvh_ndt* h, int min_points, int* num_points) { return fvh_ndt_target_from_map(h, min_points, num_points); }
+  static int num_source_points(fvh_ndt* h, int* n) { return fvh_ndt_get_num_source_points(h, n); }
+  static int score_source(fvh_ndt* h, const double* T16, int neighbors, int min_points, double max_m2, double score_scale, fvh_map_score* out, int* found, int* best, double* best_m2) { return fvh_ndt_score_source(h, T16, neighbors, min_points, max_m2, score_scale, out, found, best, best_m2); }
 };
 }  // namespace detail
 
@@ -740,6 +755,29 @@ protected:
     call(Map::clear_rays_source(core_, T16, origin3, min_range, max_range, end_margin, min_misses, &out.removed, &out.rays_used), "clear_rays_source");
     return out;
   }
+  /// How well the target voxel map (batch or incremental) explains the current source at pose T (fvh_*_score_source through
+  /// detail::MapCalls, read-only on the handle; public on the classes that own a voxel map: FastVGICPCuda, FastVGICP, NDTCuda): around
+  /// every point the voxels of `neighbors` (DIRECT1 / DIRECT7 / DIRECT27) with >= min_points points are looked up and the squared
+  /// Mahalanobis distance to each voxel's Gaussian is formed; a point is explained when its best one is finite and <= max_m2; scores are
+  /// exp(-0.5 * score_scale * m2). per_point: also found / best / best_m2 per source point. The source is the HANDLE's -- one set by
+  /// setInputSource or one adopted from a device-side preparation, which leaves no host cloud behind: the rows are sized by the handle's count.
+  MapScore scoreTarget(const Matrix4f& T, NeighborSearchMethod neighbors = NeighborSearchMethod::DIRECT7, int min_points = 1,
+                       double max_m2 = std::numeric_limits<double>::infinity(), double score_scale = 1.0, bool per_point = false) {
+    double T16[16];
+    Isometry3d::from(T).to_colmajor16(T16);
+    MapScore out;
+    fvh_map_score s;
+    int rows = 0;
+    if (per_point) call(Map::num_source_points(core_, &rows), "get_num_source_points");
+    const size_t n = (size_t)rows;
+    out.found.resize(n); out.best.resize(n); out.best_m2.resize(n);
+    call(Map::score_source(core_, T16, (int)neighbors, min_points, max_m2, score_scale, &s, n ? out.found.data() : nullptr, n ? out.best.data() : nullptr, n ? out.best_m2.data() : nullptr), "score_source");
+    out.n_points = s.n_points; out.n_used = s.n_used; out.n_in_voxel = s.n_in_voxel; out.n_near = s.n_near; out.n_explained = s.n_explained;
+    out.sum_best_m2 = s.sum_best_m2; out.sum_score_max = s.sum_score_max; out.sum_score_all = s.sum_score_all;
+    return out;
+  }
+  /// ... at the final transformation of the last align()
+  MapScore scoreTarget() { return scoreTarget(this->final_transformation_); }
   bool hasIncrementalTarget() const { return incremental_target_; }
   /// The live map becomes the handle's target CLOUD as well: one point per voxel with >= min_points points (the voxel's mean; VGICP: + its
   /// covariance), rows in ascending key order -- the row order of exportTargetMap(). getFitnessScore() and alignBest() then work on the map.
@@ -1002,6 +1040,7 @@ public:
   using Base::insertSourceIntoTarget;
   using Base::pruneTarget;
   using Base::clearTargetAlongRays;
+  using Base::scoreTarget;
   using Base::hasIncrementalTarget;
   using Base::targetCloudFromMap;
 
@@ -1186,6 +1225,7 @@ class FastVGICP : public FastGICP<PointSource, PointTarget> {
 
 public:
   using PointCloudTargetConstPtr = typename Base::PointCloudTargetConstPtr;
+  using Base::scoreTarget;  // (this class owns a voxel map; FastGICP does not)
 
   explicit FastVGICP(int device = 0) : Base(device) {  // fast_vgicp_impl.hpp:19-25
     this->calls_ = &detail::kVgicpVoxelCalls;  // what it replaces in FastGICP: voxel correspondences, and the calls only they have
@@ -1264,6 +1304,7 @@ public:
   using Base::insertSourceIntoTarget;
   using Base::pruneTarget;
   using Base::clearTargetAlongRays;
+  using Base::scoreTarget;
   using Base::hasIncrementalTarget;
   using Base::targetCloudFromMap;
   using Base::exportTargetMap;

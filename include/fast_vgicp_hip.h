@@ -315,6 +315,63 @@ int fvh_vgicp_map_get_info(fvh_vgicp* h, int* incremental, int* num_voxels, int*
  * (communicator, peers, tile, map sharding) and FVH_COMPUTE_CUDA_COMPAT (FVH_ERR_UNSUPPORTED). n == 0: FVH_OK, nothing removed. */
 int fvh_vgicp_clear_rays_source(fvh_vgicp* h, const double* T16, const double* origin3, double min_range, double max_range, double end_margin, int min_misses, int* num_removed, int* rays_used);
 int fvh_vgicp_clear_rays_cloud(fvh_vgicp* h, const float* xyz, int n, int stride_floats, int on_device, const double* T16, const double* origin3, double min_range, double max_range, double end_margin, int min_misses, int* num_removed, int* rays_used);
+/* new: SCORING a posed scan against the target voxel map, per point, on the device. How well does the map explain the scan at pose T: the
+ * share of points that fall into occupied voxels (gtsam_points / GLIM: "overlap"), a likelihood (Autoware's NDT matcher: "transform
+ * probability", "nearest voxel transformation likelihood"), and per point whether the map explains it or it is novel. The map is the handle's
+ * CURRENT target voxel map, batch (create_target_voxelmap) or incremental (map_begin), of any accumulation mode and precision: the call reads
+ * the voxel records {num_points, mean, covariance} and nothing else. It is point-to-distribution: source covariances play no part.
+ *   _source   scores the handle's current source points (no covariances needed), walked in the source's Morton order when it has one.
+ *   _cloud    ... xyz: n points on the host or the device (on_device), stride_floats 3 or 4.
+ *   T16       4x4 double column-major, scan frame -> map frame (R, t).
+ *   neighbors FVH_DIRECT1, FVH_DIRECT7 or FVH_DIRECT27: the voxels looked up around a point, independent of the handle's own search method.
+ *   min_points  voxels with fewer points are not candidates (<= 1: every voxel).  max_m2: a point is EXPLAINED when its best squared
+ *   Mahalanobis distance is finite and <= max_m2 (+inf allowed: every finite distance explains).  score_scale: the scores are exp(-0.5 * score_scale * m2).
+ *   out       required.  found, best, best_m2: host arrays of n rows in INPUT order, each may be NULL; with all three NULL the call reads back
+ *             sizeof(fvh_map_score) bytes and nothing else.
+ * The contract (res = the map's resolution):
+ *   point     p' = (float)(R p + t), the bits an insert of the same point at the same pose bins (the device expression of the insert and of
+ *             clear_rays); c = floor((double)p' / res - 0.5) per axis. SKIPPED when a coordinate of p is non-finite or c is outside
+ *             |c| < 2^20 - 4096: found = -1, best = -1, best_m2 = NaN, not counted in n_used.
+ *   offsets   DIRECT1: (0,0,0). DIRECT7: (0,0,0), +x, -x, +y, -y, +z, -z. DIRECT27: dx outermost, then dy, then dz, each -1, 0, 1 (so
+ *             (0,0,0) is index 13). `best` is an index into that order.
+ *   candidate the voxel c + o when it lies inside the key range, exists in the map and its record's num_points >= min_points. A live
+ *             occupancy bitmap may answer for absent cells first; the result is the same with and without it.
+ *   distance  d = (double)p' - (double)mean per axis; the record's six covariance floats widened to fp64; then in fp64, every product and
+ *             sum rounded on its own (no contraction):
+ *               a00 = cyy*czz - cyz*cyz, a01 = cxz*cyz - cxy*czz, a02 = cxy*cyz - cxz*cyy,
+ *               a11 = cxx*czz - cxz*cxz, a12 = cxy*cxz - cxx*cyz, a22 = cxx*cyy - cxy*cxy,
+ *               det = (cxx*a00 + cxy*a01) + cxz*a02,
+ *               q = (((dx*dx)*a00 + (dy*dy)*a11) + (dz*dz)*a22) + 2.0*((((dx*dy)*a01) + ((dx*dz)*a02)) + ((dy*dz)*a12)),
+ *             m2 = q / det when det > 0 and det, q are finite (a negative quotient becomes 0), else m2 = +inf: a singular record counts as
+ *             found and explains nothing.
+ *   per point found = the number of candidates; best = the candidate with the smallest m2, the first in offset order on ties, -1 with
+ *             found = 0; best_m2 = that m2, +inf with no candidate. score(m2) = exp((-0.5 * score_scale) * m2) by the fp64 device exp, 0 for
+ *             m2 = +inf.
+ *   sums      per point three fp64 terms at its INPUT index: best_m2 if explained (best_m2 < +inf and best_m2 <= max_m2); score(best_m2) if found > 0; the sum over its candidates,
+ *             in offset order, of score(m2); 0 otherwise. Each array is summed in an order that depends on n alone (chunks of 16,384 entries;
+ *             inside a chunk thread t of 1,024 takes entries t, t + 1,024, ... in four interleaved partial sums, then a fixed tree; the chunk
+ *             sums the same way): two runs give the same bits, _source with or without a Morton order gives the same bits, _cloud of the same
+ *             points gives the same bits. The counts are integers. No floating-point atomics.
+ * Nothing of the handle is written: the map (an export before and after is byte-equal), stored correspondences, the linearisation pose, the
+ * clouds and their Morton order (the call does not sort); an align after the call gives the bits it gave before. The scratch is the call's
+ * own, so it is legal between prepare_source* and adopt_prepared_source, as target_from_map is. One exception: a batch map whose hint-sized
+ * table had dropped points is rebuilt at the safe size first, as align, compute_error and the voxel getters do. The call synchronises once.
+ * Refusals (the handle stays usable; host input is validated before anything is queued): no target voxel map, an align_async in flight,
+ * _source without a source cloud (FVH_ERR_BAD_STATE); a NULL or non-finite T16, NULL out, neighbors other than the three above
+ * (FVH_DIRECT_RADIUS too), max_m2 NaN or < 0, score_scale not finite or <= 0, n < 0, NULL xyz with n > 0, a stride other than 3 or 4
+ * (FVH_ERR_INVALID_ARGUMENT); multi-GPU handles -- communicator, peers, tile, map sharding -- (FVH_ERR_UNSUPPORTED). n == 0: FVH_OK, all zeros. */
+typedef struct fvh_map_score {
+  int n_points;        /* rows offered */
+  int n_used;          /* not skipped */
+  int n_in_voxel;      /* used points whose OWN voxel (offset 0,0,0) is a candidate */
+  int n_near;          /* used points with at least one candidate among the offsets */
+  int n_explained;     /* ... whose best squared Mahalanobis distance is finite and <= max_m2 */
+  double sum_best_m2;  /* over explained points */
+  double sum_score_max;/* over near points: exp(-0.5 * score_scale * best m2) */
+  double sum_score_all;/* over used points: sum over candidates of exp(-0.5 * score_scale * m2) */
+} fvh_map_score;
+int fvh_vgicp_score_source(fvh_vgicp* h, const double* T16, int neighbors, int min_points, double max_m2, double score_scale, fvh_map_score* out, int* found, int* best, double* best_m2);
+int fvh_vgicp_score_cloud(fvh_vgicp* h, const float* xyz, int n, int stride_floats, int on_device, const double* T16, int neighbors, int min_points, double max_m2, double score_scale, fvh_map_score* out, int* found, int* best, double* best_m2);
 /* Snapshots of the live incremental map: write it out, bring it back, add another map to it.
  * A snapshot is a header -- resolution, mode (0 additive, 2 multiplicative), num_inserts (the map's insert count), num_points, num_voxels --
  * and per voxel coords[3] (int32), sums[10] (fp64: {sum p | sum C^-1 p (3), sum C | sum C^-1 (6), count}, the device's own sums) and an age
@@ -590,6 +647,9 @@ int fvh_ndt_map_get_info(fvh_ndt* h, int* incremental, int* num_voxels, int* cap
 /* free-space carving, as fvh_vgicp_clear_rays_source / _cloud above, argument for argument and under the same contract */
 int fvh_ndt_clear_rays_source(fvh_ndt* h, const double* T16, const double* origin3, double min_range, double max_range, double end_margin, int min_misses, int* num_removed, int* rays_used);
 int fvh_ndt_clear_rays_cloud(fvh_ndt* h, const float* xyz, int n, int stride_floats, int on_device, const double* T16, const double* origin3, double min_range, double max_range, double end_margin, int min_misses, int* num_removed, int* rays_used);
+/* a posed scan scored against the target voxel map, as fvh_vgicp_score_source / _cloud above, argument for argument and under the same contract */
+int fvh_ndt_score_source(fvh_ndt* h, const double* T16, int neighbors, int min_points, double max_m2, double score_scale, fvh_map_score* out, int* found, int* best, double* best_m2);
+int fvh_ndt_score_cloud(fvh_ndt* h, const float* xyz, int n, int stride_floats, int on_device, const double* T16, int neighbors, int min_points, double max_m2, double score_scale, fvh_map_score* out, int* found, int* best, double* best_m2);
 int fvh_ndt_voxelmap_export(fvh_ndt* h, int* num_voxels, double* resolution, int* mode, int* num_inserts, long long* num_points, int* coords3, double* sums10, unsigned* ages);
 int fvh_ndt_voxelmap_import(fvh_ndt* h, int n, const int* coords3, const double* sums10, const unsigned* ages, double resolution, int mode, int num_inserts, long long num_points);
 int fvh_ndt_voxelmap_merge_from(fvh_ndt* h, fvh_ndt* other);
@@ -603,6 +663,7 @@ int fvh_ndt_transform_map(fvh_ndt* h, const double* T16, int* rows_skipped);
  * newer afterwards -- and fvh_ndt_align after it runs on the incremental map, bit for bit as before; stored correspondences are kept.
  * FVH_ERR_BAD_STATE without a live incremental map or with an align_async in flight. */
 int fvh_ndt_target_from_map(fvh_ndt* h, int min_points, int* num_points_out);
+int fvh_ndt_get_num_source_points(const fvh_ndt* h, int* n); /* points of the current source cloud (the rows fvh_ndt_score_source writes): 0 without one */
 int fvh_ndt_get_num_target_points(const fvh_ndt* h, int* n); /* rows of fvh_ndt_get_target_points: 0 without a target cloud */
 int fvh_ndt_get_target_points(fvh_ndt* h, float* xyz3);
 /* new (round 6): the output of the filter's last ApproximateVoxelGrid call becomes the cloud WITHOUT a copy -- the filter's emit kernel wrote it as
