@@ -90,7 +90,7 @@ def load():
                 continue
             fn.argtypes = argtypes
             fn.restype = C.c_int
-        for name, argtypes in DESKEW_ARGTYPES.items():
+        for name, argtypes in list(DESKEW_ARGTYPES.items()) + list(CLUSTER_ARGTYPES.items()):
             fn = getattr(L, name, None)
             if fn is None:  # (an older build of the ABI, as above)
                 continue
@@ -131,6 +131,17 @@ def _deskew_argtypes():
 
 
 DESKEW_ARGTYPES = _deskew_argtypes()
+
+
+def _cluster_argtypes():
+    """fvh_voxelgrid_cluster_euclidean[_strided|_device] and fvh_voxelgrid_get_cluster_labels, as the header declares them"""
+    h, p, i, d = C.c_void_p, C.c_void_p, C.c_int, C.c_double
+    tail = [d, i, i, p, p]  # tolerance, min_cluster_size, max_cluster_size, num_clusters, out_n
+    return {"fvh_voxelgrid_cluster_euclidean": [h, p, i] + tail, "fvh_voxelgrid_cluster_euclidean_strided": [h, p, i, i] + tail,
+            "fvh_voxelgrid_cluster_euclidean_device": [h, p, i, i] + tail, "fvh_voxelgrid_get_cluster_labels": [h, p, p]}
+
+
+CLUSTER_ARGTYPES = _cluster_argtypes()
 
 
 def declared_symbols():
@@ -929,7 +940,8 @@ class VoxelGrid:
     def __init__(self, device=0):
         self._lib = load()
         self._h = C.c_void_p()
-        self._n_in = 0  # input size of the last crop / outlier call (scores())
+        self._n_in = 0  # input size of the last crop / outlier / cluster call (scores(), cluster_labels())
+        self.num_clusters = 0  # kept components of the last cluster_euclidean call
         rc = self._lib.fvh_voxelgrid_create(int(device), C.byref(self._h))
         if rc != 0:
             raise FvhError("fvh_voxelgrid_create failed: %d" % rc)
@@ -1012,7 +1024,7 @@ class VoxelGrid:
         self._check(self._lib.fvh_voxelgrid_profile_reset(self._h), "profile_reset")
 
     def profile_get(self, cls="downsample"):
-        """(total ms, launches) of one profile class of the filter's engine: "downsample", "sort", "knn", "outlier_count", "outlier_score", "compact", "deskew" """
+        """(total ms, launches) of one profile class of the filter's engine: "downsample", "sort", "knn", "outlier_count", "outlier_score", "compact", "deskew", "cluster" """
         ms, n = C.c_double(0), C.c_int(0)
         if cls == "downsample":
             self._check(self._lib.fvh_voxelgrid_profile_get(self._h, C.byref(ms), C.byref(n)), "profile_get")
@@ -1111,6 +1123,35 @@ class VoxelGrid:
         self._check(self._lib.fvh_voxelgrid_deskew_device(self._h, C.c_void_p(d_xyz), int(n), int(stride), C.c_void_p(d_times), int(time_stride), _p(tau), _p(T), len(tau), t_ref,
                                                           C.byref(m)), "fvh_voxelgrid_deskew_device")
         return self.device_points()
+
+    # ---- Euclidean cluster extraction (fvh_voxelgrid_cluster_euclidean): connected components of "closer than tolerance", a size window,
+    # clusters numbered by their smallest input index. The kept points are the handle's output (get_points / device_points /
+    # kept_indices / scores work on it as after an outlier filter). ----
+    def cluster_euclidean(self, points, tolerance, min_size=1, max_size=0, device=False, stride=3):
+        """(labels int32[n]: cluster number per INPUT point or -1, sizes int32[num_clusters]). points: a host array of n x `stride`
+        floats, or with device=True a (device pointer, n) pair -- which may be this handle's own device_points()."""
+        nc, m = C.c_int(0), C.c_int(0)
+        if device:
+            d_ptr, n = points
+            n = int(n)
+            rc = self._lib.fvh_voxelgrid_cluster_euclidean_device(self._h, C.c_void_p(d_ptr), n, int(stride), float(tolerance), int(min_size), int(max_size), C.byref(nc), C.byref(m))
+        else:
+            a = _f32(np.asarray(points).reshape(-1, stride))
+            n = len(a)
+            if stride == 3:
+                rc = self._lib.fvh_voxelgrid_cluster_euclidean(self._h, _p(a), n, float(tolerance), int(min_size), int(max_size), C.byref(nc), C.byref(m))
+            else:
+                rc = self._lib.fvh_voxelgrid_cluster_euclidean_strided(self._h, _p(a), n, int(stride), float(tolerance), int(min_size), int(max_size), C.byref(nc), C.byref(m))
+        self._n_in = max(n, 0)
+        self.num_clusters = nc.value  # (0 after a refused call)
+        self._check(rc, "fvh_voxelgrid_cluster_euclidean")
+        return self.cluster_labels()
+
+    def cluster_labels(self):
+        """(labels, sizes) of the last cluster_euclidean call on this handle"""
+        labels, sizes = np.empty(self._n_in, np.int32), np.empty(self.num_clusters, np.int32)
+        self._check(self._lib.fvh_voxelgrid_get_cluster_labels(self._h, _p(labels), _p(sizes)), "fvh_voxelgrid_get_cluster_labels")
+        return labels, sizes
 
     def device_points(self):
         """(device pointer to the packed xyz of the last output, count)"""

@@ -26,6 +26,7 @@
 #include "kernels_cov.hpp"
 #include "kernels_downsample.hpp"
 #include "kernels_outlier.hpp"
+#include "kernels_cluster.hpp"
 #include "kernels_deskew.hpp"
 #include "kernels_peer.hpp"
 #include "kernels_sort.hpp"
@@ -452,6 +453,7 @@ inline void pose_to_rowmajor12f(const double* T16, float* T12) {  // what the se
 #include "host_gicp.inc.hpp"
 #include "host_downsample.inc.hpp"
 #include "host_outlier.inc.hpp"
+#include "host_cluster.inc.hpp"
 #include "host_deskew.inc.hpp"
 
 }  // namespace
@@ -655,12 +657,13 @@ struct fvh_voxelgrid {
   DownsampleDev d;
   OutlierDev o;  // side outputs of crop_range / remove_*_outliers (host_outlier.inc.hpp)
   DeskewDev k;   // segment records and times of fvh_voxelgrid_deskew (host_deskew.inc.hpp)
+  ClusterDev c;  // union-find, labels and cluster sizes of fvh_voxelgrid_cluster_euclidean (host_cluster.inc.hpp)
   bool in_flight() const { return false; }  // (a filter has no pipeline: CHECK_HANDLE never refuses on it)
   static constexpr const char* prefix = "fvh_voxelgrid";
   static constexpr bool gang_kernels = false;          // a filter never launches a persistent / cooperative kernel
   static constexpr bool side_stream_first = false;     // (it has no side stream of its own)
   int created() { return FVH_OK; }
-  void release_all() { d.release(); o.release(); k.release(); }
+  void release_all() { d.release(); o.release(); k.release(); c.release(); }
 };
 
 // CHECK_HANDLE_SOURCE_CHAIN: the calls that only touch the SOURCE cloud -- they may run beside a target-map build on the side
@@ -1975,6 +1978,15 @@ int fvh_voxelgrid_deskew(fvh_voxelgrid* h, const float* xyz, int n, const float*
 int fvh_voxelgrid_deskew_strided(fvh_voxelgrid* h, const float* xyz, int n, int stride, const float* times, int time_stride, const double* knot_times, const double* knot_poses, int K, double t_ref, int* out_n) { FVH_DESKEW_CALL(xyz, stride, false, times); }
 int fvh_voxelgrid_deskew_device(fvh_voxelgrid* h, const float* d_xyz, int n, int stride, const float* d_times, int time_stride, const double* knot_times, const double* knot_poses, int K, double t_ref, int* out_n) { FVH_DESKEW_CALL(d_xyz, stride, true, d_times); }
 #undef FVH_DESKEW_CALL
+
+// ---- Euclidean cluster extraction on the filter handle (host_cluster.inc.hpp, kernels_cluster.hpp) ----
+#define FVH_CLUSTER_CALL(xyz, stride, on_device) \
+  CHECK_HANDLE(h); FilterStream fs(&h->e); if (fs.rc) return fs.rc; return cluster_euclidean(&h->e, h->d, h->o, h->c, xyz, n, stride, on_device, tolerance, min_cluster_size, max_cluster_size, num_clusters, out_n)
+int fvh_voxelgrid_cluster_euclidean(fvh_voxelgrid* h, const float* xyz, int n, double tolerance, int min_cluster_size, int max_cluster_size, int* num_clusters, int* out_n) { FVH_CLUSTER_CALL(xyz, 3, false); }
+int fvh_voxelgrid_cluster_euclidean_strided(fvh_voxelgrid* h, const float* xyz, int n, int stride, double tolerance, int min_cluster_size, int max_cluster_size, int* num_clusters, int* out_n) { FVH_CLUSTER_CALL(xyz, stride, false); }
+int fvh_voxelgrid_cluster_euclidean_device(fvh_voxelgrid* h, const float* d_xyz, int n, int stride, double tolerance, int min_cluster_size, int max_cluster_size, int* num_clusters, int* out_n) { FVH_CLUSTER_CALL(d_xyz, stride, true); }
+#undef FVH_CLUSTER_CALL
+int fvh_voxelgrid_get_cluster_labels(fvh_voxelgrid* h, int* labels, int* sizes) { CHECK_HANDLE(h); return cluster_get_labels(&h->e, h->o, h->c, labels, sizes); }
 int fvh_voxelgrid_profile_get_class(fvh_voxelgrid* h, const char* kernel_class, double* total_ms, int* launches) { CHECK_HANDLE(h); return profile_get(&h->e, kernel_class, total_ms, launches); }
 
 }  // extern "C"

@@ -7,7 +7,8 @@
 
 struct OutlierDev {
   DevBuf flags, pos, score, kept, ctl;  // keep flag and scanned position per input point, its score, kept indices, OutlierCtl
-  bool valid = false;                   // the last call on the handle was one of the three filters below (and succeeded)
+  bool valid = false;                   // the last call on the handle was one of the three filters below or cluster_euclidean (and succeeded)
+  bool cluster = false;                 // ... and it was cluster_euclidean (host_cluster.inc.hpp): labels and cluster sizes exist too
   int n_in = 0;
   double threshold = 0.0;
   void release() { flags.release(); pos.release(); score.release(); kept.release(); ctl.release(); }
@@ -19,6 +20,7 @@ enum OutlierKind { OUTLIER_CROP = 0, OUTLIER_STATISTICAL = 1, OUTLIER_RADIUS = 2
 int outlier_filter(Engine* e, DownsampleDev& d, OutlierDev& o, int kind, const float* xyz, int n, int stride, bool on_device, double p0, double p1, int k, int* out_n) {
   if (e->stream_owner) e->stream_owner->quiet = false;  // work on a borrowed stream (see downsample())
   o.valid = false;
+  o.cluster = false;
   d.out_n = 0;
   d.out4_valid = false;
   if (!out_n) return e->fail(FVH_ERR_INVALID_ARGUMENT, "outlier filter: null out_n");
@@ -102,7 +104,7 @@ int outlier_filter(Engine* e, DownsampleDev& d, OutlierDev& o, int kind, const f
 }
 
 int outlier_get_kept(Engine* e, DownsampleDev& d, OutlierDev& o, int* idx) {
-  if (!o.valid) return e->fail(FVH_ERR_BAD_STATE, "get_kept_indices: the last call on this handle was not crop_range / remove_statistical_outliers / remove_radius_outliers");
+  if (!o.valid) return e->fail(FVH_ERR_BAD_STATE, "get_kept_indices: the last call on this handle was not crop_range / remove_statistical_outliers / remove_radius_outliers / cluster_euclidean");
   if (d.out_n == 0) return FVH_OK;
   if (!idx) return e->fail(FVH_ERR_INVALID_ARGUMENT, "get_kept_indices: null output");
   HIP_OR_FAIL(e, hipMemcpyAsync(idx, o.kept.p, sizeof(int) * (size_t)d.out_n, hipMemcpyDefault, e->stream));
@@ -111,7 +113,7 @@ int outlier_get_kept(Engine* e, DownsampleDev& d, OutlierDev& o, int* idx) {
 }
 
 int outlier_get_scores(Engine* e, OutlierDev& o, float* scores, double* threshold) {
-  if (!o.valid) return e->fail(FVH_ERR_BAD_STATE, "get_scores: the last call on this handle was not crop_range / remove_statistical_outliers / remove_radius_outliers");
+  if (!o.valid) return e->fail(FVH_ERR_BAD_STATE, "get_scores: the last call on this handle was not crop_range / remove_statistical_outliers / remove_radius_outliers / cluster_euclidean");
   if (threshold) *threshold = o.threshold;
   if (scores && o.n_in > 0) {
     HIP_OR_FAIL(e, hipMemcpyAsync(scores, o.score.p, sizeof(float) * (size_t)o.n_in, hipMemcpyDefault, e->stream));

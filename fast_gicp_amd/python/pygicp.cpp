@@ -174,6 +174,23 @@ static py::object remove_outliers_device(const Points& points, const std::string
   return filtered_result(vg, rc, n, return_indices, stat ? "fvh_voxelgrid_remove_statistical_outliers" : "fvh_voxelgrid_remove_radius_outliers");
 }
 
+// Euclidean cluster extraction on the device (fvh_voxelgrid_cluster_euclidean): (labels int32[n], cluster number per input point or -1;
+// sizes int32[num_clusters]); clusters are numbered by their smallest input index
+static py::tuple cluster_euclidean_device(const Points& points, double tolerance, int min_cluster_size, int max_cluster_size, int device) {
+  auto cloud = numpy2cloud(points);
+  const std::vector<float> xyz = detail::pack_xyz(*cloud);
+  fvh_voxelgrid* vg = nullptr;
+  detail::check(fvh_voxelgrid_create(device, &vg), "fvh_voxelgrid_create", "cannot create the HIP engine (no GPU? there is no CPU fallback)");
+  int n = 0, nc = 0;
+  int rc = fvh_voxelgrid_cluster_euclidean(vg, xyz.data(), (int)cloud->size(), tolerance, min_cluster_size, max_cluster_size, &nc, &n);
+  py::array_t<int> labels((py::ssize_t)cloud->size()), sizes((py::ssize_t)nc);
+  if (!rc) rc = fvh_voxelgrid_get_cluster_labels(vg, labels.mutable_data(), sizes.mutable_data());
+  const std::string err = rc ? fvh_voxelgrid_last_error(vg) : "";
+  fvh_voxelgrid_destroy(vg);
+  detail::check(rc, "fvh_voxelgrid_cluster_euclidean", err.c_str());
+  return py::make_tuple(labels, sizes);
+}
+
 // motion compensation of a sweep on the device (fvh_voxelgrid_deskew): every point into the sensor frame of t_ref along the trajectory
 // through the knot poses ((K, 4, 4), sensor-at-that-instant -> one fixed frame); (n, 3) out, input order
 static py::array_t<double> deskew_device(const Points& points, const py::array_t<double, py::array::c_style | py::array::forcecast>& times,
@@ -364,6 +381,8 @@ PYBIND11_MODULE(pygicp, m) {
   m.def("remove_outliers_device", &remove_outliers_device, "statistical (mean_k, stddev_mul) or radius (radius, min_neighbors) outlier removal on the GPU; kept points in input order",
         py::arg("points"), py::arg("method") = "STATISTICAL", py::arg("mean_k") = 20, py::arg("stddev_mul") = 1.0, py::arg("radius") = 0.8, py::arg("min_neighbors") = 2,
         py::arg("return_indices") = false, py::arg("device") = 0);
+  m.def("cluster_euclidean_device", &cluster_euclidean_device, "Euclidean cluster extraction on the GPU: (labels per input point or -1, cluster sizes); clusters numbered by their smallest input index",
+        py::arg("points"), py::arg("tolerance"), py::arg("min_cluster_size") = 1, py::arg("max_cluster_size") = 0, py::arg("device") = 0);
   m.def("deskew_device", &deskew_device, "motion-compensate a sweep on the GPU: points (n, 3) with one time each, moved along the trajectory through the knot poses into the sensor frame of t_ref",
         py::arg("points"), py::arg("times"), py::arg("knot_times"), py::arg("knot_poses"), py::arg("t_ref") = py::none(), py::arg("device") = 0);
   m.def("align_points", &align_points, "align two point sets", py::arg("target"), py::arg("source"), py::arg("method") = "VGICP_CUDA", py::arg("downsample_resolution") = -1.0,

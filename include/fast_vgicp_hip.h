@@ -739,7 +739,7 @@ int fvh_voxelgrid_device_points(fvh_voxelgrid* h, const float** d_xyz, int* n);
 int fvh_voxelgrid_profile_enable(fvh_voxelgrid* h, int on);
 int fvh_voxelgrid_profile_reset(fvh_voxelgrid* h);
 int fvh_voxelgrid_profile_get(fvh_voxelgrid* h, double* total_ms, int* launches);
-int fvh_voxelgrid_profile_get_class(fvh_voxelgrid* h, const char* kernel_class, double* total_ms, int* launches); /* any class of the filter's engine: "downsample", "sort", "knn", "outlier_count", "outlier_score", "compact", "deskew" */
+int fvh_voxelgrid_profile_get_class(fvh_voxelgrid* h, const char* kernel_class, double* total_ms, int* launches); /* any class of the filter's engine: "downsample", "sort", "knn", "outlier_count", "outlier_score", "compact", "deskew", "cluster" */
 
 /* ---- range crop, statistical and radius outlier removal (no counterpart in the reference's cores: the stages a LiDAR front end runs
  * around the voxel filter -- the origin / range filter of src/align.cpp:127-133, pcl::StatisticalOutlierRemoval,
@@ -780,6 +780,37 @@ int fvh_voxelgrid_remove_radius_outliers_strided(fvh_voxelgrid* h, const float* 
 int fvh_voxelgrid_remove_radius_outliers_device(fvh_voxelgrid* h, const float* d_xyz, int n, int stride_floats, double radius, int min_neighbors, int* out_n);
 int fvh_voxelgrid_get_kept_indices(fvh_voxelgrid* h, int* idx /* out_n ints, host */);
 int fvh_voxelgrid_get_scores(fvh_voxelgrid* h, float* scores /* n floats (the INPUT size), host, may be NULL */, double* threshold /* may be NULL */);
+
+/* ---- Euclidean cluster extraction (no counterpart in the reference's cores: pcl::EuclideanClusterExtraction, the stage that groups the
+ * points a map does not explain -- fvh_*_score_cloud's "novel" points, or a cropped scan -- into objects, on the filter handle) ----
+ * Forms as for the outlier filters: host xyz, host rows of stride_floats (3 or 4), device pointer.
+ * Distances and edges. d2(i, j) is the fp32 (dx*dx + dy*dy) + dz*dz without contraction of the radius filter and the k-NN; it is symmetric
+ * in i, j to the bit. r2 = (float)tolerance * (float)tolerance, at most 1e37. Edge i ~ j iff i != j (by index) and d2(i, j) <= r2: exact
+ * duplicates are connected.
+ * Components and size filter. The components are the connected components of that graph. A component of size s is KEPT iff
+ * min_cluster_size <= s and (max_cluster_size <= 0 or s <= max_cluster_size).
+ * Labels. Kept components are numbered 0 .. num_clusters - 1 in ascending order of their smallest input index; labels[i] is that number,
+ * or -1 when i is in no kept component; sizes[c] is the size of cluster c. This DIFFERS from PCL, which sorts its clusters by size at the
+ * end and returns index lists; as for the outlier filters, PCL's boundary behaviour (a kd-tree radius search in its own arithmetic) was not
+ * available to compare against and no parity with it is claimed beyond the published algorithm. Everything returned is an integer or a
+ * bit copy: the result does not depend on the order in which the device visits the edges, and two runs give the same output.
+ * Output state. The points of kept components IN INPUT ORDER, as bit copies, in the handle's ordinary output state as after an outlier
+ * filter: fvh_voxelgrid_get_points, _device_points and fvh_ndt_{set_source,set_target,prepare_source}_cloud_from_voxelgrid work on it,
+ * fvh_voxelgrid_get_kept_indices gives their input indices, fvh_voxelgrid_get_scores gives the (float) size of each INPUT point's component
+ * with threshold min_cluster_size. out_n is the kept point count. fvh_voxelgrid_get_cluster_labels copies labels (n ints, INPUT order) and
+ * sizes (num_clusters ints) to host or device memory (either may be NULL); it answers FVH_ERR_BAD_STATE when the last call on the handle
+ * was not a clustering call. The input may be the handle's own fvh_voxelgrid_device_points() (crop -> cluster chains on one handle): it is
+ * copied before the output is written.
+ * Refused with FVH_ERR_INVALID_ARGUMENT, out_n = num_clusters = 0, the handle stays usable: tolerance not finite or <= 0;
+ * min_cluster_size < 1; 0 < max_cluster_size < min_cluster_size; n < 0, or NULL xyz with n > 0; stride other than 3 or 4; NULL out_n or
+ * NULL num_clusters; a non-finite coordinate (detected on the device and reported at the end of the chain, as the outlier filters do:
+ * crop_range is the stage that drops such points). n == 0: FVH_OK with zeros.
+ * The call runs on the stream the handle currently works on and synchronises it once, with one readback of its control words.
+ * Profile classes: "sort", "cluster" (the union-find sweep), "compact" (everything after it). */
+int fvh_voxelgrid_cluster_euclidean(fvh_voxelgrid* h, const float* xyz, int n, double tolerance, int min_cluster_size, int max_cluster_size, int* num_clusters, int* out_n);
+int fvh_voxelgrid_cluster_euclidean_strided(fvh_voxelgrid* h, const float* xyz, int n, int stride_floats, double tolerance, int min_cluster_size, int max_cluster_size, int* num_clusters, int* out_n);
+int fvh_voxelgrid_cluster_euclidean_device(fvh_voxelgrid* h, const float* d_xyz, int n, int stride_floats, double tolerance, int min_cluster_size, int max_cluster_size, int* num_clusters, int* out_n);
+int fvh_voxelgrid_get_cluster_labels(fvh_voxelgrid* h, int* labels /* n ints, INPUT order, host or device; may be NULL */, int* sizes /* num_clusters ints; may be NULL */);
 
 /* ---- motion compensation ("deskew") of one sweep (no counterpart in the reference: the KITTI odometry scans it runs on are untwisted by
  * the dataset; a live driver delivers points taken over ~0.1 s of vehicle motion) ----
