@@ -90,7 +90,7 @@ def load():
                 continue
             fn.argtypes = argtypes
             fn.restype = C.c_int
-        for name, argtypes in list(DESKEW_ARGTYPES.items()) + list(CLUSTER_ARGTYPES.items()):
+        for name, argtypes in list(DESKEW_ARGTYPES.items()) + list(CLUSTER_ARGTYPES.items()) + list(PLANE_ARGTYPES.items()):
             fn = getattr(L, name, None)
             if fn is None:  # (an older build of the ABI, as above)
                 continue
@@ -142,6 +142,18 @@ def _cluster_argtypes():
 
 
 CLUSTER_ARGTYPES = _cluster_argtypes()
+
+
+def _plane_argtypes():
+    """fvh_voxelgrid_segment_plane[_strided|_device] and fvh_voxelgrid_get_plane_model, as the header declares them"""
+    h, p, i, d = C.c_void_p, C.c_void_p, C.c_int, C.c_double
+    tail = [d, i, C.c_ulonglong, p, d, i, p, p, p]  # distance_threshold, max_iterations, seed, axis, eps_angle, flags, coefficients, num_inliers, out_n
+    return {"fvh_voxelgrid_segment_plane": [h, p, i] + tail, "fvh_voxelgrid_segment_plane_strided": [h, p, i, i] + tail,
+            "fvh_voxelgrid_segment_plane_device": [h, p, i, i] + tail, "fvh_voxelgrid_get_plane_model": [h, p, p, p, p]}
+
+
+PLANE_ARGTYPES = _plane_argtypes()
+PLANE_KEEP_OUTLIERS, PLANE_REFINE = 1, 2  # enum fvh_plane_flags
 
 
 def declared_symbols():
@@ -942,6 +954,7 @@ class VoxelGrid:
         self._h = C.c_void_p()
         self._n_in = 0  # input size of the last crop / outlier / cluster call (scores(), cluster_labels())
         self.num_clusters = 0  # kept components of the last cluster_euclidean call
+        self._plane_h = 0  # max_iterations of the last segment_plane call (plane_model())
         rc = self._lib.fvh_voxelgrid_create(int(device), C.byref(self._h))
         if rc != 0:
             raise FvhError("fvh_voxelgrid_create failed: %d" % rc)
@@ -1024,7 +1037,7 @@ class VoxelGrid:
         self._check(self._lib.fvh_voxelgrid_profile_reset(self._h), "profile_reset")
 
     def profile_get(self, cls="downsample"):
-        """(total ms, launches) of one profile class of the filter's engine: "downsample", "sort", "knn", "outlier_count", "outlier_score", "compact", "deskew", "cluster" """
+        """(total ms, launches) of one profile class of the filter's engine: "downsample", "sort", "knn", "outlier_count", "outlier_score", "compact", "deskew", "cluster", "plane" """
         ms, n = C.c_double(0), C.c_int(0)
         if cls == "downsample":
             self._check(self._lib.fvh_voxelgrid_profile_get(self._h, C.byref(ms), C.byref(n)), "profile_get")
@@ -1152,6 +1165,39 @@ class VoxelGrid:
         labels, sizes = np.empty(self._n_in, np.int32), np.empty(self.num_clusters, np.int32)
         self._check(self._lib.fvh_voxelgrid_get_cluster_labels(self._h, _p(labels), _p(sizes)), "fvh_voxelgrid_get_cluster_labels")
         return labels, sizes
+
+    # ---- plane segmentation by RANSAC (fvh_voxelgrid_segment_plane): H hypotheses from a counter-based generator, all scored in one sweep,
+    # optional axis constraint and least-squares refit. The inliers (or with keep_outliers everything else) are the handle's output
+    # (get_points / device_points / kept_indices / scores work on it as after an outlier filter). ----
+    def segment_plane(self, points, distance_threshold, max_iterations=256, seed=0, axis=None, eps_angle=0.0, keep_outliers=False, refine=False, device=False, stride=3, flags=None):
+        """(coefficients float64[4]: unit normal and d >= 0, num_inliers). points: a host array of n x `stride` floats, or with device=True
+        a (device pointer, n) pair -- which may be this handle's own device_points(). flags: the raw flag word instead of the two booleans."""
+        co, ni, m = np.zeros(4, np.float64), C.c_int(0), C.c_int(0)
+        ax = None if axis is None else np.ascontiguousarray(axis, np.float64).reshape(3)
+        tail = (float(distance_threshold), int(max_iterations), int(seed) & 0xFFFFFFFFFFFFFFFF, None if ax is None else _p(ax), float(eps_angle),
+                int(flags) if flags is not None else (PLANE_KEEP_OUTLIERS if keep_outliers else 0) | (PLANE_REFINE if refine else 0), _p(co), C.byref(ni), C.byref(m))
+        if device:
+            d_ptr, n = points
+            n = int(n)
+            rc = self._lib.fvh_voxelgrid_segment_plane_device(self._h, C.c_void_p(d_ptr), n, int(stride), *tail)
+        else:
+            a = _f32(np.asarray(points).reshape(-1, stride))
+            n = len(a)
+            if stride == 3:
+                rc = self._lib.fvh_voxelgrid_segment_plane(self._h, _p(a), n, *tail)
+            else:
+                rc = self._lib.fvh_voxelgrid_segment_plane_strided(self._h, _p(a), n, int(stride), *tail)
+        self._n_in = max(n, 0)
+        self._plane_h = max(int(max_iterations), 0)
+        self._check(rc, "fvh_voxelgrid_segment_plane")
+        return co, ni.value
+
+    def plane_model(self):
+        """dict(coefficients float64[4], sample int32[3], winner, valid, count_winner, num_inliers, counts int32[H]) of the last segment_plane
+        call made through this object (the C getter writes max_iterations counts: the array is sized by that call's max_iterations)"""
+        co, sample, info, counts = np.zeros(4, np.float64), np.zeros(3, np.int32), np.zeros(4, np.int32), np.empty(self._plane_h, np.int32)
+        self._check(self._lib.fvh_voxelgrid_get_plane_model(self._h, _p(co), _p(sample), _p(info), _p(counts)), "fvh_voxelgrid_get_plane_model")
+        return dict(coefficients=co, sample=sample, winner=int(info[0]), valid=int(info[1]), count_winner=int(info[2]), num_inliers=int(info[3]), counts=counts)
 
     def device_points(self):
         """(device pointer to the packed xyz of the last output, count)"""

@@ -191,6 +191,31 @@ static py::tuple cluster_euclidean_device(const Points& points, double tolerance
   return py::make_tuple(labels, sizes);
 }
 
+// RANSAC plane segmentation on the device (fvh_voxelgrid_segment_plane): (coefficients float64[4]: unit normal and d >= 0; int32 indices
+// of the kept points in input order: the plane's inliers, or with keep_outliers everything else)
+static py::tuple segment_plane_device(const Points& points, double distance_threshold, int max_iterations, unsigned long long seed, const py::object& axis, double eps_angle,
+                                      bool keep_outliers, bool refine, int device) {
+  auto cloud = numpy2cloud(points);
+  const std::vector<float> xyz = detail::pack_xyz(*cloud);
+  std::vector<double> ax;
+  if (!axis.is_none()) {
+    ax = axis.cast<std::vector<double>>();
+    if (ax.size() != 3) throw std::invalid_argument("segment_plane_device: axis must have 3 components");
+  }
+  fvh_voxelgrid* vg = nullptr;
+  detail::check(fvh_voxelgrid_create(device, &vg), "fvh_voxelgrid_create", "cannot create the HIP engine (no GPU? there is no CPU fallback)");
+  int n = 0, inliers = 0;
+  py::array_t<double> co((py::ssize_t)4);
+  int rc = fvh_voxelgrid_segment_plane(vg, xyz.data(), (int)cloud->size(), distance_threshold, max_iterations, seed, ax.empty() ? nullptr : ax.data(), eps_angle,
+                                       (keep_outliers ? FVH_PLANE_KEEP_OUTLIERS : 0) | (refine ? FVH_PLANE_REFINE : 0), co.mutable_data(), &inliers, &n);
+  py::array_t<int> ids((py::ssize_t)n);
+  if (!rc) rc = fvh_voxelgrid_get_kept_indices(vg, ids.mutable_data());
+  const std::string err = rc ? fvh_voxelgrid_last_error(vg) : "";
+  fvh_voxelgrid_destroy(vg);
+  detail::check(rc, "fvh_voxelgrid_segment_plane", err.c_str());
+  return py::make_tuple(co, ids);
+}
+
 // motion compensation of a sweep on the device (fvh_voxelgrid_deskew): every point into the sensor frame of t_ref along the trajectory
 // through the knot poses ((K, 4, 4), sensor-at-that-instant -> one fixed frame); (n, 3) out, input order
 static py::array_t<double> deskew_device(const Points& points, const py::array_t<double, py::array::c_style | py::array::forcecast>& times,
@@ -383,6 +408,9 @@ PYBIND11_MODULE(pygicp, m) {
         py::arg("return_indices") = false, py::arg("device") = 0);
   m.def("cluster_euclidean_device", &cluster_euclidean_device, "Euclidean cluster extraction on the GPU: (labels per input point or -1, cluster sizes); clusters numbered by their smallest input index",
         py::arg("points"), py::arg("tolerance"), py::arg("min_cluster_size") = 1, py::arg("max_cluster_size") = 0, py::arg("device") = 0);
+  m.def("segment_plane_device", &segment_plane_device, "RANSAC plane segmentation on the GPU: (coefficients (a, b, c, d), indices of the kept points: the inliers, or with keep_outliers everything else)",
+        py::arg("points"), py::arg("distance_threshold"), py::arg("max_iterations") = 256, py::arg("seed") = 0ull, py::arg("axis") = py::none(), py::arg("eps_angle") = 0.0,
+        py::arg("keep_outliers") = false, py::arg("refine") = false, py::arg("device") = 0);
   m.def("deskew_device", &deskew_device, "motion-compensate a sweep on the GPU: points (n, 3) with one time each, moved along the trajectory through the knot poses into the sensor frame of t_ref",
         py::arg("points"), py::arg("times"), py::arg("knot_times"), py::arg("knot_poses"), py::arg("t_ref") = py::none(), py::arg("device") = 0);
   m.def("align_points", &align_points, "align two point sets", py::arg("target"), py::arg("source"), py::arg("method") = "VGICP_CUDA", py::arg("downsample_resolution") = -1.0,

@@ -739,7 +739,7 @@ int fvh_voxelgrid_device_points(fvh_voxelgrid* h, const float** d_xyz, int* n);
 int fvh_voxelgrid_profile_enable(fvh_voxelgrid* h, int on);
 int fvh_voxelgrid_profile_reset(fvh_voxelgrid* h);
 int fvh_voxelgrid_profile_get(fvh_voxelgrid* h, double* total_ms, int* launches);
-int fvh_voxelgrid_profile_get_class(fvh_voxelgrid* h, const char* kernel_class, double* total_ms, int* launches); /* any class of the filter's engine: "downsample", "sort", "knn", "outlier_count", "outlier_score", "compact", "deskew", "cluster" */
+int fvh_voxelgrid_profile_get_class(fvh_voxelgrid* h, const char* kernel_class, double* total_ms, int* launches); /* any class of the filter's engine: "downsample", "sort", "knn", "outlier_count", "outlier_score", "compact", "deskew", "cluster", "plane" */
 
 /* ---- range crop, statistical and radius outlier removal (no counterpart in the reference's cores: the stages a LiDAR front end runs
  * around the voxel filter -- the origin / range filter of src/align.cpp:127-133, pcl::StatisticalOutlierRemoval,
@@ -811,6 +811,51 @@ int fvh_voxelgrid_cluster_euclidean(fvh_voxelgrid* h, const float* xyz, int n, d
 int fvh_voxelgrid_cluster_euclidean_strided(fvh_voxelgrid* h, const float* xyz, int n, int stride_floats, double tolerance, int min_cluster_size, int max_cluster_size, int* num_clusters, int* out_n);
 int fvh_voxelgrid_cluster_euclidean_device(fvh_voxelgrid* h, const float* d_xyz, int n, int stride_floats, double tolerance, int min_cluster_size, int max_cluster_size, int* num_clusters, int* out_n);
 int fvh_voxelgrid_get_cluster_labels(fvh_voxelgrid* h, int* labels /* n ints, INPUT order, host or device; may be NULL */, int* sizes /* num_clusters ints; may be NULL */);
+
+/* ---- plane segmentation by RANSAC (no counterpart in the reference's cores: pcl::SACSegmentation with SACMODEL_PLANE /
+ * SACMODEL_PERPENDICULAR_PLANE and SAC_RANSAC, the ground removal that sits between the filters and the clustering) ----
+ * Forms as for the outlier filters: host xyz, host rows of stride_floats (3 or 4), device pointer.
+ * Hypotheses. All arithmetic is uint32 with wrap-around. mix32(x): x ^= x>>16; x *= 0x7feb352d; x ^= x>>15; x *= 0x846ca68b; x ^= x>>16.
+ * s0 = mix32(lo32(seed) ^ mix32(hi32(seed) ^ 0x9e3779b9)). Hypothesis h (0 <= h < H = max_iterations, 1 <= H <= 16384) samples the INPUT
+ * indices i_j = ((uint64)mix32(s0 + 0x9e3779b9 * (3h + j + 1)) * n) >> 32 for j = 0, 1, 2. No resampling and no early exit: the outcome is
+ * a function of (cloud, parameters, seed) only. This DIFFERS from PCL, which draws from a stateful generator, redraws degenerate samples
+ * and stops adaptively; as for the outlier and cluster calls, no parity with PCL's boundary behaviour is claimed.
+ * A hypothesis's plane. Everything in fp64 without contraction, associations as written, coordinates widened to double first:
+ * e1 = p[i1] - p[i0], e2 = p[i2] - p[i0], (a, b, c) = e1 x e2 with each component as x*y - z*w, nn = (a*a + b*b) + c*c. The hypothesis is
+ * INVALID if two of its indices are equal or nn == 0; with axis non-NULL also unless dot*dot >= (c2*nn)*aa, dot = (a*ax + b*ay) + c*az,
+ * aa = (ax*ax + ay*ay) + az*az, c2 = cos(eps_angle)^2 (the host's cos): the normal is within eps_angle of +-axis. No finite float32 input
+ * overflows these expressions (the largest intermediate is below 1e235).
+ * Score. count_h = #{ i : s_i*s_i <= t2*nn }, u = p[i] - p[i0], s_i = (a*ux + b*uy) + c*uz, t2 = distance_threshold^2: no division and no
+ * square root. The winner is the valid hypothesis with the largest count, ties to the smallest h. With no valid hypothesis (n < 3, a
+ * collinear or all-duplicate cloud, an axis nothing satisfies) the call returns FVH_OK with num_inliers = 0, coefficients 0, winner -1 and
+ * every point an outlier: a streaming loop does not die on one bad frame.
+ * Refit (FVH_PLANE_REFINE; skipped when the winner has fewer than 3 inliers). Count, first and second moments of p - q over the winner's
+ * inliers, q = p[i0], in fp64 and in a FIXED order (two runs give the same bits); mean mu and covariance C = S2/m - mu mu^T; v = the unit
+ * eigenvector of C's smallest eigenvalue (cyclic Jacobi, on the device); the plane is (v, d = -v.(q + mu)). The axis test is not repeated.
+ * Returned coefficients (a, b, c, d): unit normal, sign such that d >= 0 (the normal faces the sensor origin; d == 0: the first non-zero
+ * component is positive). Without a refit they are the winner's plane normalised on the host (one square root, three divisions,
+ * d = -((a*qx + b*qy) + c*qz) on the normalised normal); the labelling IS the winner's count test and num_inliers == count_winner. With a
+ * refit the labelling uses the RETURNED doubles: i is an inlier iff s*s <= t2*((a*a + b*b) + c*c), s = ((a*x + b*y) + c*z) + d, and
+ * num_inliers counts that labelling.
+ * Output state. The kept points are the inliers (FVH_PLANE_KEEP_OUTLIERS: everything else), IN INPUT ORDER, as bit copies, in the handle's
+ * ordinary output state as after an outlier filter: fvh_voxelgrid_get_points, _device_points, fvh_ndt_*_from_voxelgrid and
+ * fvh_voxelgrid_get_kept_indices work on it; out_n is their count. fvh_voxelgrid_get_scores gives each INPUT point's distance to the
+ * WINNER's plane, (float)(|s_i| / sqrt(nn)) (+inf when there is no model), with threshold distance_threshold. The input may be the handle's
+ * own fvh_voxelgrid_device_points(): it is copied before the output is written. fvh_voxelgrid_get_cluster_labels answers
+ * FVH_ERR_BAD_STATE afterwards. fvh_voxelgrid_get_plane_model returns the coefficients, the winner's three indices, info = {winner,
+ * number of valid hypotheses, count_winner, num_inliers} and all H counts (-1 for an invalid hypothesis; host or device memory); each
+ * output may be NULL; it answers FVH_ERR_BAD_STATE when the last call on the handle was not a successful plane segmentation.
+ * Refused with FVH_ERR_INVALID_ARGUMENT, zero outputs, the handle stays usable: distance_threshold not finite or <= 0; max_iterations
+ * outside [1, 16384]; with an axis, eps_angle not in [0, pi/2] or an axis that is not finite or is zero; unknown flag bits; n < 0, or NULL
+ * xyz with n > 0; stride other than 3 or 4; NULL coefficients, num_inliers or out_n; a non-finite coordinate (detected on the device and
+ * reported at the end of the chain, as the cluster call does). n == 0: FVH_OK with zeros (winner -1, every count -1).
+ * The call runs on the stream the handle currently works on and synchronises it once, with one readback of its control words.
+ * Profile classes: "plane" (hypotheses, sweep, winner, refit), "compact" (everything after it). */
+enum fvh_plane_flags { FVH_PLANE_KEEP_OUTLIERS = 1, FVH_PLANE_REFINE = 2 };
+int fvh_voxelgrid_segment_plane(fvh_voxelgrid* h, const float* xyz, int n, double distance_threshold, int max_iterations, unsigned long long seed, const double* axis /* 3 doubles, host; NULL: no constraint */, double eps_angle, int flags, double* coefficients /* 4 */, int* num_inliers, int* out_n);
+int fvh_voxelgrid_segment_plane_strided(fvh_voxelgrid* h, const float* xyz, int n, int stride_floats, double distance_threshold, int max_iterations, unsigned long long seed, const double* axis, double eps_angle, int flags, double* coefficients, int* num_inliers, int* out_n);
+int fvh_voxelgrid_segment_plane_device(fvh_voxelgrid* h, const float* d_xyz, int n, int stride_floats, double distance_threshold, int max_iterations, unsigned long long seed, const double* axis, double eps_angle, int flags, double* coefficients, int* num_inliers, int* out_n);
+int fvh_voxelgrid_get_plane_model(fvh_voxelgrid* h, double* coefficients /* 4 */, int* sample /* 3 */, int* info /* 4 */, int* counts /* max_iterations ints, host or device */);
 
 /* ---- motion compensation ("deskew") of one sweep (no counterpart in the reference: the KITTI odometry scans it runs on are untwisted by
  * the dataset; a live driver delivers points taken over ~0.1 s of vehicle motion) ----
