@@ -5,7 +5,8 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libfast_vgicp_hip.so")
-SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("fvh_capi.hip", "host_runtime.inc.hpp", "host_stages.inc.hpp", "host_incmap.inc.hpp", "host_gicp.inc.hpp", "host_downsample.inc.hpp", "host_outlier.inc.hpp", "host_deskew.inc.hpp", "host_cluster.inc.hpp", "kernels_cluster.hpp", "host_plane.inc.hpp", "kernels_plane.hpp", "kernels_compat.hpp", "kernels_cost.hpp", "kernels_cov.hpp", "kernels_voxelmap.hpp", "kernels_mapscore.hpp", "kernels_sort.hpp", "sort_granule.hpp", "kernels_downsample.hpp", "kernels_outlier.hpp", "kernels_deskew.hpp", "kernels_peer.hpp", "dev_math.hpp", "voxel_key.hpp")]
+_CSRC = os.path.join(_HERE, "csrc")
+SOURCES = [os.path.join(_CSRC, "fvh_capi.hip")] + sorted(os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f != "fvh_capi.hip")  # the one translation unit, then everything it includes
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "fast_vgicp_hip.h")
 # -disable-machine-licm: the persistent LM kernel is one big loop over LM transitions; machine LICM hoists ~25 constant
 # materialisations and thread-index-derived addresses of its epilogue into the kernel prologue, where they stay live across

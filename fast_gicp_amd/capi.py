@@ -1047,24 +1047,27 @@ class VoxelGrid:
 
     # ---- range crop / outlier removal (fvh_voxelgrid_crop_range, _remove_statistical_outliers, _remove_radius_outliers): the kept points in
     # input order, bit copies of the input; kept_indices() / scores() describe the last of these calls ----
-    def _outlier_host(self, name, xyz, stride, *params):
-        a = _f32(np.asarray(xyz).reshape(-1, stride))
-        n = C.c_int(0)
-        self._n_in = len(a)
-        if stride == 3:
-            rc = getattr(self._lib, "fvh_voxelgrid_" + name)(self._h, _p(a), len(a), *params, C.byref(n))
+    def _stage(self, name, points, stride, *tail):
+        """One stage call (crop / outlier / deskew / cluster / plane) in the form its points ask for: a host array of n x `stride` floats
+        (fvh_voxelgrid_<name>, or _strided when stride != 3) or a (device pointer, n) pair (_device). `tail`: the stage's own arguments."""
+        if isinstance(points, tuple):
+            sym, n = "fvh_voxelgrid_" + name + "_device", int(points[1])
+            head = (C.c_void_p(points[0]), n, int(stride))
         else:
-            rc = getattr(self._lib, "fvh_voxelgrid_" + name + "_strided")(self._h, _p(a), len(a), int(stride), *params, C.byref(n))
-        self._check(rc, "fvh_voxelgrid_" + name)
+            a = _f32(np.asarray(points).reshape(-1, stride))
+            n = len(a)
+            sym, head = ("fvh_voxelgrid_" + name, (_p(a), n)) if stride == 3 else ("fvh_voxelgrid_" + name + "_strided", (_p(a), n, int(stride)))
+        self._n_in = max(n, 0)  # what scores() and cluster_labels() size their arrays by
+        self._check(getattr(self._lib, sym)(self._h, *head, *tail), sym)
+
+    def _outlier_host(self, name, xyz, stride, *params):
+        n = C.c_int(0)
+        self._stage(name, xyz, stride, *params, C.byref(n))
         return self.get_points(n.value)
 
     def _outlier_device(self, name, d_ptr, n, stride, *params):
-        m = C.c_int(0)
-        self._n_in = int(n)
-        self._check(getattr(self._lib, "fvh_voxelgrid_" + name + "_device")(self._h, C.c_void_p(d_ptr), int(n), int(stride), *params, C.byref(m)), "fvh_voxelgrid_" + name + "_device")
-        ptr = C.c_void_p()
-        self._check(self._lib.fvh_voxelgrid_device_points(self._h, C.byref(ptr), C.byref(m)), "fvh_voxelgrid_device_points")
-        return ptr.value or 0, m.value
+        self._stage(name, (d_ptr, n), stride, *params, C.byref(C.c_int(0)))
+        return self.device_points()
 
     def crop_range(self, xyz, min_sq_norm=1e-3, max_sq_norm=float("inf"), stride=3):
         """Keep the finite points with min_sq_norm <= |p|^2 (fp32) <= max_sq_norm; (m, 3) float32. The defaults are the reference's origin filter."""
@@ -1121,20 +1124,14 @@ class VoxelGrid:
             if len(t) < (len(a) - 1) * int(time_stride) + 1 and len(a):
                 raise ValueError("deskew: %d times for %d points at time_stride %d" % (len(t), len(a), time_stride))
             tp = _p(t)
-        if stride == 3:
-            rc = self._lib.fvh_voxelgrid_deskew(self._h, _p(a), len(a), tp, int(time_stride), _p(tau), _p(T), len(tau), t_ref, C.byref(n))
-        else:
-            rc = self._lib.fvh_voxelgrid_deskew_strided(self._h, _p(a), len(a), int(stride), tp, int(time_stride), _p(tau), _p(T), len(tau), t_ref, C.byref(n))
-        self._check(rc, "fvh_voxelgrid_deskew")
+        self._stage("deskew", a, stride, tp, int(time_stride), _p(tau), _p(T), len(tau), t_ref, C.byref(n))
         return self.get_points(n.value)
 
     def deskew_device(self, d_xyz, n, d_times, knot_times, knot_poses, t_ref=None, stride=3, time_stride=1):
         """Device pointers in (the knots stay host arrays); (device pointer to packed xyz, count) as filter_device returns them.
         d_xyz may be this handle's own device_points()."""
         tau, T, t_ref = self._knots(knot_times, knot_poses, t_ref)
-        m = C.c_int(0)
-        self._check(self._lib.fvh_voxelgrid_deskew_device(self._h, C.c_void_p(d_xyz), int(n), int(stride), C.c_void_p(d_times), int(time_stride), _p(tau), _p(T), len(tau), t_ref,
-                                                          C.byref(m)), "fvh_voxelgrid_deskew_device")
+        self._stage("deskew", (d_xyz, n), stride, C.c_void_p(d_times), int(time_stride), _p(tau), _p(T), len(tau), t_ref, C.byref(C.c_int(0)))
         return self.device_points()
 
     # ---- Euclidean cluster extraction (fvh_voxelgrid_cluster_euclidean): connected components of "closer than tolerance", a size window,
@@ -1144,20 +1141,10 @@ class VoxelGrid:
         """(labels int32[n]: cluster number per INPUT point or -1, sizes int32[num_clusters]). points: a host array of n x `stride`
         floats, or with device=True a (device pointer, n) pair -- which may be this handle's own device_points()."""
         nc, m = C.c_int(0), C.c_int(0)
-        if device:
-            d_ptr, n = points
-            n = int(n)
-            rc = self._lib.fvh_voxelgrid_cluster_euclidean_device(self._h, C.c_void_p(d_ptr), n, int(stride), float(tolerance), int(min_size), int(max_size), C.byref(nc), C.byref(m))
-        else:
-            a = _f32(np.asarray(points).reshape(-1, stride))
-            n = len(a)
-            if stride == 3:
-                rc = self._lib.fvh_voxelgrid_cluster_euclidean(self._h, _p(a), n, float(tolerance), int(min_size), int(max_size), C.byref(nc), C.byref(m))
-            else:
-                rc = self._lib.fvh_voxelgrid_cluster_euclidean_strided(self._h, _p(a), n, int(stride), float(tolerance), int(min_size), int(max_size), C.byref(nc), C.byref(m))
-        self._n_in = max(n, 0)
-        self.num_clusters = nc.value  # (0 after a refused call)
-        self._check(rc, "fvh_voxelgrid_cluster_euclidean")
+        try:
+            self._stage("cluster_euclidean", tuple(points) if device else points, stride, float(tolerance), int(min_size), int(max_size), C.byref(nc), C.byref(m))
+        finally:
+            self.num_clusters = nc.value  # (0 after a refused call)
         return self.cluster_labels()
 
     def cluster_labels(self):
@@ -1176,20 +1163,8 @@ class VoxelGrid:
         ax = None if axis is None else np.ascontiguousarray(axis, np.float64).reshape(3)
         tail = (float(distance_threshold), int(max_iterations), int(seed) & 0xFFFFFFFFFFFFFFFF, None if ax is None else _p(ax), float(eps_angle),
                 int(flags) if flags is not None else (PLANE_KEEP_OUTLIERS if keep_outliers else 0) | (PLANE_REFINE if refine else 0), _p(co), C.byref(ni), C.byref(m))
-        if device:
-            d_ptr, n = points
-            n = int(n)
-            rc = self._lib.fvh_voxelgrid_segment_plane_device(self._h, C.c_void_p(d_ptr), n, int(stride), *tail)
-        else:
-            a = _f32(np.asarray(points).reshape(-1, stride))
-            n = len(a)
-            if stride == 3:
-                rc = self._lib.fvh_voxelgrid_segment_plane(self._h, _p(a), n, *tail)
-            else:
-                rc = self._lib.fvh_voxelgrid_segment_plane_strided(self._h, _p(a), n, int(stride), *tail)
-        self._n_in = max(n, 0)
         self._plane_h = max(int(max_iterations), 0)
-        self._check(rc, "fvh_voxelgrid_segment_plane")
+        self._stage("segment_plane", tuple(points) if device else points, stride, *tail)
         return co, ni.value
 
     def plane_model(self):

@@ -453,6 +453,7 @@ inline void pose_to_rowmajor12f(const double* T16, float* T12) {  // what the se
 #include "host_incmap.inc.hpp"
 #include "host_gicp.inc.hpp"
 #include "host_downsample.inc.hpp"
+#include "host_filter_stage.inc.hpp"
 #include "host_outlier.inc.hpp"
 #include "host_cluster.inc.hpp"
 #include "host_plane.inc.hpp"
@@ -657,10 +658,10 @@ struct fvh_ndt {
 struct fvh_voxelgrid {
   Engine e;
   DownsampleDev d;
-  OutlierDev o;  // side outputs of crop_range / remove_*_outliers (host_outlier.inc.hpp)
+  OutlierDev o;  // which call the handle saw last, and the side outputs of the mask stages (host_filter_stage.inc.hpp)
   DeskewDev k;   // segment records and times of fvh_voxelgrid_deskew (host_deskew.inc.hpp)
   ClusterDev c;  // union-find, labels and cluster sizes of fvh_voxelgrid_cluster_euclidean (host_cluster.inc.hpp)
-  PlaneDev pl;   // hypotheses, counts and model of fvh_voxelgrid_segment_plane (host_plane.inc.hpp); any other filter call clears pl.valid
+  PlaneDev pl;   // hypotheses, counts and model of fvh_voxelgrid_segment_plane (host_plane.inc.hpp)
   bool in_flight() const { return false; }  // (a filter has no pipeline: CHECK_HANDLE never refuses on it)
   static constexpr const char* prefix = "fvh_voxelgrid";
   static constexpr bool gang_kernels = false;          // a filter never launches a persistent / cooperative kernel
@@ -1909,9 +1910,11 @@ struct FilterStream {
   }
   ~FilterStream() { e->stream = saved; }
 };
-int fvh_voxelgrid_filter(fvh_voxelgrid* h, int method, const float* xyz, int n, float leaf, int* out_n) { CHECK_HANDLE(h); h->o.valid = false; h->pl.valid = false; FilterStream fs(&h->e); if (fs.rc) return fs.rc; return downsample(&h->e, h->d, method, xyz, n, 3, false, leaf, out_n); }
-int fvh_voxelgrid_filter_strided(fvh_voxelgrid* h, int method, const float* xyz, int n, int stride, float leaf, int* out_n) { CHECK_HANDLE(h); h->o.valid = false; h->pl.valid = false; FilterStream fs(&h->e); if (fs.rc) return fs.rc; return downsample(&h->e, h->d, method, xyz, n, stride, false, leaf, out_n); }
-int fvh_voxelgrid_filter_device(fvh_voxelgrid* h, int method, const float* d_xyz, int n, int stride, float leaf, int* out_n) { CHECK_HANDLE(h); h->o.valid = false; h->pl.valid = false; FilterStream fs(&h->e); if (fs.rc) return fs.rc; return downsample(&h->e, h->d, method, d_xyz, n, stride, true, leaf, out_n); }
+// Every stage entry point of the filter handle (host_filter_stage.inc.hpp): the guard, that stream for the length of the call, the host function's result.
+#define FVH_STAGE(call) CHECK_HANDLE(h); FilterStream fs(&h->e); if (fs.rc) return fs.rc; return call
+int fvh_voxelgrid_filter(fvh_voxelgrid* h, int method, const float* xyz, int n, float leaf, int* out_n) { FVH_STAGE(voxel_stage(&h->e, h->d, h->o, method, xyz, n, 3, false, leaf, out_n)); }
+int fvh_voxelgrid_filter_strided(fvh_voxelgrid* h, int method, const float* xyz, int n, int stride, float leaf, int* out_n) { FVH_STAGE(voxel_stage(&h->e, h->d, h->o, method, xyz, n, stride, false, leaf, out_n)); }
+int fvh_voxelgrid_filter_device(fvh_voxelgrid* h, int method, const float* d_xyz, int n, int stride, float leaf, int* out_n) { FVH_STAGE(voxel_stage(&h->e, h->d, h->o, method, d_xyz, n, stride, true, leaf, out_n)); }
 // Extension for a device-resident pipeline (no PCL counterpart): the filter runs on the registration handle's stream, so what it
 // writes is ordered before whatever that handle queues next, and the _async call returns as soon as the COUNT is known (it comes
 // from the scan kernel, one kernel before the centroids exist): set_*_cloud_device + align are queued behind the emit kernel
@@ -1931,14 +1934,8 @@ int fvh_voxelgrid_share_stream_with_ndt(fvh_voxelgrid* h, fvh_ndt* other) { CHEC
 int fvh_voxelgrid_share_stream_with_vgicp(fvh_voxelgrid* h, fvh_vgicp* other) { CHECK_HANDLE(h); return share_stream(&h->e, other ? &other->e : nullptr, false); }
 int fvh_voxelgrid_share_prepare_stream_with_ndt(fvh_voxelgrid* h, fvh_ndt* other) { CHECK_HANDLE(h); return share_stream(&h->e, other ? &other->e : nullptr, true); }
 int fvh_voxelgrid_share_prepare_stream_with_vgicp(fvh_voxelgrid* h, fvh_vgicp* other) { CHECK_HANDLE(h); return share_stream(&h->e, other ? &other->e : nullptr, true); }
-int fvh_voxelgrid_filter_device_async(fvh_voxelgrid* h, int method, const float* d_xyz, int n, int stride, float leaf, int* out_n) {
-  CHECK_HANDLE(h);
-  h->o.valid = false;
-  h->pl.valid = false;
-  const bool shared = h->e.stream != h->e.owned_stream;
-  FilterStream fs(&h->e); if (fs.rc) return fs.rc;
-  return downsample(&h->e, h->d, method, d_xyz, n, stride, true, leaf, out_n, /*early=*/shared);
-}
+// (early only on a shared stream: FilterStream moves a filter from one stream of the other handle to another, never onto its own)
+int fvh_voxelgrid_filter_device_async(fvh_voxelgrid* h, int method, const float* d_xyz, int n, int stride, float leaf, int* out_n) { FVH_STAGE(voxel_stage(&h->e, h->d, h->o, method, d_xyz, n, stride, true, leaf, out_n, /*early=*/h->e.stream != h->e.owned_stream)); }
 int fvh_voxelgrid_get_points(fvh_voxelgrid* h, float* out_xyz) {
   CHECK_HANDLE(h);
   if (h->d.out_n == 0) return FVH_OK;
@@ -1960,44 +1957,33 @@ int fvh_voxelgrid_profile_reset(fvh_voxelgrid* h) { CHECK_HANDLE(h); return shar
 int fvh_voxelgrid_profile_get(fvh_voxelgrid* h, double* ms, int* n) { CHECK_HANDLE(h); return profile_get(&h->e, "downsample", ms, n); }
 
 // ---- range crop / outlier removal on the filter handle (host_outlier.inc.hpp, kernels_outlier.hpp) ----
-#define FVH_OUTLIER_CALL(kind, xyz, stride, on_device, p0, p1, k) \
-  CHECK_HANDLE(h); h->pl.valid = false; FilterStream fs(&h->e); if (fs.rc) return fs.rc; return outlier_filter(&h->e, h->d, h->o, kind, xyz, n, stride, on_device, p0, p1, k, out_n)
-int fvh_voxelgrid_crop_range(fvh_voxelgrid* h, const float* xyz, int n, double min_sq_norm, double max_sq_norm, int* out_n) { FVH_OUTLIER_CALL(OUTLIER_CROP, xyz, 3, false, min_sq_norm, max_sq_norm, 0); }
-int fvh_voxelgrid_crop_range_strided(fvh_voxelgrid* h, const float* xyz, int n, int stride, double min_sq_norm, double max_sq_norm, int* out_n) { FVH_OUTLIER_CALL(OUTLIER_CROP, xyz, stride, false, min_sq_norm, max_sq_norm, 0); }
-int fvh_voxelgrid_crop_range_device(fvh_voxelgrid* h, const float* d_xyz, int n, int stride, double min_sq_norm, double max_sq_norm, int* out_n) { FVH_OUTLIER_CALL(OUTLIER_CROP, d_xyz, stride, true, min_sq_norm, max_sq_norm, 0); }
-int fvh_voxelgrid_remove_statistical_outliers(fvh_voxelgrid* h, const float* xyz, int n, int mean_k, double stddev_mul, int* out_n) { FVH_OUTLIER_CALL(OUTLIER_STATISTICAL, xyz, 3, false, stddev_mul, 0.0, mean_k); }
-int fvh_voxelgrid_remove_statistical_outliers_strided(fvh_voxelgrid* h, const float* xyz, int n, int stride, int mean_k, double stddev_mul, int* out_n) { FVH_OUTLIER_CALL(OUTLIER_STATISTICAL, xyz, stride, false, stddev_mul, 0.0, mean_k); }
-int fvh_voxelgrid_remove_statistical_outliers_device(fvh_voxelgrid* h, const float* d_xyz, int n, int stride, int mean_k, double stddev_mul, int* out_n) { FVH_OUTLIER_CALL(OUTLIER_STATISTICAL, d_xyz, stride, true, stddev_mul, 0.0, mean_k); }
-int fvh_voxelgrid_remove_radius_outliers(fvh_voxelgrid* h, const float* xyz, int n, double radius, int min_neighbors, int* out_n) { FVH_OUTLIER_CALL(OUTLIER_RADIUS, xyz, 3, false, radius, 0.0, min_neighbors); }
-int fvh_voxelgrid_remove_radius_outliers_strided(fvh_voxelgrid* h, const float* xyz, int n, int stride, double radius, int min_neighbors, int* out_n) { FVH_OUTLIER_CALL(OUTLIER_RADIUS, xyz, stride, false, radius, 0.0, min_neighbors); }
-int fvh_voxelgrid_remove_radius_outliers_device(fvh_voxelgrid* h, const float* d_xyz, int n, int stride, double radius, int min_neighbors, int* out_n) { FVH_OUTLIER_CALL(OUTLIER_RADIUS, d_xyz, stride, true, radius, 0.0, min_neighbors); }
-#undef FVH_OUTLIER_CALL
+int fvh_voxelgrid_crop_range(fvh_voxelgrid* h, const float* xyz, int n, double min_sq_norm, double max_sq_norm, int* out_n) { FVH_STAGE(outlier_filter(&h->e, h->d, h->o, OUTLIER_CROP, xyz, n, 3, false, min_sq_norm, max_sq_norm, 0, out_n)); }
+int fvh_voxelgrid_crop_range_strided(fvh_voxelgrid* h, const float* xyz, int n, int stride, double min_sq_norm, double max_sq_norm, int* out_n) { FVH_STAGE(outlier_filter(&h->e, h->d, h->o, OUTLIER_CROP, xyz, n, stride, false, min_sq_norm, max_sq_norm, 0, out_n)); }
+int fvh_voxelgrid_crop_range_device(fvh_voxelgrid* h, const float* d_xyz, int n, int stride, double min_sq_norm, double max_sq_norm, int* out_n) { FVH_STAGE(outlier_filter(&h->e, h->d, h->o, OUTLIER_CROP, d_xyz, n, stride, true, min_sq_norm, max_sq_norm, 0, out_n)); }
+int fvh_voxelgrid_remove_statistical_outliers(fvh_voxelgrid* h, const float* xyz, int n, int mean_k, double stddev_mul, int* out_n) { FVH_STAGE(outlier_filter(&h->e, h->d, h->o, OUTLIER_STATISTICAL, xyz, n, 3, false, stddev_mul, 0.0, mean_k, out_n)); }
+int fvh_voxelgrid_remove_statistical_outliers_strided(fvh_voxelgrid* h, const float* xyz, int n, int stride, int mean_k, double stddev_mul, int* out_n) { FVH_STAGE(outlier_filter(&h->e, h->d, h->o, OUTLIER_STATISTICAL, xyz, n, stride, false, stddev_mul, 0.0, mean_k, out_n)); }
+int fvh_voxelgrid_remove_statistical_outliers_device(fvh_voxelgrid* h, const float* d_xyz, int n, int stride, int mean_k, double stddev_mul, int* out_n) { FVH_STAGE(outlier_filter(&h->e, h->d, h->o, OUTLIER_STATISTICAL, d_xyz, n, stride, true, stddev_mul, 0.0, mean_k, out_n)); }
+int fvh_voxelgrid_remove_radius_outliers(fvh_voxelgrid* h, const float* xyz, int n, double radius, int min_neighbors, int* out_n) { FVH_STAGE(outlier_filter(&h->e, h->d, h->o, OUTLIER_RADIUS, xyz, n, 3, false, radius, 0.0, min_neighbors, out_n)); }
+int fvh_voxelgrid_remove_radius_outliers_strided(fvh_voxelgrid* h, const float* xyz, int n, int stride, double radius, int min_neighbors, int* out_n) { FVH_STAGE(outlier_filter(&h->e, h->d, h->o, OUTLIER_RADIUS, xyz, n, stride, false, radius, 0.0, min_neighbors, out_n)); }
+int fvh_voxelgrid_remove_radius_outliers_device(fvh_voxelgrid* h, const float* d_xyz, int n, int stride, double radius, int min_neighbors, int* out_n) { FVH_STAGE(outlier_filter(&h->e, h->d, h->o, OUTLIER_RADIUS, d_xyz, n, stride, true, radius, 0.0, min_neighbors, out_n)); }
 int fvh_voxelgrid_get_kept_indices(fvh_voxelgrid* h, int* idx) { CHECK_HANDLE(h); return outlier_get_kept(&h->e, h->d, h->o, idx); }
 int fvh_voxelgrid_get_scores(fvh_voxelgrid* h, float* scores, double* threshold) { CHECK_HANDLE(h); return outlier_get_scores(&h->e, h->o, scores, threshold); }
 
 // ---- motion compensation of a sweep on the filter handle (host_deskew.inc.hpp, kernels_deskew.hpp) ----
-#define FVH_DESKEW_CALL(xyz, stride, on_device, times) \
-  CHECK_HANDLE(h); h->pl.valid = false; FilterStream fs(&h->e); if (fs.rc) return fs.rc; return deskew(&h->e, h->d, h->o, h->k, xyz, n, stride, on_device, times, time_stride, knot_times, knot_poses, K, t_ref, out_n)
-int fvh_voxelgrid_deskew(fvh_voxelgrid* h, const float* xyz, int n, const float* times, int time_stride, const double* knot_times, const double* knot_poses, int K, double t_ref, int* out_n) { FVH_DESKEW_CALL(xyz, 3, false, times); }
-int fvh_voxelgrid_deskew_strided(fvh_voxelgrid* h, const float* xyz, int n, int stride, const float* times, int time_stride, const double* knot_times, const double* knot_poses, int K, double t_ref, int* out_n) { FVH_DESKEW_CALL(xyz, stride, false, times); }
-int fvh_voxelgrid_deskew_device(fvh_voxelgrid* h, const float* d_xyz, int n, int stride, const float* d_times, int time_stride, const double* knot_times, const double* knot_poses, int K, double t_ref, int* out_n) { FVH_DESKEW_CALL(d_xyz, stride, true, d_times); }
-#undef FVH_DESKEW_CALL
+int fvh_voxelgrid_deskew(fvh_voxelgrid* h, const float* xyz, int n, const float* times, int time_stride, const double* knot_times, const double* knot_poses, int K, double t_ref, int* out_n) { FVH_STAGE(deskew(&h->e, h->d, h->o, h->k, xyz, n, 3, false, times, time_stride, knot_times, knot_poses, K, t_ref, out_n)); }
+int fvh_voxelgrid_deskew_strided(fvh_voxelgrid* h, const float* xyz, int n, int stride, const float* times, int time_stride, const double* knot_times, const double* knot_poses, int K, double t_ref, int* out_n) { FVH_STAGE(deskew(&h->e, h->d, h->o, h->k, xyz, n, stride, false, times, time_stride, knot_times, knot_poses, K, t_ref, out_n)); }
+int fvh_voxelgrid_deskew_device(fvh_voxelgrid* h, const float* d_xyz, int n, int stride, const float* d_times, int time_stride, const double* knot_times, const double* knot_poses, int K, double t_ref, int* out_n) { FVH_STAGE(deskew(&h->e, h->d, h->o, h->k, d_xyz, n, stride, true, d_times, time_stride, knot_times, knot_poses, K, t_ref, out_n)); }
 
 // ---- Euclidean cluster extraction on the filter handle (host_cluster.inc.hpp, kernels_cluster.hpp) ----
-#define FVH_CLUSTER_CALL(xyz, stride, on_device) \
-  CHECK_HANDLE(h); h->pl.valid = false; FilterStream fs(&h->e); if (fs.rc) return fs.rc; return cluster_euclidean(&h->e, h->d, h->o, h->c, xyz, n, stride, on_device, tolerance, min_cluster_size, max_cluster_size, num_clusters, out_n)
-int fvh_voxelgrid_cluster_euclidean(fvh_voxelgrid* h, const float* xyz, int n, double tolerance, int min_cluster_size, int max_cluster_size, int* num_clusters, int* out_n) { FVH_CLUSTER_CALL(xyz, 3, false); }
-int fvh_voxelgrid_cluster_euclidean_strided(fvh_voxelgrid* h, const float* xyz, int n, int stride, double tolerance, int min_cluster_size, int max_cluster_size, int* num_clusters, int* out_n) { FVH_CLUSTER_CALL(xyz, stride, false); }
-int fvh_voxelgrid_cluster_euclidean_device(fvh_voxelgrid* h, const float* d_xyz, int n, int stride, double tolerance, int min_cluster_size, int max_cluster_size, int* num_clusters, int* out_n) { FVH_CLUSTER_CALL(d_xyz, stride, true); }
-#undef FVH_CLUSTER_CALL
+int fvh_voxelgrid_cluster_euclidean(fvh_voxelgrid* h, const float* xyz, int n, double tolerance, int min_cluster_size, int max_cluster_size, int* num_clusters, int* out_n) { FVH_STAGE(cluster_euclidean(&h->e, h->d, h->o, h->c, xyz, n, 3, false, tolerance, min_cluster_size, max_cluster_size, num_clusters, out_n)); }
+int fvh_voxelgrid_cluster_euclidean_strided(fvh_voxelgrid* h, const float* xyz, int n, int stride, double tolerance, int min_cluster_size, int max_cluster_size, int* num_clusters, int* out_n) { FVH_STAGE(cluster_euclidean(&h->e, h->d, h->o, h->c, xyz, n, stride, false, tolerance, min_cluster_size, max_cluster_size, num_clusters, out_n)); }
+int fvh_voxelgrid_cluster_euclidean_device(fvh_voxelgrid* h, const float* d_xyz, int n, int stride, double tolerance, int min_cluster_size, int max_cluster_size, int* num_clusters, int* out_n) { FVH_STAGE(cluster_euclidean(&h->e, h->d, h->o, h->c, d_xyz, n, stride, true, tolerance, min_cluster_size, max_cluster_size, num_clusters, out_n)); }
 int fvh_voxelgrid_get_cluster_labels(fvh_voxelgrid* h, int* labels, int* sizes) { CHECK_HANDLE(h); return cluster_get_labels(&h->e, h->o, h->c, labels, sizes); }
 // ---- RANSAC plane segmentation on the filter handle (host_plane.inc.hpp, kernels_plane.hpp) ----
-#define FVH_PLANE_CALL(xyz, stride, on_device) \
-  CHECK_HANDLE(h); FilterStream fs(&h->e); if (fs.rc) return fs.rc; return segment_plane(&h->e, h->d, h->o, h->pl, xyz, n, stride, on_device, distance_threshold, max_iterations, seed, axis, eps_angle, flags, coefficients, num_inliers, out_n)
-int fvh_voxelgrid_segment_plane(fvh_voxelgrid* h, const float* xyz, int n, double distance_threshold, int max_iterations, unsigned long long seed, const double* axis, double eps_angle, int flags, double* coefficients, int* num_inliers, int* out_n) { FVH_PLANE_CALL(xyz, 3, false); }
-int fvh_voxelgrid_segment_plane_strided(fvh_voxelgrid* h, const float* xyz, int n, int stride, double distance_threshold, int max_iterations, unsigned long long seed, const double* axis, double eps_angle, int flags, double* coefficients, int* num_inliers, int* out_n) { FVH_PLANE_CALL(xyz, stride, false); }
-int fvh_voxelgrid_segment_plane_device(fvh_voxelgrid* h, const float* d_xyz, int n, int stride, double distance_threshold, int max_iterations, unsigned long long seed, const double* axis, double eps_angle, int flags, double* coefficients, int* num_inliers, int* out_n) { FVH_PLANE_CALL(d_xyz, stride, true); }
-#undef FVH_PLANE_CALL
+int fvh_voxelgrid_segment_plane(fvh_voxelgrid* h, const float* xyz, int n, double distance_threshold, int max_iterations, unsigned long long seed, const double* axis, double eps_angle, int flags, double* coefficients, int* num_inliers, int* out_n) { FVH_STAGE(segment_plane(&h->e, h->d, h->o, h->pl, xyz, n, 3, false, distance_threshold, max_iterations, seed, axis, eps_angle, flags, coefficients, num_inliers, out_n)); }
+int fvh_voxelgrid_segment_plane_strided(fvh_voxelgrid* h, const float* xyz, int n, int stride, double distance_threshold, int max_iterations, unsigned long long seed, const double* axis, double eps_angle, int flags, double* coefficients, int* num_inliers, int* out_n) { FVH_STAGE(segment_plane(&h->e, h->d, h->o, h->pl, xyz, n, stride, false, distance_threshold, max_iterations, seed, axis, eps_angle, flags, coefficients, num_inliers, out_n)); }
+int fvh_voxelgrid_segment_plane_device(fvh_voxelgrid* h, const float* d_xyz, int n, int stride, double distance_threshold, int max_iterations, unsigned long long seed, const double* axis, double eps_angle, int flags, double* coefficients, int* num_inliers, int* out_n) { FVH_STAGE(segment_plane(&h->e, h->d, h->o, h->pl, d_xyz, n, stride, true, distance_threshold, max_iterations, seed, axis, eps_angle, flags, coefficients, num_inliers, out_n)); }
+#undef FVH_STAGE
 int fvh_voxelgrid_get_plane_model(fvh_voxelgrid* h, double* coefficients, int* sample, int* info, int* counts) { CHECK_HANDLE(h); return plane_get_model(&h->e, h->o, h->pl, coefficients, sample, info, counts); }
 int fvh_voxelgrid_profile_get_class(fvh_voxelgrid* h, const char* kernel_class, double* total_ms, int* launches) { CHECK_HANDLE(h); return profile_get(&h->e, kernel_class, total_ms, launches); }
 

@@ -4,7 +4,7 @@
 // The host does everything that happens once per call, in fp64: the rigidity test of the knot poses, the SE(3) logarithm of every
 // segment, T(t_ref), and A_j = T(t_ref)^-1 * T[j]. The segment records travel through a pinned buffer of the handle (64 records:
 // more than the engine's own pinned block holds) into a small device buffer, by one hipMemcpyAsync in front of the kernel.
-// The call writes the handle's output state like a crop does (DownsampleDev::out / out4 / out_n), the input is widened first.
+// A stage of host_filter_stage.inc.hpp that keeps every point: begin, the cloud checks, the upload and the publication are that layer's.
 
 struct DeskewDev {
   DevBuf segs, times;       // nseg DeskewSeg records; the times of a HOST call, packed
@@ -119,14 +119,11 @@ inline int deskew_segment(const double* tau, int K, double x) {
 
 int deskew(Engine* e, DownsampleDev& d, OutlierDev& o, DeskewDev& k, const float* xyz, int n, int stride, bool on_device, const float* times, int time_stride,
            const double* knot_times, const double* knot_poses, int K, double t_ref, int* out_n) {
-  if (e->stream_owner) e->stream_owner->quiet = false;  // work on a borrowed stream (see downsample())
-  o.valid = false;
-  d.out_n = 0;
-  d.out4_valid = false;
+  stage_begin(e, d, o);
   if (!out_n) return e->fail(FVH_ERR_INVALID_ARGUMENT, "deskew: null out_n");
   *out_n = 0;
-  if (n < 0 || (n > 0 && (!xyz || !times))) return e->fail(FVH_ERR_INVALID_ARGUMENT, "deskew: null points or times");
-  if (stride != 3 && stride != 4) return e->fail(FVH_ERR_INVALID_ARGUMENT, "deskew: stride must be 3 or 4 floats");
+  int rc = stage_check_cloud(e, "deskew", xyz && times, n, stride, "points or times");
+  if (rc) return rc;
   if (time_stride < 1) return e->fail(FVH_ERR_INVALID_ARGUMENT, "deskew: time_stride must be >= 1");
   if (K < 2 || K > DESKEW_MAX_KNOTS) return e->fail(FVH_ERR_INVALID_ARGUMENT, "deskew: the number of knots must be in [2, 64]");
   if (!knot_times || !knot_poses) return e->fail(FVH_ERR_INVALID_ARGUMENT, "deskew: null knots");
@@ -147,7 +144,7 @@ int deskew(Engine* e, DownsampleDev& d, OutlierDev& o, DeskewDev& k, const float
     const double th = deskew_se3_log(deskew_mul(deskew_inv(T[j]), T[j + 1]), w[j], v[j]);
     if (!(th <= 3.14159265358979323846 - 1e-6)) return e->fail(FVH_ERR_INVALID_ARGUMENT, "deskew: segment " + std::to_string(j) + " turns by more than pi - 1e-6: its logarithm is not unique");
   }
-  if (n == 0) return FVH_OK;
+  if (n == 0) return stage_publish(e, d, o, LAST_DESKEW, 0, out_n);
   if (!k.host_segs) HIP_OR_FAIL(e, hipHostMalloc(&k.host_segs, sizeof(DeskewSeg) * (DESKEW_MAX_KNOTS - 1), hipHostMallocDefault));
   {
     const int jr = deskew_segment(knot_times, K, t_ref);
@@ -166,8 +163,7 @@ int deskew(Engine* e, DownsampleDev& d, OutlierDev& o, DeskewDev& k, const float
       hs[j].inv_dt = 1.0 / (knot_times[j + 1] - knot_times[j]);
     }
   }
-  int rc = upload_cloud(e, d.cloud, xyz, n, stride, on_device, false);  // before anything below writes d.out / d.out4: xyz may alias them
-  if (rc) return rc;
+  if ((rc = stage_upload(e, d, xyz, n, stride, on_device))) return rc;
   const float* d_times = times;
   int d_time_stride = time_stride;
   if (!on_device) {
@@ -180,18 +176,11 @@ int deskew(Engine* e, DownsampleDev& d, OutlierDev& o, DeskewDev& k, const float
   }
   HIP_OR_FAIL(e, k.segs.ensure(sizeof(DeskewSeg) * (DESKEW_MAX_KNOTS - 1)));
   HIP_OR_FAIL(e, hipMemcpyAsync(k.segs.p, k.host_segs, sizeof(DeskewSeg) * (size_t)nseg, hipMemcpyHostToDevice, e->stream));
-  HIP_OR_FAIL(e, d.out.ensure(sizeof(float) * 3 * (size_t)n));   // (never a reallocation when xyz is this buffer: its n points fit)
-  HIP_OR_FAIL(e, d.out4.ensure(sizeof(float4) * (size_t)n));
   {
     ProfScope ps(e, "deskew");
     deskew_points_kernel<<<(n + 255) / 256, 256, 0, e->stream>>>(d.cloud.pts.as<float4>(), n, d_times, d_time_stride, k.segs.as<double>(), nseg, d.out.as<float>(), d.out4.as<float4>());
   }
   HIP_OR_FAIL(e, hipGetLastError());
   HIP_OR_FAIL(e, hipStreamSynchronize(e->stream));
-  d.out_n = n;
-  d.out4_valid = true;
-  d.out_stream = e->stream;
-  d.out_complete = true;
-  *out_n = n;
-  return FVH_OK;
+  return stage_publish(e, d, o, LAST_DESKEW, n, out_n);
 }

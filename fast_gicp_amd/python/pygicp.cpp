@@ -110,50 +110,53 @@ static py::array_t<double> downsample(const Points& points, double resolution) {
   return cloud2numpy(filtered);
 }
 
-// downsample on the device: the same filter (pcl::ApproximateVoxelGrid semantics, or pcl::VoxelGrid with exact=True), bit-identical
-// output in the same order, computed by fvh_voxelgrid_* (kernels_downsample.hpp)
-static py::array_t<double> downsample_device(const Points& points, double resolution, bool exact, int device) {
-  auto cloud = numpy2cloud(points);
-  const std::vector<float> xyz = detail::pack_xyz(*cloud);
+// A filter handle for the length of one binding call: destroyed with the scope; check() throws with the handle's last error
+struct TempVoxelGrid {
   fvh_voxelgrid* vg = nullptr;
-  detail::check(fvh_voxelgrid_create(device, &vg), "fvh_voxelgrid_create", "cannot create the HIP engine (no GPU? there is no CPU fallback)");
-  int n = 0;
-  int rc = fvh_voxelgrid_filter(vg, exact ? FVH_VOXELGRID_EXACT : FVH_VOXELGRID_APPROXIMATE, xyz.data(), (int)cloud->size(), (float)resolution, &n);
+  explicit TempVoxelGrid(int device) { detail::check(fvh_voxelgrid_create(device, &vg), "fvh_voxelgrid_create", "cannot create the HIP engine (no GPU? there is no CPU fallback)"); }
+  ~TempVoxelGrid() { fvh_voxelgrid_destroy(vg); }
+  TempVoxelGrid(const TempVoxelGrid&) = delete;
+  TempVoxelGrid& operator=(const TempVoxelGrid&) = delete;
+  operator fvh_voxelgrid*() const { return vg; }
+  void check(int rc, const char* what) const { if (rc) detail::check(rc, what, fvh_voxelgrid_last_error(vg)); }
+};
+
+// The n points of the handle's last call as an (n, 3) float64 array (fvh_voxelgrid_get_points); a refused call (rc) throws as `what`
+static py::array_t<double> filtered_points(const TempVoxelGrid& vg, int rc, int n, const char* what) {
   std::vector<float> out((size_t)3 * n);
   if (!rc) rc = fvh_voxelgrid_get_points(vg, out.data());
-  const std::string err = rc ? fvh_voxelgrid_last_error(vg) : "";
-  fvh_voxelgrid_destroy(vg);
-  detail::check(rc, "fvh_voxelgrid_filter", err.c_str());
+  vg.check(rc, what);
   py::array_t<double> res({(py::ssize_t)n, (py::ssize_t)3});
   auto w = res.mutable_unchecked<2>();
   for (int i = 0; i < n; i++) for (int a = 0; a < 3; a++) w(i, a) = out[3 * (size_t)i + a];
   return res;
 }
 
-// The kept points of a filter call as an (m, 3) float64 array (fvh_voxelgrid_get_points), optionally with their indices into the input
-static py::object filtered_result(fvh_voxelgrid* vg, int rc, int n, bool return_indices, const char* what) {
-  std::vector<float> out((size_t)3 * n);
-  std::vector<int> idx(return_indices ? (size_t)n : 0);
-  if (!rc) rc = fvh_voxelgrid_get_points(vg, out.data());
-  if (!rc && return_indices) rc = fvh_voxelgrid_get_kept_indices(vg, idx.data());
-  const std::string err = rc ? fvh_voxelgrid_last_error(vg) : "";
-  fvh_voxelgrid_destroy(vg);
-  detail::check(rc, what, err.c_str());
-  py::array_t<double> res({(py::ssize_t)n, (py::ssize_t)3});
-  auto w = res.mutable_unchecked<2>();
-  for (int i = 0; i < n; i++) for (int a = 0; a < 3; a++) w(i, a) = out[3 * (size_t)i + a];
+// ... optionally with their indices into the input (fvh_voxelgrid_get_kept_indices)
+static py::object filtered_result(const TempVoxelGrid& vg, int rc, int n, bool return_indices, const char* what) {
+  py::array_t<double> res = filtered_points(vg, rc, n, what);
   if (!return_indices) return std::move(res);
   py::array_t<int> ids((py::ssize_t)n);
-  std::copy(idx.begin(), idx.end(), ids.mutable_data());
+  vg.check(fvh_voxelgrid_get_kept_indices(vg, ids.mutable_data()), what);
   return py::make_tuple(res, ids);
+}
+
+// downsample on the device: the same filter (pcl::ApproximateVoxelGrid semantics, or pcl::VoxelGrid with exact=True), bit-identical
+// output in the same order, computed by fvh_voxelgrid_* (kernels_downsample.hpp)
+static py::array_t<double> downsample_device(const Points& points, double resolution, bool exact, int device) {
+  auto cloud = numpy2cloud(points);
+  const std::vector<float> xyz = detail::pack_xyz(*cloud);
+  TempVoxelGrid vg(device);
+  int n = 0;
+  const int rc = fvh_voxelgrid_filter(vg, exact ? FVH_VOXELGRID_EXACT : FVH_VOXELGRID_APPROXIMATE, xyz.data(), (int)cloud->size(), (float)resolution, &n);
+  return filtered_points(vg, rc, n, "fvh_voxelgrid_filter");
 }
 
 // the origin / range filter of the reference's callers (src/align.cpp:127-133) on the device: fvh_voxelgrid_crop_range
 static py::object crop_range_device(const Points& points, double min_sq_norm, double max_sq_norm, bool return_indices, int device) {
   auto cloud = numpy2cloud(points);
   const std::vector<float> xyz = detail::pack_xyz(*cloud);
-  fvh_voxelgrid* vg = nullptr;
-  detail::check(fvh_voxelgrid_create(device, &vg), "fvh_voxelgrid_create", "cannot create the HIP engine (no GPU? there is no CPU fallback)");
+  TempVoxelGrid vg(device);
   int n = 0;
   const int rc = fvh_voxelgrid_crop_range(vg, xyz.data(), (int)cloud->size(), min_sq_norm, max_sq_norm, &n);
   return filtered_result(vg, rc, n, return_indices, "fvh_voxelgrid_crop_range");
@@ -165,8 +168,7 @@ static py::object remove_outliers_device(const Points& points, const std::string
   if (method != "STATISTICAL" && method != "RADIUS") throw std::invalid_argument("unknown outlier removal method " + method + " (STATISTICAL, RADIUS)");
   auto cloud = numpy2cloud(points);
   const std::vector<float> xyz = detail::pack_xyz(*cloud);
-  fvh_voxelgrid* vg = nullptr;
-  detail::check(fvh_voxelgrid_create(device, &vg), "fvh_voxelgrid_create", "cannot create the HIP engine (no GPU? there is no CPU fallback)");
+  TempVoxelGrid vg(device);
   int n = 0;
   const bool stat = method == "STATISTICAL";
   const int rc = stat ? fvh_voxelgrid_remove_statistical_outliers(vg, xyz.data(), (int)cloud->size(), mean_k, stddev_mul, &n)
@@ -179,15 +181,11 @@ static py::object remove_outliers_device(const Points& points, const std::string
 static py::tuple cluster_euclidean_device(const Points& points, double tolerance, int min_cluster_size, int max_cluster_size, int device) {
   auto cloud = numpy2cloud(points);
   const std::vector<float> xyz = detail::pack_xyz(*cloud);
-  fvh_voxelgrid* vg = nullptr;
-  detail::check(fvh_voxelgrid_create(device, &vg), "fvh_voxelgrid_create", "cannot create the HIP engine (no GPU? there is no CPU fallback)");
+  TempVoxelGrid vg(device);
   int n = 0, nc = 0;
-  int rc = fvh_voxelgrid_cluster_euclidean(vg, xyz.data(), (int)cloud->size(), tolerance, min_cluster_size, max_cluster_size, &nc, &n);
+  vg.check(fvh_voxelgrid_cluster_euclidean(vg, xyz.data(), (int)cloud->size(), tolerance, min_cluster_size, max_cluster_size, &nc, &n), "fvh_voxelgrid_cluster_euclidean");
   py::array_t<int> labels((py::ssize_t)cloud->size()), sizes((py::ssize_t)nc);
-  if (!rc) rc = fvh_voxelgrid_get_cluster_labels(vg, labels.mutable_data(), sizes.mutable_data());
-  const std::string err = rc ? fvh_voxelgrid_last_error(vg) : "";
-  fvh_voxelgrid_destroy(vg);
-  detail::check(rc, "fvh_voxelgrid_cluster_euclidean", err.c_str());
+  vg.check(fvh_voxelgrid_get_cluster_labels(vg, labels.mutable_data(), sizes.mutable_data()), "fvh_voxelgrid_cluster_euclidean");
   return py::make_tuple(labels, sizes);
 }
 
@@ -202,17 +200,14 @@ static py::tuple segment_plane_device(const Points& points, double distance_thre
     ax = axis.cast<std::vector<double>>();
     if (ax.size() != 3) throw std::invalid_argument("segment_plane_device: axis must have 3 components");
   }
-  fvh_voxelgrid* vg = nullptr;
-  detail::check(fvh_voxelgrid_create(device, &vg), "fvh_voxelgrid_create", "cannot create the HIP engine (no GPU? there is no CPU fallback)");
+  TempVoxelGrid vg(device);
   int n = 0, inliers = 0;
   py::array_t<double> co((py::ssize_t)4);
-  int rc = fvh_voxelgrid_segment_plane(vg, xyz.data(), (int)cloud->size(), distance_threshold, max_iterations, seed, ax.empty() ? nullptr : ax.data(), eps_angle,
-                                       (keep_outliers ? FVH_PLANE_KEEP_OUTLIERS : 0) | (refine ? FVH_PLANE_REFINE : 0), co.mutable_data(), &inliers, &n);
+  vg.check(fvh_voxelgrid_segment_plane(vg, xyz.data(), (int)cloud->size(), distance_threshold, max_iterations, seed, ax.empty() ? nullptr : ax.data(), eps_angle,
+                                       (keep_outliers ? FVH_PLANE_KEEP_OUTLIERS : 0) | (refine ? FVH_PLANE_REFINE : 0), co.mutable_data(), &inliers, &n),
+           "fvh_voxelgrid_segment_plane");
   py::array_t<int> ids((py::ssize_t)n);
-  if (!rc) rc = fvh_voxelgrid_get_kept_indices(vg, ids.mutable_data());
-  const std::string err = rc ? fvh_voxelgrid_last_error(vg) : "";
-  fvh_voxelgrid_destroy(vg);
-  detail::check(rc, "fvh_voxelgrid_segment_plane", err.c_str());
+  vg.check(fvh_voxelgrid_get_kept_indices(vg, ids.mutable_data()), "fvh_voxelgrid_segment_plane");
   return py::make_tuple(co, ids);
 }
 
@@ -233,11 +228,10 @@ static py::array_t<double> deskew_device(const Points& points, const py::array_t
   auto r = knot_poses.unchecked<3>();
   for (int k = 0; k < K; k++) for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) poses[(size_t)16 * k + j * 4 + i] = r(k, i, j);
   const double ref = t_ref.is_none() ? knot_times.data()[K - 1] : t_ref.cast<double>();
-  fvh_voxelgrid* vg = nullptr;
-  detail::check(fvh_voxelgrid_create(device, &vg), "fvh_voxelgrid_create", "cannot create the HIP engine (no GPU? there is no CPU fallback)");
+  TempVoxelGrid vg(device);
   int n = 0;
   const int rc = fvh_voxelgrid_deskew(vg, xyz.data(), (int)cloud->size(), t.data(), 1, knot_times.data(), poses.data(), K, ref, &n);
-  return filtered_result(vg, rc, n, false, "fvh_voxelgrid_deskew").cast<py::array_t<double>>();
+  return filtered_points(vg, rc, n, "fvh_voxelgrid_deskew");
 }
 
 // align_points, main.cpp:64-150. "VGICP" (the CPU FastVGICP in the reference, main.cpp:102-108) runs on the same GPU engine in

@@ -165,10 +165,15 @@ def test_header_library_and_capi_expose_clustering():
     for k in ("cluster_init_kernel", "cluster_link_kernel", "cluster_flatten_kernel", "cluster_flag_kernel", "cluster_label_kernel"):
         assert re.search(r"__global__[^;{]*\b%s\b" % k, src), k
         assert re.search(r"\b%s<<<" % k, host), k
-    for k in ("outlier_finite_kernel<<<", "outlier_compact_kernel<<<", "ensure_sorted(", "device_scan("):  # the existing stages are reused, not copied
+    stage = open(os.path.join(util.ROOT, "fast_gicp_amd", "csrc", "host_filter_stage.inc.hpp")).read()
+    for k in ("mask_stage_setup(", "mask_stage_compact(", "mask_stage_finish(", "ensure_sorted(", "device_scan("):  # the existing stages are reused, not copied
         assert k in host, k
-    assert host.index("upload_cloud(") < host.index("d.out.ensure(")  # the input is widened before the output state is touched
-    assert host.count("hipStreamSynchronize(") == 2 and host.count("hipMemcpyDeviceToHost") == 1  # one per entry point; one readback of the control words
+    for k in ("outlier_finite_kernel<<<", "outlier_compact_kernel<<<", "device_scan("):  # (the shared layer launches what every mask stage launches)
+        assert k in stage and (k == "device_scan(" or k not in host), k
+    assert "upload_cloud(" not in host and "d.out.ensure(" not in host and stage.index("upload_cloud(") < stage.index("d.out.ensure(")  # the input is widened before the output state is touched
+    # one synchronisation per entry point and one readback of the control words: the call's are the shared finish's, the getter's its own
+    assert host.count("hipStreamSynchronize(") == 1 and host.count("hipMemcpyDeviceToHost") == 0 and host.count("mask_stage_finish(") == 1
+    assert stage.count("hipStreamSynchronize(") == 1 and stage.count("hipMemcpyDeviceToHost") == 1
     # every access to parent[] in the link kernel is an agent-scope atomic
     link = src[src.index("void cluster_link_kernel"):src.index("void cluster_flatten_kernel")]
     assert not re.search(r"parent\s*\[", link) and "__HIP_MEMORY_SCOPE_AGENT" in src and "atomicCAS(" in src

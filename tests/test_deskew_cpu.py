@@ -180,7 +180,8 @@ def test_header_library_and_upper_layers_expose_deskew():
     csrc = os.path.join(util.ROOT, "fast_gicp_amd", "csrc")
     src, host, capi_src = (open(os.path.join(csrc, f)).read() for f in ("kernels_deskew.hpp", "host_deskew.inc.hpp", "fvh_capi.hip"))
     assert re.search(r"__global__[^;{]*\bdeskew_points_kernel\b", src) and re.search(r"\bdeskew_points_kernel<<<", host)
-    assert host.index("upload_cloud(") < host.index("d.out.ensure(")  # the input is widened before the output state is touched
+    stage = open(os.path.join(csrc, "host_filter_stage.inc.hpp")).read()  # the upload every stage shares
+    assert host.index("stage_upload(") < host.index("deskew_points_kernel<<<") and stage.index("upload_cloud(") < stage.index("d.out.ensure(")  # the input is widened before the output state is touched
     assert capi_src.index('#include "host_outlier.inc.hpp"') < capi_src.index('#include "host_deskew.inc.hpp"')
     for f in ("kernels_deskew.hpp", "host_deskew.inc.hpp"):
         assert any(s.endswith(os.sep + f) for s in build.SOURCES), f

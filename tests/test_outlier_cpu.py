@@ -115,10 +115,11 @@ def test_header_library_and_capi_expose_the_filters():
     # the kernels are device code of the library's one translation unit, launched by the host section
     src = open(os.path.join(util.ROOT, "fast_gicp_amd", "csrc", "kernels_outlier.hpp")).read()
     host = open(os.path.join(util.ROOT, "fast_gicp_amd", "csrc", "host_outlier.inc.hpp")).read()
+    stage = open(os.path.join(util.ROOT, "fast_gicp_amd", "csrc", "host_filter_stage.inc.hpp")).read()  # set-up and compaction of every mask stage
     for k in ("outlier_radius_count_kernel", "outlier_mean_dist_kernel", "outlier_stats_kernel", "outlier_flag_kernel", "crop_flag_kernel", "outlier_compact_kernel"):
         assert re.search(r"__global__[^;{]*\b%s\b" % k, src), k
-        assert re.search(r"\b%s(<\d+>)?<<<" % k, host), k
-    assert "upload_cloud(" in host and host.index("upload_cloud(") < host.index("d.out.ensure(")  # the input is widened before the output state is touched
+        assert re.search(r"\b%s(<\d+>)?<<<" % k, stage if k == "outlier_compact_kernel" else host), k
+    assert "mask_stage_setup(" in host and "upload_cloud(" in stage and stage.index("upload_cloud(") < stage.index("d.out.ensure(")  # the input is widened before the output state is touched
     for f in ("kernels_outlier.hpp", "host_outlier.inc.hpp"):
         assert any(s.endswith(os.sep + f) for s in build.SOURCES), f
     pyg = open(os.path.join(util.ROOT, "fast_gicp_amd", "python", "pygicp.cpp")).read()

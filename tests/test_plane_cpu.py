@@ -162,13 +162,18 @@ def test_header_library_and_capi_expose_plane_segmentation():
         assert re.search(r"__global__[^;{]*\b%s\b" % k, src), k
         assert re.search(r"\b%s<<<" % k, host), k
         assert not any(s in k for s in TAKEN), k
-    for k in ("outlier_finite_kernel<<<", "outlier_compact_kernel<<<", "device_scan("):  # the existing stages are reused, not copied
+    stage = open(os.path.join(util.ROOT, "fast_gicp_amd", "csrc", "host_filter_stage.inc.hpp")).read()
+    for k in ("mask_stage_setup(", "mask_stage_compact(", "mask_stage_finish("):  # the existing stages are reused, not copied
         assert k in host, k
+    for k in ("outlier_finite_kernel<<<", "outlier_compact_kernel<<<", "device_scan("):  # (the shared layer launches what every mask stage launches)
+        assert k in stage and k not in host, k
     assert "ensure_sorted(" not in host  # no Morton sort: the samples are input indices, the sweep is dense
     assert "sym_eig3(" in src and "sqrt(" not in src[src.index("void plane_sweep_kernel"):src.index("void plane_winner_kernel")]
     assert src.count("#pragma clang fp contract(off)") >= 5 and not re.search(r"atomic\w*\([^;]*(float|double)", src)
-    assert host.index("upload_cloud(") < host.index("d.out.ensure(")  # the input is widened before the output state is touched
-    assert host.count("hipStreamSynchronize(") == 2 and host.count("hipMemcpyDeviceToHost") == 1  # one per entry point; one readback of the control words
+    assert "upload_cloud(" not in host and "d.out.ensure(" not in host and stage.index("upload_cloud(") < stage.index("d.out.ensure(")  # the input is widened before the output state is touched
+    # one synchronisation per entry point and one readback of the control words: the call's are the shared finish's, the getter's its own
+    assert host.count("hipStreamSynchronize(") == 1 and host.count("hipMemcpyDeviceToHost") == 0 and host.count("mask_stage_finish(") == 1
+    assert stage.count("hipStreamSynchronize(") == 1 and stage.count("hipMemcpyDeviceToHost") == 1
     for f in ("kernels_plane.hpp", "host_plane.inc.hpp"):
         assert any(s.endswith(os.sep + f) for s in build.SOURCES), f
     capi_hip = open(os.path.join(util.ROOT, "fast_gicp_amd", "csrc", "fvh_capi.hip")).read()
