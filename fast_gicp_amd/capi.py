@@ -54,6 +54,11 @@ class MapScore(C.Structure):
                 ("sum_best_m2", C.c_double), ("sum_score_max", C.c_double), ("sum_score_all", C.c_double)]
 
 
+class RayCast(C.Structure):
+    """fvh_ray_cast (include/fast_vgicp_hip.h): what fvh_*_cast_rays_source / _cast_rays_cloud report"""
+    _fields_ = [("n_rays", C.c_int), ("n_used", C.c_int), ("n_hit", C.c_int), ("n_hit_at_origin", C.c_int), ("n_cells", C.c_longlong)]
+
+
 class FvhError(RuntimeError):
     pass
 
@@ -404,6 +409,75 @@ class _MapScoring:
         r["tp"] = r["sum_score_all"] / r["n_used"] if r["n_used"] else nan
         if per_point:
             r["found"], r["best"], r["best_m2"] = found, best, best_m2
+        return r
+
+
+def ray_endpoints(origin, directions, length, T=None):
+    """Rays given as directions, for map_cast_rays: -> (xyz, max_range). xyz: float32 (m, 3) endpoints origin + length * unit direction in the
+    scan frame (directions need not be unit; length: a scalar or one value per ray); max_range: the value to pass with them at pose T (4x4,
+    default identity), chosen so that NO ray of these is skipped for range: the library measures a ray between the float32 roundings of the
+    POSED origin and endpoint, which can come out longer than `length` by a few float32 roundings of the posed coordinates. Needs no GPU."""
+    o = np.asarray(origin, np.float64).reshape(3)
+    d = np.asarray(directions, np.float64).reshape(-1, 3)
+    norm = np.sqrt((d * d).sum(axis=1))
+    if not (np.all(np.isfinite(o)) and np.all(np.isfinite(d)) and np.all(norm > 0.0)):
+        raise FvhError("ray_endpoints: origin and directions must be finite and no direction may be zero")
+    ln = np.broadcast_to(np.asarray(length, np.float64), (len(d),))
+    if not (np.all(np.isfinite(ln)) and np.all(ln > 0.0)):
+        raise FvhError("ray_endpoints: length must be finite and > 0")
+    xyz = (o + d / norm[:, None] * ln[:, None]).astype(np.float32)
+    if not len(xyz):
+        return xyz, 0.0
+    # the library's own measure, r = |(float)(R p + t) - (float)(R o + t)|, formed here in numpy; how numpy adds up R p + t may move a
+    # float32 rounding by one ulp of the posed coordinate on either end, per axis: four ulps of the largest posed magnitude times sqrt(3) cover it
+    M = np.eye(4) if T is None else np.asarray(T, np.float64).reshape(4, 4)
+    po = (M[:3, :3] @ o + M[:3, 3]).astype(np.float32).astype(np.float64)
+    pp = (xyz.astype(np.float64) @ M[:3, :3].T + M[:3, 3]).astype(np.float32).astype(np.float64)
+    r = float(np.sqrt(((pp - po) ** 2).sum(axis=1)).max())
+    big = max(float(np.abs(po).max()), float(np.abs(pp).max()))
+    return xyz, r + 4.0 * 2.0 ** -23 * big * 1.7320508075688772 + r * 2.0 ** -50
+
+
+class _RayCasting:
+    """Rays cast into the handle's target voxel map, batch or incremental (include/fast_vgicp_hip.h: fvh_{vgicp,ndt}_cast_rays_source /
+    _cast_rays_cloud): mixed into VGICPMapCore and NDTMapCore, the handle classes for scan-to-map work."""
+
+    def map_cast_rays(self, T=None, xyz=None, device_ptr=None, n=None, stride=3, origin=None, min_range=0.0, max_range=100.0, min_points=1, max_m2=float("inf"), per_ray=True):
+        """What the map says a sensor at pose T (4x4, default identity) should see along each ray: the segments from `origin` (scan frame,
+        None: (0, 0, 0)) to the current source points (xyz and device_ptr None), to the host points xyz (m, 3), or to n device points at
+        device_ptr (stride 3 or 4 floats) are walked through the grid; in every voxel with >= min_points points the segment's point of
+        smallest squared Mahalanobis distance to the voxel's Gaussian is found, and the first voxel where it is <= max_m2 (and beyond
+        min_range metres) is the hit. Rays longer than max_range are skipped. Read-only on the handle. -> dict of the struct's fields;
+        per_ray adds hit (int32: 1, 0 no hit, -1 skipped), cell (m, 3) int32, range and m2 (float64), one row per ray in input order.
+        (ray_endpoints() makes endpoints and a max_range out of directions.)"""
+        t = _IDENTITY16 if T is None else _colmajor16(T)
+        o = None if origin is None else np.ascontiguousarray(origin, np.float64).reshape(3)
+        out = RayCast()
+        head = (_p(t), None if o is None else _p(o), C.c_double(min_range), C.c_double(max_range), int(min_points), C.c_double(max_m2), C.byref(out))
+        if device_ptr is not None:
+            m = int(n)
+        elif xyz is not None:
+            a = _f32(xyz).reshape(-1, 3)
+            m = len(a)
+        else:  # the rows a cast to the source writes are the source cloud's
+            cnt = C.c_int(0)
+            if per_ray:
+                self._call("get_num_source_points", C.byref(cnt))
+            m = cnt.value
+        hit = np.empty(m, np.int32) if per_ray else None
+        cell = np.empty((m, 3), np.int32) if per_ray else None
+        rng = np.empty(m, np.float64) if per_ray else None
+        m2 = np.empty(m, np.float64) if per_ray else None
+        rows = tuple(_p(v) if per_ray and m else None for v in (hit, cell, rng, m2))
+        if device_ptr is not None:
+            self._call("cast_rays_cloud", C.c_void_p(device_ptr), m, int(stride), 1, *head, *rows)
+        elif xyz is not None:
+            self._call("cast_rays_cloud", _p(a) if m else None, m, 3, 0, *head, *rows)
+        else:
+            self._call("cast_rays_source", *head, *rows)
+        r = {name: getattr(out, name) for name, _ in RayCast._fields_}
+        if per_ray:
+            r["hit"], r["cell"], r["range"], r["m2"] = hit, cell, rng, m2
         return r
 
 
@@ -938,7 +1012,7 @@ class VGICPCore(_Core, _IncrementalMap):
         return n.value
 
 
-class VGICPMapCore(VGICPCore, _MapTarget, _PosedMap, _RayClearing, _MapScoring):
+class VGICPMapCore(VGICPCore, _MapTarget, _PosedMap, _RayClearing, _MapScoring, _RayCasting):
     """A VGICP handle for scan-to-map work: VGICPCore (which has the map_* calls) + target_from_map / get_target_points, on the same C handle
     type -- as NDTMapCore is to NDTCore."""
 
@@ -1286,7 +1360,7 @@ class NDTCore(_Core):
         return coords, num, means, covs
 
 
-class NDTMapCore(NDTCore, _IncrementalMap, _MapTarget, _PosedMap, _RayClearing, _MapScoring):
+class NDTMapCore(NDTCore, _IncrementalMap, _MapTarget, _PosedMap, _RayClearing, _MapScoring, _RayCasting):
     """An NDT handle with the calls of its incremental target map (include/fast_vgicp_hip.h: fvh_ndt_map_* / fvh_ndt_voxelmap_*): map_begin,
     map_insert_source, map_prune, map_info, map_export, map_import, map_merge_from, map_save come from _IncrementalMap as on VGICPCore; NDT
     voxels take points only. Everything else is NDTCore's, on the same C handle type."""

@@ -33,6 +33,7 @@
 #include "kernels_sort.hpp"
 #include "kernels_voxelmap.hpp"
 #include "kernels_mapscore.hpp"
+#include "kernels_raycast.hpp"
 
 using namespace fvh;
 
@@ -890,6 +891,48 @@ int map_score(H* h, bool from_source, const float* xyz, int n, int stride_floats
   out->n_points = n;
   return FVH_OK;
 }
+// rays origin3 -> endpoint, both at pose T16, cast into the CURRENT target voxel map (batch or incremental): the first hit per ray. The endpoints
+// are staged and walked as map_score's points are; read-only on the handle; an overflowed hint-sized batch table is rebuilt first.
+template <class H>
+int map_cast_rays(H* h, bool from_source, const float* xyz, int n, int stride_floats, int on_device, const double* T16, const double* origin3, double min_range, double max_range,
+                  int min_points, double max_m2, fvh_ray_cast* out, int* hit, int* cell3, double* range, double* m2) {
+  const char* who = from_source ? "cast_rays_source" : "cast_rays_cloud";
+  Engine* e = &h->e;
+  if (h->multi_gpu()) return e->fail(FVH_ERR_UNSUPPORTED, std::string(who) + ": not on a multi-GPU handle (communicator / peers / tile / map sharding)");
+  VoxelMapDev& vm = h->target_map();
+  if (!vm.valid || vm.capacity == 0) return e->fail(FVH_ERR_BAD_STATE, std::string(who) + ": no target voxel map (create_target_voxelmap or " + H::prefix + "_map_begin)");
+  if (from_source && !h->source.has_pts) return e->fail(FVH_ERR_BAD_STATE, std::string(who) + ": the source cloud is not set");
+  { const int rc = map_cast_check(e, vm, T16, origin3, min_range, max_range, max_m2, out, who); if (rc) return rc; }
+  const float* d_xyz = nullptr;
+  const int* order = nullptr;
+  int stride = 4;
+  if (from_source) {
+    n = h->source.n;
+    d_xyz = h->source.pts.template as<float>();
+    order = coherent_order(h->source, e->params.coherent_min_points);
+  } else {
+    if (n < 0) return e->fail(FVH_ERR_INVALID_ARGUMENT, std::string(who) + ": n < 0");
+    if (n > 0 && !xyz) return e->fail(FVH_ERR_INVALID_ARGUMENT, std::string(who) + ": null points with n > 0");
+    if (stride_floats != 3 && stride_floats != 4) return e->fail(FVH_ERR_INVALID_ARGUMENT, std::string(who) + ": stride must be 3 or 4 floats");
+    stride = stride_floats;
+    d_xyz = xyz;
+    if (!on_device && n > 0) {
+      const size_t bytes = sizeof(float) * (size_t)stride * (size_t)n;
+      HIP_OR_FAIL(e, vm.score_xyz.ensure(bytes));
+      HIP_OR_FAIL(e, hipMemcpyAsync(vm.score_xyz.p, xyz, bytes, hipMemcpyHostToDevice, e->stream));
+      d_xyz = vm.score_xyz.template as<float>();
+    }
+  }
+  for (int attempt = 0;; attempt++) {
+    bool overflowed = false;
+    { const int rc = map_cast_run(e, h->target_map(), d_xyz, stride, n, order, T16, origin3, min_range, max_range, min_points, max_m2, out, hit, cell3, range, m2, &overflowed); if (rc) return rc; }
+    if (!overflowed) break;
+    if (attempt == 1) return e->fail(FVH_ERR_BAD_STATE, std::string(who) + ": voxel map overflow persists after safe rebuild");
+    { const int rc = h->rebuild_safe()(); if (rc) return rc; }
+  }
+  out->n_rays = n;
+  return FVH_OK;
+}
 template <class H>
 int map_get_info(H* h, int* incremental, int* num_voxels, int* capacity, int* num_inserts, long long* num_points, int* num_dropped) {
   VoxelMapDev& vm = h->target_map();
@@ -1000,6 +1043,8 @@ int fvh_vgicp_clear_rays_source(fvh_vgicp* h, const double* T16, const double* o
 int fvh_vgicp_clear_rays_cloud(fvh_vgicp* h, const float* xyz, int n, int stride_floats, int on_device, const double* T16, const double* origin3, double min_range, double max_range, double end_margin, int min_misses, int* num_removed, int* rays_used) { CHECK_HANDLE(h); return shared::map_clear_rays(h, false, xyz, n, stride_floats, on_device, T16, origin3, min_range, max_range, end_margin, min_misses, num_removed, rays_used); }
 int fvh_vgicp_score_source(fvh_vgicp* h, const double* T16, int neighbors, int min_points, double max_m2, double score_scale, fvh_map_score* out, int* found, int* best, double* best_m2) { CHECK_HANDLE(h); return shared::map_score(h, true, nullptr, 0, 4, 1, T16, neighbors, min_points, max_m2, score_scale, out, found, best, best_m2); }
 int fvh_vgicp_score_cloud(fvh_vgicp* h, const float* xyz, int n, int stride_floats, int on_device, const double* T16, int neighbors, int min_points, double max_m2, double score_scale, fvh_map_score* out, int* found, int* best, double* best_m2) { CHECK_HANDLE(h); return shared::map_score(h, false, xyz, n, stride_floats, on_device, T16, neighbors, min_points, max_m2, score_scale, out, found, best, best_m2); }
+int fvh_vgicp_cast_rays_source(fvh_vgicp* h, const double* T16, const double* origin3, double min_range, double max_range, int min_points, double max_m2, fvh_ray_cast* out, int* hit, int* cell3, double* range, double* m2) { CHECK_HANDLE(h); return shared::map_cast_rays(h, true, nullptr, 0, 4, 1, T16, origin3, min_range, max_range, min_points, max_m2, out, hit, cell3, range, m2); }
+int fvh_vgicp_cast_rays_cloud(fvh_vgicp* h, const float* xyz, int n, int stride_floats, int on_device, const double* T16, const double* origin3, double min_range, double max_range, int min_points, double max_m2, fvh_ray_cast* out, int* hit, int* cell3, double* range, double* m2) { CHECK_HANDLE(h); return shared::map_cast_rays(h, false, xyz, n, stride_floats, on_device, T16, origin3, min_range, max_range, min_points, max_m2, out, hit, cell3, range, m2); }
 int fvh_vgicp_map_get_info(fvh_vgicp* h, int* incremental, int* num_voxels, int* capacity, int* num_inserts, long long* num_points, int* num_dropped) { CHECK_HANDLE(h); return shared::map_get_info(h, incremental, num_voxels, capacity, num_inserts, num_points, num_dropped); }
 int fvh_vgicp_voxelmap_export(fvh_vgicp* h, int* num_voxels, double* resolution, int* mode, int* num_inserts, long long* num_points, int* coords3, double* sums10, unsigned* ages) { CHECK_HANDLE(h); return shared::voxelmap_export(h, num_voxels, resolution, mode, num_inserts, num_points, coords3, sums10, ages); }
 int fvh_vgicp_voxelmap_import(fvh_vgicp* h, int n, const int* coords3, const double* sums10, const unsigned* ages, double resolution, int mode, int num_inserts, long long num_points) { CHECK_HANDLE(h); return shared::voxelmap_import(h, n, coords3, sums10, ages, resolution, mode, num_inserts, num_points); }
@@ -1675,6 +1720,8 @@ int fvh_ndt_clear_rays_source(fvh_ndt* h, const double* T16, const double* origi
 int fvh_ndt_clear_rays_cloud(fvh_ndt* h, const float* xyz, int n, int stride_floats, int on_device, const double* T16, const double* origin3, double min_range, double max_range, double end_margin, int min_misses, int* num_removed, int* rays_used) { CHECK_HANDLE(h); return shared::map_clear_rays(h, false, xyz, n, stride_floats, on_device, T16, origin3, min_range, max_range, end_margin, min_misses, num_removed, rays_used); }
 int fvh_ndt_score_source(fvh_ndt* h, const double* T16, int neighbors, int min_points, double max_m2, double score_scale, fvh_map_score* out, int* found, int* best, double* best_m2) { CHECK_HANDLE(h); return shared::map_score(h, true, nullptr, 0, 4, 1, T16, neighbors, min_points, max_m2, score_scale, out, found, best, best_m2); }
 int fvh_ndt_score_cloud(fvh_ndt* h, const float* xyz, int n, int stride_floats, int on_device, const double* T16, int neighbors, int min_points, double max_m2, double score_scale, fvh_map_score* out, int* found, int* best, double* best_m2) { CHECK_HANDLE(h); return shared::map_score(h, false, xyz, n, stride_floats, on_device, T16, neighbors, min_points, max_m2, score_scale, out, found, best, best_m2); }
+int fvh_ndt_cast_rays_source(fvh_ndt* h, const double* T16, const double* origin3, double min_range, double max_range, int min_points, double max_m2, fvh_ray_cast* out, int* hit, int* cell3, double* range, double* m2) { CHECK_HANDLE(h); return shared::map_cast_rays(h, true, nullptr, 0, 4, 1, T16, origin3, min_range, max_range, min_points, max_m2, out, hit, cell3, range, m2); }
+int fvh_ndt_cast_rays_cloud(fvh_ndt* h, const float* xyz, int n, int stride_floats, int on_device, const double* T16, const double* origin3, double min_range, double max_range, int min_points, double max_m2, fvh_ray_cast* out, int* hit, int* cell3, double* range, double* m2) { CHECK_HANDLE(h); return shared::map_cast_rays(h, false, xyz, n, stride_floats, on_device, T16, origin3, min_range, max_range, min_points, max_m2, out, hit, cell3, range, m2); }
 int fvh_ndt_map_get_info(fvh_ndt* h, int* incremental, int* num_voxels, int* capacity, int* num_inserts, long long* num_points, int* num_dropped) { CHECK_HANDLE(h); return shared::map_get_info(h, incremental, num_voxels, capacity, num_inserts, num_points, num_dropped); }
 int fvh_ndt_voxelmap_export(fvh_ndt* h, int* num_voxels, double* resolution, int* mode, int* num_inserts, long long* num_points, int* coords3, double* sums10, unsigned* ages) { CHECK_HANDLE(h); return shared::voxelmap_export(h, num_voxels, resolution, mode, num_inserts, num_points, coords3, sums10, ages); }
 int fvh_ndt_voxelmap_import(fvh_ndt* h, int n, const int* coords3, const double* sums10, const unsigned* ages, double resolution, int mode, int num_inserts, long long num_points) { CHECK_HANDLE(h); return shared::voxelmap_import(h, n, coords3, sums10, ages, resolution, mode, num_inserts, num_points); }

@@ -342,6 +342,65 @@ int map_score_run(Engine* e, VoxelMapDev& vm, const float* d_xyz, int stride, in
   return FVH_OK;
 }
 
+// ---- rays cast into the target voxel map: the first hit per ray (fvh_*_cast_rays_source / _cast_rays_cloud; kernels_raycast.hpp) ----------
+static_assert(sizeof(fvh_ray_cast) == sizeof(VmCastOut) && offsetof(fvh_ray_cast, n_hit_at_origin) == offsetof(VmCastOut, n_hit_at_origin) &&
+              offsetof(fvh_ray_cast, n_cells) == offsetof(VmCastOut, n_cells) && sizeof(long long) == 8,
+              "VmCastOut is the device image of fvh_ray_cast");
+// what the host refuses before anything is queued (the cloud's own arguments -- n, xyz, stride -- are the caller's)
+int map_cast_check(Engine* e, const VoxelMapDev& vm, const double* T16, const double* origin3, double min_range, double max_range, double max_m2, const fvh_ray_cast* out, const char* who) {
+  const std::string w(who);
+  if (!T16) return e->fail(FVH_ERR_INVALID_ARGUMENT, w + ": null pose");
+  for (int i = 0; i < 16; i++)
+    if (!std::isfinite(T16[i])) return e->fail(FVH_ERR_INVALID_ARGUMENT, w + ": the pose is not finite");
+  if (origin3 && !(std::isfinite(origin3[0]) && std::isfinite(origin3[1]) && std::isfinite(origin3[2]))) return e->fail(FVH_ERR_INVALID_ARGUMENT, w + ": the origin is not finite");
+  if (!out) return e->fail(FVH_ERR_INVALID_ARGUMENT, w + ": null result");
+  if (!(min_range >= 0.0)) return e->fail(FVH_ERR_INVALID_ARGUMENT, w + ": min_range must be >= 0");
+  if (!std::isfinite(max_range) || max_range < min_range) return e->fail(FVH_ERR_INVALID_ARGUMENT, w + ": max_range must be finite and >= min_range");
+  if (max_range / vm.res > 4096.0) return e->fail(FVH_ERR_INVALID_ARGUMENT, w + ": max_range is more than 4096 voxels (a lane would walk more than 12,291 cells)");
+  if (!(max_m2 >= 0.0)) return e->fail(FVH_ERR_INVALID_ARGUMENT, w + ": max_m2 must be >= 0");
+  return FVH_OK;
+}
+
+// n segments origin3 -> d_xyz[i] (device, `stride` floats apart; `order`: the walk order or null), both at pose T16, against `vm`: the cast
+// kernel and ONE readback of the struct (+ the per-ray rows that were asked for). Nothing of the engine or the map is written; the scratch is
+// the map's own. Arguments checked by map_cast_check. *overflowed: the map's table had dropped points (a hint-sized batch build): `out` is
+// then not valid, the caller rebuilds the map and calls again.
+int map_cast_run(Engine* e, VoxelMapDev& vm, const float* d_xyz, int stride, int n, const int* order, const double* T16, const double* origin3, double min_range, double max_range,
+                 int min_points, double max_m2, fvh_ray_cast* out, int* hit, int* cell3, double* range, double* m2, bool* overflowed) {
+  *overflowed = false;
+  std::memset(out, 0, sizeof(*out));
+  if (n == 0) return FVH_OK;
+  // {VmCastOut (64 B) | n ranges | n m2 | n hit | 3 n cell}
+  const size_t off_range = 64, off_m2 = off_range + sizeof(double) * (size_t)n, off_hit = off_m2 + sizeof(double) * (size_t)n, off_cell = off_hit + sizeof(int) * (size_t)n;
+  HIP_OR_FAIL(e, vm.cast_buf.ensure(off_cell + sizeof(int) * 3 * (size_t)n));
+  char* base = vm.cast_buf.as<char>();
+  VmCastOut* d_out = reinterpret_cast<VmCastOut*>(base);
+  double* d_range = range ? reinterpret_cast<double*>(base + off_range) : nullptr;
+  double* d_m2 = m2 ? reinterpret_cast<double*>(base + off_m2) : nullptr;
+  int* d_hit = hit ? reinterpret_cast<int*>(base + off_hit) : nullptr;
+  int* d_cell = cell3 ? reinterpret_cast<int*>(base + off_cell) : nullptr;
+  HIP_OR_FAIL(e, hipMemsetAsync(d_out, 0, sizeof(VmCastOut), e->stream));
+  VmCast cp;
+  cp.T = pose_from_colmajor16(T16);
+  const double zero3[3] = {0.0, 0.0, 0.0};
+  for (int a = 0; a < 3; a++) cp.origin[a] = clear_rays_origin_axis(cp.T.r + 3 * a, origin3 ? origin3 : zero3, cp.T.t[a]);
+  cp.res = vm.res; cp.min_range = min_range; cp.max_range = max_range; cp.max_m2 = max_m2; cp.min_points = min_points;
+  {
+    ProfScope ps(e, "map_raycast");
+    vm_raycast_kernel<<<(n + 255) / 256, 256, 0, e->stream>>>(d_xyz, stride, n, order, cp, vm.keys_cur(), vm.capacity - 1, vm.table.as<uint4>(), vm.has_bitmap ? vm.grid.as<VmGrid>() : nullptr,
+                                                              vm.has_bitmap ? vm.bitmap.as<unsigned long long>() : nullptr, vm.counters_cur(), d_hit, d_cell, d_range, d_m2, d_out);
+  }
+  HIP_OR_FAIL(e, hipGetLastError());
+  HIP_OR_FAIL(e, hipMemcpyAsync(out, d_out, sizeof(*out), hipMemcpyDeviceToHost, e->stream));
+  if (hit) HIP_OR_FAIL(e, hipMemcpyAsync(hit, d_hit, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, e->stream));
+  if (cell3) HIP_OR_FAIL(e, hipMemcpyAsync(cell3, d_cell, sizeof(int) * 3 * (size_t)n, hipMemcpyDeviceToHost, e->stream));
+  if (range) HIP_OR_FAIL(e, hipMemcpyAsync(range, d_range, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, e->stream));
+  if (m2) HIP_OR_FAIL(e, hipMemcpyAsync(m2, d_m2, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, e->stream));
+  HIP_OR_FAIL(e, hipStreamSynchronize(e->stream));
+  if (out->n_rays < 0) { *overflowed = true; std::memset(out, 0, sizeof(*out)); }
+  return FVH_OK;
+}
+
 // ---- snapshots of the live map (fvh_vgicp_voxelmap_export / _import / _merge_from; kernels_voxelmap.hpp: "snapshots") ------------------
 // A snapshot is the header {resolution, mode, num_inserts = epoch, num_points, num_voxels} and per voxel {coords[3], sums[10], age}, rows
 // in ascending packed-key order. Rows ADD into a live map of the same grid: import (host rows) and merge_from (another handle's map, read

@@ -125,6 +125,9 @@ struct VoxelMapDev {
   // fvh_*_score_source / _score_cloud (host_incmap.inc.hpp: map_score_run): {VmScoreOut | chunk sums | 3 n terms | n best m2 | n found | n best}, and host
   // points on their way in. Its own: the Engine-wide staging and sort scratch may belong to a preparation on the second stream
   DevBuf score_buf, score_xyz;
+  // fvh_*_cast_rays_source / _cast_rays_cloud (host_incmap.inc.hpp: map_cast_run): {VmCastOut | n ranges | n m2 | n hit | 3 n cell}. Its own for the
+  // same reason; host endpoints on their way in are staged in score_xyz (both calls are read-only and synchronise before they return)
+  DevBuf cast_buf;
   DevBuf keys[2];   // voxel keys, double buffered: keys[cur] belongs to the live map, the other one is what the next build fills
   DevBuf counters;  // 2 sets of 16 ints, [0] num_voxels [1] dropped; set `cur` belongs to the live map
   int cur = 0;
@@ -156,7 +159,7 @@ struct VoxelMapDev {
   std::vector<int> h_occupied;
   std::unordered_map<int, int> bucket_to_index;
   void invalidate() { valid = false; host_valid = false; has_bitmap = false; is_shard = false; has_canon = false; }
-  void release() { table.release(); acc.release(); occupied.release(); compact_pts.release(); compact_cov.release(); counters.release(); keys[0].release(); keys[1].release(); bitmap.release(); grid.release(); region.release(); canon.release(); compat_keys.release(); compat_idx.release(); compat_seg.release(); compat_hist.release(); score_buf.release(); score_xyz.release(); inc.release(); clean_cap = 0; has_bitmap = false; is_shard = false; has_canon = false; }
+  void release() { table.release(); acc.release(); occupied.release(); compact_pts.release(); compact_cov.release(); counters.release(); keys[0].release(); keys[1].release(); bitmap.release(); grid.release(); region.release(); canon.release(); compat_keys.release(); compat_idx.release(); compat_seg.release(); compat_hist.release(); score_buf.release(); score_xyz.release(); cast_buf.release(); inc.release(); clean_cap = 0; has_bitmap = false; is_shard = false; has_canon = false; }
 };
 
 struct Profiler {

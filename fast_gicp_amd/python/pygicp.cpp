@@ -345,6 +345,38 @@ static void def_incremental_target(PyClass& c) {
         return d;
       }, py::arg("pose"), py::arg("neighbors") = 1 /* DIRECT7 */, py::arg("min_points") = 1, py::arg("max_m2") = std::numeric_limits<double>::infinity(), py::arg("score_scale") = 1.0,
          py::arg("per_point") = false)
+      // what the target voxel map (batch or incremental) says a sensor at `pose` should see along each ray (fvh_*_cast_rays_cloud / _source;
+      // read-only): rays run from `origin` (scan frame, None: the origin) to `endpoints` (m x 3, scan frame; None: the source points). -> dict
+      // of the counts, hit_ratio, and with per_ray the arrays hit (int32), cell (m x 3 int32), range and m2 (float64), one row per ray
+      .def("cast_rays", [](Reg& v, const Mat4& pose, const py::object& endpoints, const py::object& origin, double min_range, double max_range, int min_points, double max_m2, bool per_ray) {
+        std::array<double, 3> o3{};
+        const double* o = nullptr;
+        if (!origin.is_none()) {
+          const auto oa = origin.cast<py::array_t<double, py::array::c_style | py::array::forcecast>>();
+          if (oa.size() != 3) throw std::invalid_argument("cast_rays: origin must have 3 elements");
+          std::copy(oa.data(), oa.data() + 3, o3.begin());
+          o = o3.data();
+        }
+        fast_gicp::RayCast s;
+        if (endpoints.is_none()) {
+          s = v.castRaysToSource(numpy2mat4(pose), o, min_range, max_range, min_points, max_m2, per_ray);
+        } else {
+          const auto e = endpoints.cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
+          if (e.size() % 3) throw std::invalid_argument("cast_rays: endpoints must be m x 3");
+          s = v.castRays(numpy2mat4(pose), std::vector<float>(e.data(), e.data() + e.size()), o, min_range, max_range, min_points, max_m2, per_ray);
+        }
+        py::dict d;
+        d["n_rays"] = s.n_rays; d["n_used"] = s.n_used; d["n_hit"] = s.n_hit; d["n_hit_at_origin"] = s.n_hit_at_origin; d["n_cells"] = s.n_cells;
+        d["hit_ratio"] = s.hitRatio();
+        if (per_ray) {
+          d["hit"] = py::array_t<int>((py::ssize_t)s.hit.size(), s.hit.data());
+          d["cell"] = py::array_t<int>(std::vector<py::ssize_t>{(py::ssize_t)s.hit.size(), 3}, s.cell.data());
+          d["range"] = py::array_t<double>((py::ssize_t)s.range.size(), s.range.data());
+          d["m2"] = py::array_t<double>((py::ssize_t)s.m2.size(), s.m2.data());
+        }
+        return d;
+      }, py::arg("pose"), py::arg("endpoints") = py::none(), py::arg("origin") = py::none(), py::arg("min_range") = 0.0, py::arg("max_range") = 100.0, py::arg("min_points") = 1,
+         py::arg("max_m2") = std::numeric_limits<double>::infinity(), py::arg("per_ray") = true)
       // the map as the handle's target cloud too (one point per voxel with >= min_points points; a snapshot): get_fitness_score() and
       // align_best() then work in this mode. -> number of points
       .def("target_cloud_from_map", [](Reg& v, int min_points) { return v.targetCloudFromMap(min_points); }, py::arg("min_points") = 1)

@@ -561,6 +561,15 @@ struct MapScore {
   double tp() const { return n_used ? sum_score_all / n_used : std::numeric_limits<double>::quiet_NaN(); }             // transform probability
 };
 
+/// what castRays() / castRaysToSource() report (C ABI: fvh_ray_cast + the per-ray rows): what the target voxel map says a sensor should see
+struct RayCast {
+  int n_rays = 0, n_used = 0, n_hit = 0, n_hit_at_origin = 0;
+  long long n_cells = 0;
+  std::vector<int> hit, cell;      // with per_ray: hit one row per ray in input order (1, 0 no hit, -1 skipped), cell three per ray
+  std::vector<double> range, m2;   // ... the range of the hit in metres and its squared Mahalanobis distance (+inf without a hit, NaN when skipped)
+  double hitRatio() const { return n_used ? (double)n_hit / n_used : std::numeric_limits<double>::quiet_NaN(); }  // share of used rays that hit the map
+};
+
 /// A snapshot of an incremental target map (FastVGICPCuda / NDTCuda exportTargetMap / importTargetMap; C ABI: fvh_vgicp_voxelmap_export /
 /// _import, fvh_ndt_voxelmap_export / _import): per voxel coords[3], the device's ten fp64 sums and an age, rows in ascending packed-key
 /// order (z-major, then y, then x).
@@ -645,6 +654,8 @@ struct MapCalls<fvh_vgicp> {
   static int transform(fvh_vgicp* h, const double* T16, int* rows_skipped) { return fvh_vgicp_transform_map(h, T16, rows_skipped); }
   static int target_from_map(fvh_vgicp* h, int min_points, int* num_points) { return fvh_vgicp_target_from_map(h, min_points, num_points); }
   static int num_source_points(fvh_vgicp* h, int* n) { return fvh_vgicp_get_num_source_points(h, n); }
+  static int cast_rays_source(fvh_vgicp* h, const double* T16, const double* origin3, double min_range, double max_range, int min_points, double max_m2, fvh_ray_cast* out, int* hit, int* cell3, double* range, double* m2) { return fvh_vgicp_cast_rays_source(h, T16, origin3, min_range, max_range, min_points, max_m2, out, hit, cell3, range, m2); }
+  static int cast_rays_cloud(fvh_vgicp* h, const float* xyz, int n, const double* T16, const double* origin3, double min_range, double max_range, int min_points, double max_m2, fvh_ray_cast* out, int* hit, int* cell3, double* range, double* m2) { return fvh_vgicp_cast_rays_cloud(h, xyz, n, 3, 0, T16, origin3, min_range, max_range, min_points, max_m2, out, hit, cell3, range, m2); }
   static int score_source(fvh_vgicp* h, const double* T16, int neighbors, int min_points, double max_m2, double score_scale, fvh_map_score* out, int* found, int* best, double* best_m2) { return fvh_vgicp_score_source(h, T16, neighbors, min_points, max_m2, score_scale, out, found, best, best_m2); }
 };
 template <>
@@ -660,6 +671,8 @@ struct MapCalls<fvh_ndt> {
   static int transform(fvh_ndt* h, const double* T16, int* rows_skipped) { return fvh_ndt_transform_map(h, T16, rows_skipped); }
   static int target_from_map(fvh_ndt* h, int min_points, int* num_points) { return fvh_ndt_target_from_map(h, min_points, num_points); }
   static int num_source_points(fvh_ndt* h, int* n) { return fvh_ndt_get_num_source_points(h, n); }
+  static int cast_rays_source(fvh_ndt* h, const double* T16, const double* origin3, double min_range, double max_range, int min_points, double max_m2, fvh_ray_cast* out, int* hit, int* cell3, double* range, double* m2) { return fvh_ndt_cast_rays_source(h, T16, origin3, min_range, max_range, min_points, max_m2, out, hit, cell3, range, m2); }
+  static int cast_rays_cloud(fvh_ndt* h, const float* xyz, int n, const double* T16, const double* origin3, double min_range, double max_range, int min_points, double max_m2, fvh_ray_cast* out, int* hit, int* cell3, double* range, double* m2) { return fvh_ndt_cast_rays_cloud(h, xyz, n, 3, 0, T16, origin3, min_range, max_range, min_points, max_m2, out, hit, cell3, range, m2); }
   static int score_source(fvh_ndt* h, const double* T16, int neighbors, int min_points, double max_m2, double score_scale, fvh_map_score* out, int* found, int* best, double* best_m2) { return fvh_ndt_score_source(h, T16, neighbors, min_points, max_m2, score_scale, out, found, best, best_m2); }
 };
 }  // namespace detail
@@ -778,7 +791,44 @@ protected:
   }
   /// ... at the final transformation of the last align()
   MapScore scoreTarget() { return scoreTarget(this->final_transformation_); }
+  /// What the target voxel map (batch or incremental) says a sensor at pose T should see along each ray (fvh_*_cast_rays_cloud through
+  /// detail::MapCalls, read-only on the handle; public on the classes that own a voxel map: FastVGICPCuda, FastVGICP, NDTCuda). A ray is
+  /// the segment from origin3 (scan frame; null: the origin) to an endpoint (endpoints_xyz: three floats per ray, scan frame); it is walked
+  /// through the grid, in every voxel with >= min_points points its point of smallest squared Mahalanobis distance to the voxel's Gaussian
+  /// is found, and the first voxel where that is <= max_m2 (and beyond min_range metres) is the hit. Rays longer than max_range are
+  /// skipped. per_ray: also hit / cell / range / m2 per ray. The intended loop: align, castRaysToSource(T) and compare with the measured
+  /// ranges, clearTargetAlongRays(T), insertSourceIntoTarget(T).
+  RayCast castRays(const Matrix4f& T, const std::vector<float>& endpoints_xyz, const double* origin3 = nullptr, double min_range = 0.0, double max_range = 100.0, int min_points = 1,
+                   double max_m2 = std::numeric_limits<double>::infinity(), bool per_ray = true) {
+    if (endpoints_xyz.size() % 3) throw std::invalid_argument("castRays: endpoints_xyz must hold three floats per ray");
+    return cast_rays(T, endpoints_xyz.data(), (int)(endpoints_xyz.size() / 3), false, origin3, min_range, max_range, min_points, max_m2, per_ray);
+  }
+  /// ... with the handle's current source points as the endpoints (fvh_*_cast_rays_source): the rows are sized by the handle's count
+  RayCast castRaysToSource(const Matrix4f& T, const double* origin3 = nullptr, double min_range = 0.0, double max_range = 100.0, int min_points = 1,
+                           double max_m2 = std::numeric_limits<double>::infinity(), bool per_ray = true) {
+    return cast_rays(T, nullptr, 0, true, origin3, min_range, max_range, min_points, max_m2, per_ray);
+  }
   bool hasIncrementalTarget() const { return incremental_target_; }
+private:
+  RayCast cast_rays(const Matrix4f& T, const float* xyz, int n, bool to_source, const double* origin3, double min_range, double max_range, int min_points, double max_m2, bool per_ray) {
+    double T16[16];
+    Isometry3d::from(T).to_colmajor16(T16);
+    RayCast out;
+    fvh_ray_cast s;
+    int rows = n;
+    if (to_source) { rows = 0; if (per_ray) call(Map::num_source_points(core_, &rows), "get_num_source_points"); }
+    const size_t m = per_ray ? (size_t)rows : 0;
+    out.hit.resize(m); out.cell.resize(3 * m); out.range.resize(m); out.m2.resize(m);
+    int* hit = m ? out.hit.data() : nullptr;
+    int* cell = m ? out.cell.data() : nullptr;
+    double* range = m ? out.range.data() : nullptr;
+    double* m2 = m ? out.m2.data() : nullptr;
+    if (to_source) call(Map::cast_rays_source(core_, T16, origin3, min_range, max_range, min_points, max_m2, &s, hit, cell, range, m2), "cast_rays_source");
+    else call(Map::cast_rays_cloud(core_, n ? xyz : nullptr, n, T16, origin3, min_range, max_range, min_points, max_m2, &s, hit, cell, range, m2), "cast_rays_cloud");
+    out.n_rays = s.n_rays; out.n_used = s.n_used; out.n_hit = s.n_hit; out.n_hit_at_origin = s.n_hit_at_origin; out.n_cells = s.n_cells;
+    return out;
+  }
+protected:
   /// The live map becomes the handle's target CLOUD as well: one point per voxel with >= min_points points (the voxel's mean; VGICP: + its
   /// covariance), rows in ascending key order -- the row order of exportTargetMap(). getFitnessScore() and alignBest() then work on the map.
   /// A snapshot: call it again after an insert or a prune. The map stays the align target. Returns the number of points.
@@ -1041,6 +1091,8 @@ public:
   using Base::pruneTarget;
   using Base::clearTargetAlongRays;
   using Base::scoreTarget;
+  using Base::castRays;
+  using Base::castRaysToSource;
   using Base::hasIncrementalTarget;
   using Base::targetCloudFromMap;
 
@@ -1226,6 +1278,8 @@ class FastVGICP : public FastGICP<PointSource, PointTarget> {
 public:
   using PointCloudTargetConstPtr = typename Base::PointCloudTargetConstPtr;
   using Base::scoreTarget;  // (this class owns a voxel map; FastGICP does not)
+  using Base::castRays;
+  using Base::castRaysToSource;
 
   explicit FastVGICP(int device = 0) : Base(device) {  // fast_vgicp_impl.hpp:19-25
     this->calls_ = &detail::kVgicpVoxelCalls;  // what it replaces in FastGICP: voxel correspondences, and the calls only they have
@@ -1305,6 +1359,8 @@ public:
   using Base::pruneTarget;
   using Base::clearTargetAlongRays;
   using Base::scoreTarget;
+  using Base::castRays;
+  using Base::castRaysToSource;
   using Base::hasIncrementalTarget;
   using Base::targetCloudFromMap;
   using Base::exportTargetMap;

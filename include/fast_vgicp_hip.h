@@ -372,6 +372,63 @@ typedef struct fvh_map_score {
 } fvh_map_score;
 int fvh_vgicp_score_source(fvh_vgicp* h, const double* T16, int neighbors, int min_points, double max_m2, double score_scale, fvh_map_score* out, int* found, int* best, double* best_m2);
 int fvh_vgicp_score_cloud(fvh_vgicp* h, const float* xyz, int n, int stride_floats, int on_device, const double* T16, int neighbors, int min_points, double max_m2, double score_scale, fvh_map_score* out, int* found, int* best, double* best_m2);
+/* new: RAY CASTING into the target voxel map: the first hit per ray, on the device. Every call above asks a question about a measured point;
+ * this one asks the map what a sensor at a pose should see along a ray (OctoMap: castRay; NDT-OM: the maximum-likelihood point along a ray):
+ * a predicted scan or depth image of the map, change detection BEFORE carving (the expected range against the measured one: a surface in
+ * front of a return is what clear_rays will delete), occlusion and visibility tests, a localisation check that does not use the scan's own
+ * points. A walk that stopped at the first occupied CELL would give ranges quantised to the voxel size; here the hit test uses the voxel's
+ * Gaussian: inside each occupied cell the ray's point of smallest squared Mahalanobis distance to the Gaussian is found in closed form, and
+ * the cell is a hit only if that distance is <= max_m2. The map is the handle's CURRENT target voxel map, batch or incremental, of any
+ * accumulation mode and precision: the call reads the voxel records {num_points, mean, covariance} and nothing else.
+ *   A ray is the SEGMENT from the sensor origin to an endpoint row, exactly the segments clear_rays_* walks (a caller with directions passes
+ *   origin + length * unit direction).
+ *   _source   the endpoints are the handle's current source points (no covariances needed), walked in the source's Morton order when it has one.
+ *   _cloud    ... xyz: n points on the host or the device (on_device), stride_floats 3 or 4.
+ *   T16       4x4 double column-major, scan frame -> map frame (R, t); origin3 the sensor origin in the SCAN frame, NULL = (0, 0, 0).
+ *   min_range metres: it does NOT skip a ray, it bounds where a hit may lie (t_lo below).  max_range: metres; longer rays are skipped.
+ *   min_points  voxels with fewer points are not candidates (<= 1: every voxel).  max_m2: the hit bound (+inf allowed).
+ *   out       required.  hit, cell3 (3 int per row), range, m2: host arrays of n rows in INPUT order, each may be NULL; with all four NULL the
+ *             call reads back sizeof(fvh_ray_cast) bytes and nothing else.
+ * The contract (res = the map's resolution; everything fp64 unless stated; no product is contracted into a sum anywhere):
+ *   origin, endpoint, range   word for word those of clear_rays_*: o' = (float)(R o + t), p' = (float)(R p + t), d_m = (double)p' - (double)o'
+ *             per axis, r = sqrt((dx*dx + dy*dy) + dz*dz).
+ *   skipped   when a coordinate of p is non-finite, r == 0, r > max_range, or the cell of o' or of p' is outside |c| < 2^20 - 4096.
+ *             t_lo = min_range / r.
+ *   walk      that of clear_rays_* with end_margin = 0: the same a, b, d, tMax, tDelta, tie order (x before y before z) and N; a cell is
+ *             visited only while t_in < 1.0. Every visited cell has a parameter interval: t_in = 0 for the first cell, otherwise the tMax
+ *             value the step into the cell took; t_out = min(the smallest tMax on leaving, 1.0), or 1.0 for the cell visited after N steps.
+ *             At most N + 1 cells, in walk order; the walk ends at the first hit.
+ *   candidate a visited cell that exists in the map, whose record's num_points >= min_points, and with t_out > t_lo. A live occupancy
+ *             bitmap may answer for absent cells first; the result is the same with and without it. lo = max(t_in, t_lo).
+ *   closest approach   e = (double)o' - (double)mean per axis; the record's six covariance floats widened to fp64; the adjugate terms
+ *             a00 .. a22 and det of the score_* contract above; the bilinear form
+ *               B(u, v) = (((ux*vx)*a00 + (uy*vy)*a11) + (uz*vz)*a22) + ((((ux*vy + uy*vx)*a01) + ((ux*vz + uz*vx)*a02)) + ((uy*vz + uz*vy)*a12)),
+ *             den = B(d_m, d_m), num = B(d_m, e). The record is SINGULAR for this ray if det is not > 0 or not finite, den is not > 0 or not
+ *             finite, or num is not finite: then s = lo and m2 = +inf. Otherwise s* = (-num) / den; s = lo if s* < lo, t_out if
+ *             s* > t_out, else s*; x = e + s * d_m per axis (the product, then the sum); m2 = the score_* quotient form of x (q / det, a
+ *             negative quotient 0, +inf when q is not finite).
+ *   hit       the first candidate in walk order with m2 <= max_m2 (+inf <= +inf holds: with max_m2 = +inf the first candidate cell stops
+ *             the ray, a singular one at its entry; with a finite bound singular records are passed through).
+ *   per ray   hit: hit = 1, cell3 = the hit cell, range = s * r, m2 = that m2.  used, no hit: 0, (0, 0, 0), +inf, +inf.  skipped: -1,
+ *             (0, 0, 0), NaN, NaN.
+ * The counts are integers (order does not matter); no floating-point atomics. Nothing of the handle is written: the map (an export before and
+ * after is byte-equal), stored correspondences, the clouds and their Morton order; an align after the call gives the bits it gave before. The
+ * scratch is the call's own, so it is legal between prepare_source* and adopt_prepared_source. One exception, as for score_*: a batch map
+ * whose hint-sized table had dropped points is rebuilt at the safe size first. The call synchronises once.
+ * Refusals (the handle stays usable; host input is validated before anything is queued): no target voxel map, an align_async in flight,
+ * _source without a source cloud (FVH_ERR_BAD_STATE); a NULL or non-finite T16, a non-finite origin3, NULL out, min_range < 0 or NaN,
+ * max_range not finite or < min_range or > 4096 * res (one lane then walks at most 3 * 4097 = 12,291 cells), max_m2 NaN or < 0, n < 0, NULL
+ * xyz with n > 0, a stride other than 3 or 4 (FVH_ERR_INVALID_ARGUMENT); multi-GPU handles -- communicator, peers, tile, map sharding --
+ * (FVH_ERR_UNSUPPORTED). n == 0: FVH_OK, all zeros. */
+typedef struct fvh_ray_cast {
+  int n_rays;         /* rows offered */
+  int n_used;         /* not skipped */
+  int n_hit;          /* used rays with a hit */
+  int n_hit_at_origin;/* ... whose hit is in the origin's own cell (the sensor sits inside map matter) */
+  long long n_cells;  /* cells visited over all used rays, the hit cell included (integer: order does not matter) */
+} fvh_ray_cast;
+int fvh_vgicp_cast_rays_source(fvh_vgicp* h, const double* T16, const double* origin3, double min_range, double max_range, int min_points, double max_m2, fvh_ray_cast* out, int* hit, int* cell3, double* range, double* m2);
+int fvh_vgicp_cast_rays_cloud(fvh_vgicp* h, const float* xyz, int n, int stride_floats, int on_device, const double* T16, const double* origin3, double min_range, double max_range, int min_points, double max_m2, fvh_ray_cast* out, int* hit, int* cell3, double* range, double* m2);
 /* Snapshots of the live incremental map: write it out, bring it back, add another map to it.
  * A snapshot is a header -- resolution, mode (0 additive, 2 multiplicative), num_inserts (the map's insert count), num_points, num_voxels --
  * and per voxel coords[3] (int32), sums[10] (fp64: {sum p | sum C^-1 p (3), sum C | sum C^-1 (6), count}, the device's own sums) and an age
@@ -650,6 +707,9 @@ int fvh_ndt_clear_rays_cloud(fvh_ndt* h, const float* xyz, int n, int stride_flo
 /* a posed scan scored against the target voxel map, as fvh_vgicp_score_source / _cloud above, argument for argument and under the same contract */
 int fvh_ndt_score_source(fvh_ndt* h, const double* T16, int neighbors, int min_points, double max_m2, double score_scale, fvh_map_score* out, int* found, int* best, double* best_m2);
 int fvh_ndt_score_cloud(fvh_ndt* h, const float* xyz, int n, int stride_floats, int on_device, const double* T16, int neighbors, int min_points, double max_m2, double score_scale, fvh_map_score* out, int* found, int* best, double* best_m2);
+/* rays cast into the target voxel map, as fvh_vgicp_cast_rays_source / _cloud above, argument for argument and under the same contract */
+int fvh_ndt_cast_rays_source(fvh_ndt* h, const double* T16, const double* origin3, double min_range, double max_range, int min_points, double max_m2, fvh_ray_cast* out, int* hit, int* cell3, double* range, double* m2);
+int fvh_ndt_cast_rays_cloud(fvh_ndt* h, const float* xyz, int n, int stride_floats, int on_device, const double* T16, const double* origin3, double min_range, double max_range, int min_points, double max_m2, fvh_ray_cast* out, int* hit, int* cell3, double* range, double* m2);
 int fvh_ndt_voxelmap_export(fvh_ndt* h, int* num_voxels, double* resolution, int* mode, int* num_inserts, long long* num_points, int* coords3, double* sums10, unsigned* ages);
 int fvh_ndt_voxelmap_import(fvh_ndt* h, int n, const int* coords3, const double* sums10, const unsigned* ages, double resolution, int mode, int num_inserts, long long num_points);
 int fvh_ndt_voxelmap_merge_from(fvh_ndt* h, fvh_ndt* other);
